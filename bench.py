@@ -43,6 +43,13 @@ second small all-reduce sums the shards' cost and landmark step norm.  Rank 0 al
 unsharded C4 problem on its own GPU after the timed region (``c4_single_gpu_ms``).
 
 Prints ONE JSON line (rank 0).
+
+``--dump-outputs DIR`` (after the timed region): what the last timed solve handed its caller --
+``cost_history``, ``pcg_iterations`` and ``pcg_relative_residual`` per iteration, the solved
+``poses`` (rows R | t) and ``points`` in problem order -- as DIR/<name>.npy, float64, at most
+64 MB in all (beyond that a fixed seeded sample of rows, numbered in ``<name>_rows``).  The
+inputs are a function of the arguments alone (seeded generator), so two builds can be compared
+array by array.
 """
 import argparse
 import hashlib
@@ -57,7 +64,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-HBM_PEAK_GBS = 8000.0           # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+HBM_PEAK_GBS = 8000.0           # MI355X: HBM3E 8 TB/s spec
 PCG_TOL = 1e-12
 PCG_MAX = 1000
 
@@ -174,7 +181,7 @@ def cold_solves(dev, start, total_iters, fence, warm_solves=1):
     sharded driver) under the reference example's options, until exactly `total_iters` iterations have run (the last
     solve is cut there).  Timed per solve: start cost + iterations + snapshots + final restore + the synchronisation that
     ends it; NOT timed: ps_reset_solver_state and the upload of the start parameters.
-    -> dict(seconds, iterations, solves, per_call_ms (median by position in the solve), pcg_iters, cost_history)."""
+    -> dict(seconds, iterations, solves, per_call_ms (median by position in the solve), pcg_iters, cost_history, last_solve)."""
     from pyslam_amd.problem import device_solve
     core = dev.dev if hasattr(dev, 'dev') else dev
 
@@ -189,7 +196,7 @@ def cold_solves(dev, start, total_iters, fence, warm_solves=1):
         t0 = time.perf_counter()
         hist, stats = device_solve(dev, opt, call_ms=call_ms)
         fence()                                           # (the final restore of the best parameters is enqueue-only)
-        return time.perf_counter() - t0, hist, [(ms, st[0]) for ms, st in zip(call_ms, stats)]
+        return time.perf_counter() - t0, hist, [(ms, st[0]) for ms, st in zip(call_ms, stats)], stats
 
     for _ in range(max(1, warm_solves)):
         one(None)
@@ -198,7 +205,7 @@ def cold_solves(dev, start, total_iters, fence, warm_solves=1):
     gc_was = gc.isenabled()
     gc.disable()              # (as timeit does: a collection of the interpreter inside a 1.3 ms solve is not the solver's time)
     while its < total_iters:
-        dt, hist, calls = one(total_iters - its)
+        dt, hist, calls, last_stats = one(total_iters - its)
         sec += dt; its += len(calls); solves += 1
         per_solve.append(round(dt * 1e3, 4)); per_solve_its.append(len(calls))
         if hist0 is None:
@@ -214,7 +221,56 @@ def cold_solves(dev, start, total_iters, fence, warm_solves=1):
             # exactly K iterations, as the bench contract wants it; one slow solve moves the mean, not this)
             'ms_median_of_solves': round(float(np.median([m / max(n, 1) for m, n in zip(per_solve, per_solve_its)])), 4),
             'per_call_ms': [round(float(np.median(c)), 4) for c in calls_by_pos],      # median over the solves, by call index
-            'pcg_iters': pcg0, 'cost_history': hist0}
+            'pcg_iters': pcg0, 'cost_history': hist0,
+            'last_solve': {'cost_history': hist, 'stats': last_stats}}        # (what the last timed solve returned: --dump-outputs)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def fit_outputs(arrays, max_bytes=DUMP_MAX_BYTES):
+    """float64 copies of `arrays` that together take at most `max_bytes`: the smallest first and whole while they fit; an array
+    that does not is cut to a sample of its rows drawn by a fixed seed (a function of its row count only, so two runs draw the
+    same rows), in ascending order, the row numbers beside it as `<name>_rows`."""
+    out, left = {}, max_bytes
+    for name in sorted(arrays, key=lambda k: (np.asarray(arrays[k]).size, k)):
+        a = np.ascontiguousarray(arrays[name], dtype=np.float64)
+        if a.nbytes > left and a.ndim > 0 and len(a) > 0:
+            k = min(len(a), left // (a.nbytes // len(a) + 8))           # (+ 8 bytes: the row number)
+            rows = np.sort(np.random.default_rng(0).choice(len(a), size=k, replace=False))
+            a = a[rows]
+            out[name + '_rows'] = rows.astype(np.float64)
+            left -= out[name + '_rows'].nbytes
+        if a.nbytes > left:
+            raise ValueError('bench.py: {} ({} bytes) does not fit the {}-byte output budget'.format(name, a.nbytes, max_bytes))
+        out[name] = a
+        left -= a.nbytes
+    return out
+
+
+def solved_params(dev, dist, lp_full, world, order):
+    """(poses, points) on the device in the full problem's numbering: a sharded run gathers every rank's landmark rows (a
+    collective: every rank calls it)."""
+    poses, points = dev.get_params()
+    if dist is None or world == 1:
+        return poses, points
+    from pyslam_amd.distributed import landmark_owner_lists
+    owners = landmark_owner_lists(lp_full, world, order)
+    parts = [None] * world
+    dist.all_gather_object(parts, points)
+    full = np.empty((lp_full.num_points, 3))
+    for r in range(world):
+        full[owners[r]] = np.asarray(parts[r]).reshape(-1, 3)
+    return poses, full
+
+
+def dump_outputs(outdir, arrays):
+    """DIR/<name>.npy for every array of fit_outputs(arrays); -> {name: shape}."""
+    os.makedirs(outdir, exist_ok=True)
+    fitted = fit_outputs(arrays)
+    for name, a in fitted.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in sorted(fitted.items())}
 
 
 def time_steps(dev, steps, warmup, fence):
@@ -510,7 +566,11 @@ def main():
     ap.add_argument('--shard-order', default='first_pose', choices=['first_pose', 'index'],
                     help="how landmarks are cut into shards (pyslam_amd/distributed.py: landmark_owner_lists)")
     ap.add_argument('--exchange', default=None, choices=['allreduce', 'segments'])
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed solve returned as DIR/<name>.npy (module docstring)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -573,6 +633,12 @@ def main():
     # (the warm-up solves run inside cold_solves, before its clock; their Schur timings are discarded below)
     cold = cold_solves(dev, start, args.steps, fence, warm_solves=warm_solves)
     stages = dev.stage_times(reset=True)
+    outputs = None
+    if args.dump_outputs:                                    # (before the untimed solves below move the parameters)
+        poses, points = solved_params(dev, dist, lp_full, world, args.shard_order)
+        last = cold['last_solve']
+        outputs = {'cost_history': last['cost_history'], 'pcg_iterations': [st[0] for st in last['stats']],
+                   'pcg_relative_residual': [st[1] for st in last['stats']], 'poses': poses, 'points': points}
     dev.set_profiling(0)
     elapsed = cold['seconds']
     if dist is not None:
@@ -711,6 +777,8 @@ def main():
                     line['cold_solve_wall_ms']['C4'] = {'run': w4['first_in_process'], 'note': w4['note']}
         if not args.no_cpu_baseline and world == 1:
             line['cpu_baseline'] = cpu_baseline(lp)
+        if outputs is not None:
+            line['dumped_outputs'] = dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(line))
     if dist is not None:
         dist.barrier()

@@ -1,7 +1,7 @@
 """C3 on the host: the reference-faithful linear solve (scipy spsolve of the full normal equations, reference
 problem.py:186) next to the CPU Schur complement the bench's cpu_baseline uses.  Minutes of CPU time (SuperLU fill)."""
 import os, sys, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import scipy.sparse.linalg as spla
 from oracle import gn_oracle as orc

@@ -113,3 +113,30 @@ def test_committed_line_names_the_top_kernel_of_the_committed_kernel_stats():
     assert 'value_median' in line and line['value_median']['ms_per_iteration_median_of_solves'] > 0
     top4, total4 = _largest_iteration_kernel(os.path.join(REPO, 'profiles', 'r06_c4_kernel_stats.csv'))
     assert line['c4_single_gpu']['roofline']['kernel'] == top4, (line['c4_single_gpu']['roofline']['kernel'], total4)
+
+
+def test_dumped_outputs_fit_the_budget_with_a_fixed_sample():
+    """--dump-outputs: arrays that fit are written whole and as float64; beyond the budget the largest is cut to a sample of its
+    rows that depends on its row count only (the same rows in every run), numbered beside it."""
+    import bench
+    small = {'cost_history': [3.0, 2.0, 1.0], 'poses': np.arange(24.).reshape(2, 12), 'points': np.arange(30.).reshape(10, 3)}
+    out = bench.fit_outputs(small)
+    assert sorted(out) == ['cost_history', 'points', 'poses']
+    assert all(a.dtype == np.float64 for a in out.values())
+    assert np.array_equal(out['points'], small['points']) and np.array_equal(out['cost_history'], [3.0, 2.0, 1.0])
+    big = dict(small, points=np.arange(3000.).reshape(1000, 3))
+    cap = 4096
+    a, b = bench.fit_outputs(big, cap), bench.fit_outputs(dict(big), cap)
+    assert sum(x.nbytes for x in a.values()) <= cap
+    assert np.array_equal(a['points_rows'], b['points_rows']) and np.array_equal(a['points'], b['points'])
+    rows = a['points_rows'].astype(np.int64)
+    assert 0 < rows.size < 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a['points'], big['points'][rows]) and np.array_equal(a['poses'], small['poses'])
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+
+
+def test_steps_below_one_are_refused():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and '--steps must be at least 1' in r.stderr

@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.distributed as dist
 os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT='29521', RANK='0', WORLD_SIZE='1')
 torch.cuda.set_device(0)

@@ -1,6 +1,6 @@
 """coarse_auto_hold on / off: per-iteration time and CG iterations of real solves (C2 pose graph, C4 BA), final parameters."""
 import os, sys, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from pyslam_amd import synthetic
 from pyslam_amd.device import DeviceProblem

@@ -1,6 +1,6 @@
 """Explicit two-level PCG: banded factorisation / inverse of the coarse matrix against the dense one (option band_chol)."""
 import os, sys, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from pyslam_amd import synthetic
 from pyslam_amd.device import DeviceProblem

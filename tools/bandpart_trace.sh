@@ -1,12 +1,12 @@
 #!/bin/bash
 # per-kernel durations of the partitioned band factorisation at C2's / C4's coarse sizes (rocprofv3 kernel trace)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-OUT=${GRAFT_REPO_ROOT:-/root/repo}/gpurun_out/bp_trace
-mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o bp -- python ${GRAFT_REPO_ROOT:-/root/repo}/tools/bandpart_probe.py > $OUT/run.txt 2>&1
-python - <<'P'
+OUT=$(mktemp -d); trap 'rm -rf "$OUT"' EXIT       # (the trace is read below and not kept)
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o bp -- python $ROOT/tools/bandpart_probe.py > $OUT/run.txt 2>&1
+OUT=$OUT python - <<'P'
 import csv, glob, os
-out = os.path.join(os.environ.get('GRAFT_REPO_ROOT', '/root/repo'), 'gpurun_out/bp_trace')
+out = os.environ['OUT']
 f = glob.glob(out + '/**/*kernel_trace.csv', recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))

@@ -1,6 +1,6 @@
 """C2 probe: SE(3) pose graph, 10k poses / 50k edges, Huber, prior on pose 0."""
 import os, sys, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from pyslam_amd import synthetic
 from pyslam_amd.device import DeviceProblem

@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel stats (rocprofv3) of cold C3 solves: bash tools/c3_kstats.sh <tag> [cold_probe args]
 TAG=${1:-c3k}; shift
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/$TAG
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/$TAG -o k -- python $ROOT/tools/cold_probe.py 200 50000 6 "$@" > $OUT/run.txt 2>&1

@@ -1,6 +1,6 @@
 """C4-scale probe: 2000 keyframes x 500k landmarks x 10 obs (5 M blocks) on ONE GPU."""
 import os, sys, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from pyslam_amd import synthetic
 from pyslam_amd.device import DeviceProblem

@@ -7,7 +7,7 @@ import __graft_entry__ as _ge
 if not _os.path.exists(_ge.OUT_MEASURE) or _os.path.getmtime(_ge.OUT_MEASURE) < _os.path.getmtime(_ge.SRC):
     _ge.build_measure()
 import os, sys, time, csv
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pyslam_amd import synthetic
 from pyslam_amd.device import DeviceProblem
 lp,_ = synthetic.stereo_ba(200, 50000, 10, 20, seed=0)

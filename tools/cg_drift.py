@@ -10,8 +10,8 @@ component, so it is never reduced while gamma = r.r keeps counting it -- four or
 projection.  delta - beta gamma / alpha is then a difference of quantities polluted by the leaked component: when it
 turns non-positive the device reports a breakdown and RESTARTS from the true residual V^T (g^ - S^ V x~), which is the
 projection (cg_fused_run).  usage: python tools/cg_drift.py [seed]"""
-import sys
-sys.path.insert(0, '/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, scipy.linalg as sl
 from oracle import gn_oracle as orc
 from pyslam_amd import synthetic, losses

@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from pyslam_amd import synthetic
 from pyslam_amd.device import DeviceProblem

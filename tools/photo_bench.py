@@ -1,7 +1,7 @@
 """Dense photometric alignment at 640 x 480: one Gauss-Newton iteration on the MI355X (ps_photometric_iteration,
 host round trip included) vs the numpy product-class evaluate + normal equations on the host."""
 import os, sys, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from pyslam_amd import synthetic
 from pyslam_amd.device import PhotometricDevice

@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ counters of the observation passes (VALU-bound or waiting?): bash tools/pmc_sq.sh <tag> [kf lm]
 TAG=${1:-sq}; KF=${2:-200}; LM=${3:-50000}
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 i=0

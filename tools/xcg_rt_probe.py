@@ -1,7 +1,7 @@
 """Explicit two-level PCG, three launches per iteration against four: C4 (BA, 2000 x 500k) and C2 (10k-pose graph).
 Same iterate, both forms: time per iteration, CG iterations, difference of the steps."""
 import os, sys, time
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from pyslam_amd import synthetic
 from pyslam_amd.device import DeviceProblem
