@@ -508,6 +508,42 @@ int ps_photometric_normal_equations(ps_photo* h, double* H36, double* b6, double
    pyslam/problem.py:362-398), else the cost of the linearisation point (:188-192). */
 int ps_photometric_iteration(ps_photo* h, int32_t split_params, int32_t linesearch, double* dx6, double* cost);
 
+/* Dense RGB-D visual odometry (reference pyslam/pipelines/dense.py, keyframes.py): image pyramids, keyframe pixel
+   tables and the coarse-to-fine tracking of a frame against a keyframe, all on the device.  A handle holds
+   num_slots frames of at most max_height x max_width, each with `levels` pyramid levels (the cv2.pyrDown chain,
+   ((h+1)/2, (w+1)/2) per level); its device memory is fixed at create time.  Every frame of a handle has one size. */
+typedef struct ps_dense ps_dense;
+int ps_dense_create(int32_t levels, int32_t max_height, int32_t max_width, int32_t num_slots, void* hip_stream, ps_dense** out);
+int ps_dense_destroy(ps_dense* h);
+/* Upload a frame into a slot and build its image pyramid (dtype 0: uint8, 1: float64; row-major height x width).
+   The float64 level images are raw / 255. (keyframes.py: compute_image_pyramid).  depth (float64, height x width,
+   NaN / <= 0 = none) may come with the image or later with image == NULL.  No synchronisation: the caller keeps both
+   buffers alive until its next synchronising call (ps_dense_track, a read). */
+int ps_dense_upload(ps_dense* h, int32_t slot, int32_t dtype, int32_t height, int32_t width, const void* image, const double* depth);
+/* Pixel tables of a keyframe slot for the listed levels, exactly as PhotometricResidualSE3's constructor builds them
+   (ps_photo_desc): gradient 0.5 * Sobel, depth level depth[::2^l, ::2^l], RGBDCamera.is_valid_measurement on the
+   level camera, |gradient| >= min_grad, kept pixels in raster order.  cams6: num_levels x (cu cv fu fv w h). */
+int ps_dense_make_tables(ps_dense* h, int32_t slot, int32_t num_levels, const int32_t* levels, const double* cams6,
+                         double intensity_covar, double depth_covar, double min_grad);
+/* Track the frame in track_slot against the keyframe in ref_slot: for each listed level in order, Problem.solve's loop
+   (options: max_iters, min_update_norm, min_cost, min_cost_decrease, allow_nondecreasing_steps, max_nondecreasing_steps,
+   linesearch) on the level's PhotometricResidualSE3 with the (R, t) parameter split; rot_only[k] != 0 holds t constant
+   (H[3:6,3:6] dphi = b[3:6], R <- exp(dphi) R).  The pose (T_track_ref, 12 doubles) carries from level to level on the
+   device; one synchronisation per call.  iterations[k] and cost_history[k * history_cap + 0 .. iterations[k]] per level
+   (history_cap >= max_iters + 2).  Errors as ps_photometric_iteration; pose12_out is then not written. */
+int ps_dense_track(ps_dense* h, int32_t ref_slot, int32_t track_slot, int32_t num_levels, const int32_t* levels,
+                   const int32_t* rot_only, const ps_solve_options* options, int32_t loss_id, double loss_k,
+                   const double* pose12_in, double* pose12_out, int32_t* iterations, double* cost_history, int32_t history_cap);
+/* Read back: level shape; a level's image (what 0, h x w), gradient (1, 2 x h x w: d/du then d/dv) or depth (2, h x w);
+   the number of table pixels of a level and its tables (layout of ps_photo_desc). */
+int ps_dense_level_shape(ps_dense* h, int32_t level, int32_t* height, int32_t* width);
+int ps_dense_read_level(ps_dense* h, int32_t slot, int32_t level, int32_t what, double* out);
+int ps_dense_num_pixels(ps_dense* h, int32_t slot, int32_t level, int32_t* num_pixels);
+int ps_dense_read_tables(ps_dense* h, int32_t slot, int32_t level, int32_t num_pixels, double* pt_ref, double* im_ref,
+                         double* im_jac, double* tri_jac_d);
+/* device memory held by the handle */
+int ps_dense_device_bytes(ps_dense* h, int64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

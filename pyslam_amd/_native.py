@@ -130,6 +130,17 @@ SIGNATURES = {
     'ps_photometric_eval_cost': (C.c_int, [H, c_f64p, C.POINTER(C.c_int64)]),
     'ps_photometric_normal_equations': (C.c_int, [H, c_f64p, c_f64p, c_f64p, C.POINTER(C.c_int64)]),
     'ps_photometric_iteration': (C.c_int, [H, C.c_int32, C.c_int32, c_f64p, c_f64p]),
+    'ps_dense_create': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(H)]),
+    'ps_dense_destroy': (C.c_int, [H]),
+    'ps_dense_upload': (C.c_int, [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, c_f64p]),
+    'ps_dense_make_tables': (C.c_int, [H, C.c_int32, C.c_int32, c_i32p, c_f64p, C.c_double, C.c_double, C.c_double]),
+    'ps_dense_track': (C.c_int, [H, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, C.POINTER(SolveOptions), C.c_int32,
+                                 C.c_double, c_f64p, c_f64p, c_i32p, c_f64p, C.c_int32]),
+    'ps_dense_level_shape': (C.c_int, [H, C.c_int32, c_i32p, c_i32p]),
+    'ps_dense_read_level': (C.c_int, [H, C.c_int32, C.c_int32, C.c_int32, c_f64p]),
+    'ps_dense_num_pixels': (C.c_int, [H, C.c_int32, C.c_int32, c_i32p]),
+    'ps_dense_read_tables': (C.c_int, [H, C.c_int32, C.c_int32, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p]),
+    'ps_dense_device_bytes': (C.c_int, [H, C.POINTER(C.c_int64)]),
     'ps_dense_normal_solve': (C.c_int, [c_f64p, c_f64p, C.c_int32, C.c_int32, c_f64p, c_f64p]),
     'ps_sparse_normal_solve': (C.c_int, [C.c_int32, C.c_int32, c_i32p, c_i32p, c_f64p, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p,
                                          C.c_double, C.c_int32, c_f64p, c_i32p, c_f64p]),

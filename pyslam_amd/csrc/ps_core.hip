@@ -25,6 +25,7 @@
 #include "ps_kernels.h"
 #include "ps_ransac.h"
 #include "ps_photo.h"
+#include "ps_k_dense.h"
 #include "ps_sparse.h"
 
 namespace {
@@ -674,5 +675,6 @@ extern "C" {
 #include "ps_abi_problem.h"
 #include "ps_abi_solver.h"
 #include "ps_abi_small.h"
+#include "ps_abi_dense.h"
 
 }  // extern "C"

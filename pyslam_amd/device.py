@@ -534,6 +534,121 @@ class PhotometricDevice:
         return cost, float(np.linalg.norm(dx)), 0, 0.0
 
 
+
+class DenseTracker:
+    """Device side of the dense RGB-D VO pipeline (include/pyslam_hip.h: ps_dense_*; pyslam_amd/pipelines/dense.py drives
+    it): a fixed number of frame slots, each with its image pyramid, gradient and depth levels and per-level pixel tables,
+    and the coarse-to-fine solve of one frame in one call.  Device memory is fixed at construction."""
+
+    def __init__(self, levels, height, width, num_slots=3, stream=None):
+        lib = nat.require_gpu()
+        self._lib = lib
+        self.levels, self.height, self.width, self.num_slots = int(levels), int(height), int(width), int(num_slots)
+        self._pending = []          # host buffers of uploads not yet synchronised (ps_dense_upload does not wait)
+        self._h = nat.H()
+        nat.check(lib.ps_dense_create(self.levels, self.height, self.width, self.num_slots, C.c_void_p(stream or 0),
+                                      C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._lib.ps_dense_destroy(self._h)
+            self._h = None
+        self._pending = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def level_shape(self, level):
+        h, w = C.c_int32(), C.c_int32()
+        nat.check(self._lib.ps_dense_level_shape(self._h, int(level), C.byref(h), C.byref(w)))
+        return h.value, w.value
+
+    def upload(self, slot, image=None, depth=None):
+        """Image (uint8 or float64, height x width) and / or depth (float64) into `slot`; an image rebuilds the pyramid."""
+        img = None
+        if image is not None:
+            img = np.asarray(image)
+            if img.dtype not in (np.uint8, np.float64):
+                raise TypeError('DenseTracker: uint8 or float64 images only, got {}'.format(img.dtype))
+            if img.ndim != 2:
+                raise ValueError('DenseTracker: a single-channel image is required, got shape {}'.format(img.shape))
+            img = np.ascontiguousarray(img)
+        dep = None
+        if depth is not None:
+            dep = np.ascontiguousarray(np.asarray(depth, dtype=np.float64))
+            if img is not None and dep.shape != img.shape:
+                raise ValueError('DenseTracker: depth shape {} differs from the image shape {}'.format(dep.shape, img.shape))
+        h, w = (img.shape if img is not None else dep.shape)
+        self._pending += [a for a in (img, dep) if a is not None]
+        nat.check(self._lib.ps_dense_upload(self._h, int(slot), 0 if img is None or img.dtype == np.uint8 else 1, int(h), int(w),
+                                            None if img is None else img.ctypes.data_as(C.c_void_p), nat.f64p(dep)))
+
+    def make_tables(self, slot, levels, cams, intensity_covar, depth_covar, min_grad):
+        """Pixel tables of `slot` for each level of `levels`, with the camera of the same position in `cams` (RGBDCamera)."""
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        c6 = np.ascontiguousarray([[c.cu, c.cv, c.fu, c.fv, c.w, c.h] for c in cams], dtype=np.float64).reshape(-1, 6)
+        if c6.shape[0] != lv.size:
+            raise ValueError('one camera per level is required')
+        nat.check(self._lib.ps_dense_make_tables(self._h, int(slot), int(lv.size), nat.i32p(lv), nat.f64p(c6),
+                                                 float(intensity_covar), float(depth_covar), float(min_grad)))
+
+    def track(self, ref_slot, track_slot, levels, rot_only, options, loss, pose12):
+        """Coarse-to-fine solve: -> (pose12, [iterations per level], [cost history per level])."""
+        from pyslam_amd.lowering import _loss_id_k
+        lv = np.ascontiguousarray(levels, dtype=np.int32)
+        ro = np.ascontiguousarray([1 if r else 0 for r in rot_only], dtype=np.int32)
+        o = nat.SolveOptions()
+        o.max_iters = int(options.max_iters)
+        o.allow_nondecreasing_steps = int(bool(options.allow_nondecreasing_steps))
+        o.max_nondecreasing_steps = int(options.max_nondecreasing_steps)
+        o.linesearch = int(options.linesearch_max_iters > 0)
+        o.min_update_norm, o.min_cost = float(options.min_update_norm), float(options.min_cost)
+        o.min_cost_decrease, o.lm_lambda = float(options.min_cost_decrease), float(getattr(options, 'lm_lambda', 0.))
+        lid, lk = _loss_id_k(loss)
+        cap = o.max_iters + 2
+        pin = np.ascontiguousarray(pose12, dtype=np.float64).reshape(12)
+        pout = np.zeros(12)
+        its = np.zeros(max(lv.size, 1), dtype=np.int32)
+        hist = np.zeros((max(lv.size, 1), cap))
+        try:
+            nat.check(self._lib.ps_dense_track(self._h, int(ref_slot), int(track_slot), int(lv.size), nat.i32p(lv), nat.i32p(ro),
+                                               C.byref(o), int(lid), float(lk), nat.f64p(pin), nat.f64p(pout), nat.i32p(its),
+                                               nat.f64p(hist), cap))
+        finally:
+            self._pending = []
+        return pout, [int(i) for i in its[:lv.size]], [hist[k, :its[k] + 1].copy() for k in range(lv.size)]
+
+    def read_level(self, slot, level, what):
+        """'image' (h, w), 'gradient' (2, h, w) or 'depth' (h, w) of a slot's pyramid level."""
+        h, w = self.level_shape(level)
+        code = {'image': 0, 'gradient': 1, 'depth': 2}[what]
+        out = np.zeros((2, h, w) if code == 1 else (h, w))
+        nat.check(self._lib.ps_dense_read_level(self._h, int(slot), int(level), code, nat.f64p(out)))
+        self._pending = []
+        return out
+
+    def num_pixels(self, slot, level):
+        n = C.c_int32()
+        nat.check(self._lib.ps_dense_num_pixels(self._h, int(slot), int(level), C.byref(n)))
+        return n.value
+
+    def read_tables(self, slot, level):
+        """The level's pixel tables, named as PhotometricResidualSE3.device_tables() names them."""
+        n = self.num_pixels(slot, level)
+        t = dict(pt_ref=np.zeros((n, 3)), im_ref=np.zeros(n), im_jac=np.zeros((n, 2)), tri_jac_d=np.zeros((n, 3)))
+        nat.check(self._lib.ps_dense_read_tables(self._h, int(slot), int(level), n, nat.f64p(t['pt_ref']), nat.f64p(t['im_ref']),
+                                                 nat.f64p(t['im_jac']), nat.f64p(t['tri_jac_d'])))
+        self._pending = []
+        return t
+
+    def device_bytes(self):
+        b = C.c_int64()
+        nat.check(self._lib.ps_dense_device_bytes(self._h, C.byref(b)))
+        return b.value
+
 _TABLES_F64 = ('obs_uvd', 'cams', 'stiff3', 'obs_groups', 'e_Tobs_inv', 'u_Tobs_inv', 'stiffd', 'edge_groups')
 _TABLES_I32 = ('pose_rid', 'point_vid', 'obs_pose', 'obs_point', 'obs_grp', 'e_i', 'e_j', 'e_grp', 'u_i', 'u_grp')
 

@@ -356,3 +356,58 @@ def photometric_scene(h=48, w=64, seed=5, xi_true=(0.03, -0.02, 0.04, 0.01, -0.0
     cam = (cu, cv, fu, fv, 0. if rgbd else b, w, h)
     return dict(cam=cam, im_ref=im_ref, depth_ref=depth_ref, im_track=im_track, im_jac=np.stack([gx, gy]),
                 T_true=T.as_matrix(), rgbd=rgbd)
+
+
+def rgbd_sequence(h=96, w=128, n_frames=8, seed=0, step=(0.02, -0.01, 0.04, 0.012, 0.015, -0.006), hole_fraction=0.01,
+                  texture=1.0):
+    """An RGB-D sequence of an exactly rendered textured scene (three planes: a back wall, a floor and a slanted side
+    wall, so the depth has edges) seen along a smooth trajectory, rendered as photometric_scene renders its plane: every
+    pixel is the intensity of the 3-D point its ray meets first, with no warping or resampling.
+
+    The camera starts at the world origin and moves by about ``step`` (translation, rotation; per frame) with a slow
+    sinusoidal wobble.  Intensities are smooth functions of the world point, quantised to uint8; ``texture`` scales the
+    spatial frequencies (1.0: a few pixels per intensity step at every size).  Depth is the camera z in metres with
+    ``hole_fraction`` of the pixels NaN and as many 0 (invalid measurements).
+
+    Returns ``images`` (n, h, w) uint8, ``depth`` (n, h, w) float64, ``cam`` = (cu, cv, fu, fv, w, h) and ``T_c_w``
+    (n, 4, 4) world-to-camera poses."""
+    rng = np.random.default_rng(seed)
+    fu = fv = 0.9 * w
+    cu, cv = 0.5 * w - 0.5, 0.5 * h - 0.5
+    planes = [(np.array([0., 0., 1.]), 5.0),                                    # back wall z = 5
+              (np.array([0., 1., 0.]), 1.0),                                    # floor y = 1 (y points down)
+              (np.array([1., 0., 0.35]) / np.linalg.norm([1., 0., 0.35]), -1.2)]  # slanted wall on the left
+    k = fu / 100. * texture
+    freq = rng.uniform(0.8, 2.6, size=(6, 3)) * rng.choice([-1., 1.], size=(6, 3)) * k
+    phase = rng.uniform(0, 2 * np.pi, 6)
+    amp = rng.uniform(12., 22., 6)
+
+    def intensity(P):
+        return 128. + np.sum(amp * np.sin(P @ freq.T + phase), axis=-1)
+
+    u, v = np.meshgrid(np.arange(w, dtype=float), np.arange(h, dtype=float), indexing='xy')
+    rays = np.stack([(u - cu) / fu, (v - cv) / fv, np.ones_like(u)], axis=-1)
+    step = np.asarray(step, dtype=float)
+    images = np.zeros((n_frames, h, w), dtype=np.uint8)
+    depth = np.zeros((n_frames, h, w))
+    T_c_w = np.zeros((n_frames, 4, 4))
+    for f in range(n_frames):
+        xi = step * f + 0.3 * step * np.sin(0.7 * f)
+        T = SE3.exp(xi)
+        R, t = T.rot.as_matrix(), np.asarray(T.trans, dtype=float)
+        s_best = np.full((h, w), np.inf)
+        for n, c in planes:
+            Rn = R @ n                                   # n . P_w = c with P_w = R^T (s d - t)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                s = (c + Rn @ t) / (rays @ Rn)
+            s_best = np.where((s > 0.05) & (s < s_best), s, s_best)
+        P_c = rays * s_best[..., None]
+        P_w = (P_c - t) @ R                              # rows: R^T (P_c - t)
+        images[f] = np.clip(np.round(intensity(P_w)), 0, 255).astype(np.uint8)
+        d = s_best.copy()
+        holes = rng.random((h, w))
+        d[holes < hole_fraction] = np.nan
+        d[(holes >= hole_fraction) & (holes < 2 * hole_fraction)] = 0.
+        depth[f] = d
+        T_c_w[f] = T.as_matrix()
+    return dict(images=images, depth=depth, cam=(cu, cv, fu, fv, w, h), T_c_w=T_c_w)
