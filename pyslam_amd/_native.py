@@ -56,7 +56,7 @@ class ProblemInfo(C.Structure):
         ('ldi_solves', C.c_int64), ('ldi_fallbacks', C.c_int64), ('ldi_seeds', C.c_int64),
         ('xcg_fused_solves', C.c_int64), ('xcg_fused_fallbacks', C.c_int64),
         ('cg_persist_solves', C.c_int64), ('cg_persist_failures', C.c_int64), ('cg_persist_refused', C.c_int64),
-        ('persist_cus', C.c_int32), ('persist_cus_needed', C.c_int32), ('landmark_passes_taken_over', C.c_int64), ('xcg_persist4_solves', C.c_int64),
+        ('persist_cus', C.c_int32), ('persist_cus_needed', C.c_int32), ('landmark_passes_taken_over', C.c_int64),
     ]
 
 
@@ -177,8 +177,8 @@ def _share_torch_hip_runtime():
         pass
 
 
-_CREATE_ENV = {'PS_CREATE_DEVICE', 'PS_CREATE_KEYS64', 'PS_PAIRS_BY_LANDMARK', 'PS_SCHUR_MODE', 'PS_SCHUR_STREAM',
-               'PS_SCHUR_TILE_KB', 'PS_SCHUR_TILE_MIN_MB', 'PS_ST_TILES'}       # ps_create_env(): read by every build
+_CREATE_ENV = {'PS_CREATE_DEVICE', 'PS_CREATE_KEYS64', 'PS_PAIRS_BY_LANDMARK',
+               'PS_SCHUR_TILE_KB', 'PS_SCHUR_TILE_MIN_MB'}       # ps_create_env(): read by every build
 
 
 # ps_env(): the measurement / debugging switches of the -DPS_MEASURE build (tests/test_host_api.py holds this list against the sources)

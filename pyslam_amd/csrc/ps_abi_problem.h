@@ -113,7 +113,6 @@ int ps_problem_destroy(ps_problem* h) {
     h->arena_release();            // arena block, its pinned mirror and the pinned result words go back to the process-wide pool
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
     if (h->ev_ldi) { hipEventDestroy(h->ev_ldi); hipEventDestroy(h->ev_ldi_sread); hipEventDestroy(h->ev_ldi_ritz); }
-    if (h->aux) { hipStreamSynchronize(h->aux); if (!ps_pool().give(ps_pool().side_streams, h->aux)) hipStreamDestroy(h->aux); hipEventDestroy(h->ev_fork); hipEventDestroy(h->ev_join); }
     if (h->ldi_stream && !ps_pool().give(ps_pool().side_streams, h->ldi_stream)) hipStreamDestroy(h->ldi_stream);
     if (h->side) { hipStreamSynchronize(h->side); if (!h->side_poolable || !ps_pool().give(ps_pool().side_streams, h->side)) hipStreamDestroy(h->side); hipEventDestroy(h->ev_ac); hipEventDestroy(h->ev_chol); hipEventDestroy(h->ev_acdone); }
     if (h->own_stream && h->stream && !ps_pool().give(ps_pool().streams, h->stream)) hipStreamDestroy(h->stream);
@@ -221,8 +220,6 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
     const bool wide = d->num_obs_groups > 255;
     const int create_dev_env = ps_create_env("PS_CREATE_DEVICE") ? atoi(ps_create_env("PS_CREATE_DEVICE")) : 1;
     const bool dev_build = create_dev_env != 0 && D == 6 && N > 0 && nr > 0 && nv > 0 && !wide && (create_dev_env == 2 || N >= 200000) &&
-                           !(ps_create_env("PS_SCHUR_MODE") && atoi(ps_create_env("PS_SCHUR_MODE")) != 0) &&
-                           !(ps_create_env("PS_SCHUR_STREAM") && atoi(ps_create_env("PS_SCHUR_STREAM")) != 0) &&
                            !ps_create_env("PS_SCHUR_TILE_KB") && !ps_create_env("PS_PAIRS_BY_LANDMARK");
     if (!dev_build && staged.pull_obs()) return -1;
     std::vector<int32_t> first_pose(dev_build ? 0 : L, INT32_MAX);
@@ -435,116 +432,6 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
     if (h->alloc(&h->fscratch, (size_t)F * FROW)) return -1;
 
     lap("pose factors");
-    // ---- pose-stationary Schur lists (round 4; kernel k_schur_pose, csrc/ps_k_schur3.h; NOT the default: slower, see below).
-    // A workgroup takes a SEGMENT of up to PS_PP_SEG rows of ONE pose i -- its Z rows on variable landmarks, in landmark
-    // order -- brings them into LDS once, and its waves work through the tasks (segment, partner pose j > i): the pairs
-    // (a = local index of pose i's row, b = the Z row of pose j on the same landmark).  Only the partner rows are gathered:
-    // 0.5 M + 2.25 M row fetches at C3 instead of 4.5 M.  One partial block per task, summed in segment order by
-    // k_schur_combine (fixed order).  Not built when a landmark is observed twice from one pose (a diagonal-block task: the
-    // gather kernels handle that) or when a Z row index does not fit 23 bits.
-    std::vector<uint64_t> pose_keys;              // upper block keys (ri < rj) that receive pairs, unsorted, with repeats
-    std::vector<PoseSeg> psegs;
-    std::vector<int32_t> pseg_rows;
-    std::vector<PairItem> ptasks;                 // slot / slotT are filled once the block pattern exists
-    std::vector<uint64_t> ptask_key;
-    std::vector<uint32_t> ppairs;
-    std::vector<long> pseg_pairs;                 // pairs per segment (XCD balancing)
-    // Measured (tools/schur_probe.py): 0.121 ms at C3 against 0.046 for the pipelined gather kernel, 1.01 ms
-    // against 0.515 at C4 -- a workgroup needs 157 KB of LDS (the segment + two chunk buffers per wave), so ONE is resident per
-    // CU and the dependent loads of its start-up (order -> segment -> row indices -> rows -> pair words -> partner rows) are
-    // covered by nothing; with products, fetches, fill and stores all removed the skeleton still takes 0.06 ms.  Kept as an
-    // independent variant (parity-tested against the gather kernels and the oracle); built with PS_SCHUR_MODE=1 (this
-    // kernel only) or 2 (both list sets: option "schur_mode" switches).
-    const int schur_mode_env = ps_create_env("PS_SCHUR_MODE") ? atoi(ps_create_env("PS_SCHUR_MODE")) : 0;
-    bool pose_mode = schur_mode_env != 0 && D == 6 && nv > 0 && nr > 0 && Nl > 0 && Nl < (1L << 23);
-    if (pose_mode) {
-        std::vector<int32_t> rid_row((size_t)Nl), lm_row((size_t)Nl);
-        for (int v = 0; v < nv; ++v)
-            for (int a = lm_ptr[v]; a < lm_ptr[v + 1]; ++a) { lm_row[a] = v; rid_row[a] = d->pose_rid[PS_POSE_OF(lobs[a])]; }
-        struct Tri { int32_t rb, al, b; };
-        struct Part {                                   // what one host thread produces for its range of poses
-            std::vector<PoseSeg> segs; std::vector<int32_t> rows; std::vector<PairItem> tasks; std::vector<uint64_t> keys;
-            std::vector<uint32_t> pairs; std::vector<long> seg_pairs; bool diag = false;
-        };
-        const int nth = std::max(1, std::min({(int)std::thread::hardware_concurrency(), 16, nr}));
-        std::vector<Part> parts(nth);
-        auto work = [&](int th) {
-            Part& o = parts[th];
-            const int r0 = (int)((long)nr * th / nth), r1 = (int)((long)nr * (th + 1) / nth);
-            std::vector<Tri> tri, sorted;
-            std::vector<int32_t> cnt((size_t)nr + 1, 0), touched;
-            for (int r = r0; r < r1; ++r) {
-                // pose r's Z rows (variable landmarks only), ascending
-                int s0 = pcount[r];
-                const int s_end = pcount[r + 1];
-                while (s0 < s_end) {
-                    PoseSeg sg{(int32_t)o.rows.size(), 0, (int32_t)o.tasks.size(), 0};
-                    tri.clear();
-                    int al = 0;
-                    for (; s0 < s_end && al < PS_PP_SEG - 1; ++s0) {
-                        const int k = pidx[s0];
-                        if (k >= Nl) continue;                   // an observation of a constant point: no Z row
-                        o.rows.push_back(k);
-                        const int v = lm_row[k];
-                        for (int b = lm_ptr[v]; b < lm_ptr[v + 1]; ++b) {
-                            const int rb = rid_row[b];
-                            if (rb > r) tri.push_back({rb, al, b});
-                            else if (rb == r && b != k) o.diag = true;
-                        }
-                        ++al;
-                    }
-                    sg.row_count = al;
-                    // tasks: the pairs by partner (stable counting sort: pairs of a task stay in landmark order)
-                    touched.clear();
-                    for (const Tri& t : tri) { if (cnt[t.rb]++ == 0) touched.push_back(t.rb); }
-                    std::sort(touched.begin(), touched.end());
-                    int32_t run = 0;
-                    for (int32_t rb : touched) { const int32_t c = cnt[rb]; cnt[rb] = run; run += c; }
-                    sorted.resize(tri.size());
-                    for (const Tri& t : tri) sorted[cnt[t.rb]++] = t;
-                    // every task's words are padded to a multiple of 32 (one product pass of the kernel); a padding word carries
-                    // the reserved a-row index and the task's last partner row (a harmless fetch)
-                    int32_t prev = 0;
-                    for (int32_t rb : touched) {
-                        const int32_t end = cnt[rb];
-                        const int32_t w0 = (int32_t)o.pairs.size();
-                        for (int32_t q = prev; q < end; ++q) o.pairs.push_back(((uint32_t)sorted[q].al << 23) | (uint32_t)sorted[q].b);
-                        while ((o.pairs.size() - (size_t)w0) % 32) o.pairs.push_back(((uint32_t)511u << 23) | (uint32_t)sorted[end - 1].b);
-                        o.tasks.push_back({-1, -1, w0, (int32_t)o.pairs.size()});
-                        o.keys.push_back(((uint64_t)r << 32) | (uint32_t)rb);
-                        prev = end;
-                        cnt[rb] = 0;
-                    }
-                    sg.task_end = (int32_t)o.tasks.size();
-                    if (al > 0) { o.segs.push_back(sg); o.seg_pairs.push_back((long)tri.size()); }
-                    else { o.rows.resize(sg.row_start); }
-                }
-            }
-        };
-        if (nth == 1) work(0);
-        else {
-            std::vector<std::thread> pool;
-            for (int th = 0; th < nth; ++th) pool.emplace_back(work, th);
-            for (auto& t : pool) t.join();
-        }
-        size_t tot_pairs = 0, tot_tasks = 0;
-        for (const Part& o : parts) { pose_mode = pose_mode && !o.diag; tot_pairs += o.pairs.size(); tot_tasks += o.tasks.size(); }
-        if (tot_pairs >= (1UL << 31) || tot_tasks >= (1UL << 31) / 36) pose_mode = false;
-        if (pose_mode) {
-            for (const Part& o : parts) {                   // concatenate in pose order, rebasing the offsets
-                const int32_t rb = (int32_t)pseg_rows.size(), tb = (int32_t)ptasks.size(), pb = (int32_t)ppairs.size();
-                for (PoseSeg sg : o.segs) { sg.row_start += rb; sg.task_start += tb; sg.task_end += tb; psegs.push_back(sg); }
-                for (PairItem t : o.tasks) { t.start += pb; t.end += pb; ptasks.push_back(t); }
-                pseg_rows.insert(pseg_rows.end(), o.rows.begin(), o.rows.end());
-                ptask_key.insert(ptask_key.end(), o.keys.begin(), o.keys.end());
-                ppairs.insert(ppairs.end(), o.pairs.begin(), o.pairs.end());
-                pseg_pairs.insert(pseg_pairs.end(), o.seg_pairs.begin(), o.seg_pairs.end());
-            }
-            pose_keys = ptask_key;
-        }
-    }
-    const bool gather_lists = !pose_mode || schur_mode_env == 2;      // the pair lists of the gather kernels (k_schur_pairs[_db])
-    lap("pose-stationary lists");
     // ---- Schur pairs per landmark (upper-triangle block keys)
     // Landmark tiles: when Z (144 B per row) is much larger than the eight 4 MB L2s, the pair list is
     // cut into tiles of consecutive landmarks (consecutive Z rows) and ONE XCD works through a whole
@@ -566,22 +453,22 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
     }
     // Device build of the pair list (csrc/ps_host_build.h): pairs generated, sorted and left in HBM; the host receives the task
     // starts and keys only.
-    const bool dev_pairs = gather_lists && dev_build && ntiles < 65536;
+    const bool dev_pairs = dev_build && ntiles < 65536;
     // (a device build leaves no observation tables on the host: the host pair loop below would see empty lists and the reduced
     //  system would silently lose every landmark coupling -- round-4 ADVICE.  65 536 tiles = 590 GB of Z rows: not reachable)
-    if (dev_build && gather_lists && !dev_pairs) return fail("too many landmark tiles for the device pair build");
+    if (dev_build && !dev_pairs) return fail("too many landmark tiles for the device pair build");
     DevPairBuild devb;
     std::vector<long> lm_pairs_before(nv + 1, 0);
     if (dev_pairs) {
         if (h->arena_flush() || devb.prepare(h, nv, nr, Nl)) return -1;
     } else {
-        for (int v = 0; v < nv && gather_lists; ++v) {
+        for (int v = 0; v < nv; ++v) {
             long nvar = 0;
             for (int a = lm_ptr[v]; a < lm_ptr[v + 1]; ++a) nvar += d->pose_rid[PS_POSE_OF(lobs[a])] >= 0;
             lm_pairs_before[v + 1] = lm_pairs_before[v] + nvar * (nvar - 1) / 2;
         }
     }
-    const long total_pairs = dev_pairs ? (long)devb.total : (gather_lists ? lm_pairs_before[nv] : 0);
+    const long total_pairs = dev_pairs ? (long)devb.total : lm_pairs_before[nv];
     if (total_pairs >= (1L << 31)) return fail("too many Schur pairs for 32-bit indexing");
     if (dev_pairs) {
         // the same decisions as the host loop below, on lists that are never on the host
@@ -611,7 +498,7 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
     // shard of a multi-GPU run: 36 pairs per block at C4 / 8 -- the per-task skeleton dominates and the
     // untiled list wins (C4 / 8 shard: Schur stage 0.159 -> 0.119 ms).  Decided on the generated list: fewer than 64 pairs
     // per task on average -> generated again without tiles.
-    for (int attempt = 0; attempt < 2 && gather_lists && !dev_pairs; ++attempt) {
+    for (int attempt = 0; attempt < 2 && !dev_pairs; ++attempt) {
         auto tile_of = [&](int v) {
             return (ntiles > 1 && total_pairs > 0)
                 ? (int)std::min<long>(ntiles - 1, (long)((double)ntiles * (double)lm_pairs_before[v] / (double)total_pairs)) : 0;
@@ -734,10 +621,9 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
         if (prs.size() >= 64 * ntask && !blocks_fill_chip) break;
         ntiles = 1;
     }
-    if (!gather_lists) ntiles = 1;
     h->schur_tiles = ntiles;
     const long npairs_l = dev_pairs ? total_pairs : (long)prs.size();
-    h->npairs = gather_lists ? npairs_l : (long)ppairs.size();
+    h->npairs = npairs_l;
     if (prs.size() >= (1UL << 31)) return fail("too many Schur pairs for 32-bit indexing");
 
     lap("pair generation + sort");
@@ -770,7 +656,6 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
     keys.reserve(task_keyv.size() + nr + F + d->num_extra_pairs);
     for (int r = 0; r < nr; ++r) keys.push_back(((uint64_t)r << 32) | (uint32_t)r);
     keys.insert(keys.end(), task_keyv.begin(), task_keyv.end());
-    keys.insert(keys.end(), pose_keys.begin(), pose_keys.end());
     for (long f = 0; f < E; ++f) {
         const int ra = d->pose_rid[f_i[f]], rb = d->pose_rid[f_j[f]];
         if (ra >= 0 && rb >= 0 && ra != rb)
@@ -885,228 +770,8 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
             if (h->alloc(&h->Spart, xit.size() * 36)) return -1;
         }
     }
-    if (pose_mode && !ptasks.empty()) {
-        for (size_t t = 0; t < ptasks.size(); ++t) {
-            const int a = (int)(ptask_key[t] >> 32), b = (int)(uint32_t)ptask_key[t];
-            ptasks[t].slot = slot_of(a, b); ptasks[t].slotT = slot_of(b, a);
-        }
-        // XCD x sweeps a contiguous range of poses (its segments in pose order: neighbouring poses share landmarks, hence
-        // partner rows -- temporal locality in that XCD's L2 and in the Infinity Cache); ranges balanced by pair count
-        long total = 0;
-        for (long c : pseg_pairs) total += c + 64;           // (+ a per-segment constant: the row fill)
-        std::vector<std::vector<int32_t>> lists(8);
-        long run = 0;
-        for (size_t q = 0; q < psegs.size(); ++q) {
-            lists[std::min(7, (int)(8.0 * (double)run / (double)std::max(total, 1L)))].push_back((int32_t)q);
-            run += pseg_pairs[q] + 64;
-        }
-        size_t mx = 0;
-        for (auto& l : lists) mx = std::max(mx, l.size());
-        mx = std::max<size_t>(mx, 1);
-        std::vector<int32_t> order(8 * mx, -1);
-        for (int x = 0; x < 8; ++x) for (size_t q = 0; q < lists[x].size(); ++q) order[x * mx + q] = lists[x][q];
-        // per-block task lists in segment order (tasks are numbered pose-, segment-, partner-major)
-        std::vector<std::pair<int32_t, int32_t>> bt(ptasks.size());
-        for (size_t k = 0; k < ptasks.size(); ++k) bt[k] = {ptasks[k].slot, (int32_t)k};
-        std::stable_sort(bt.begin(), bt.end(), [](const std::pair<int32_t, int32_t>& x, const std::pair<int32_t, int32_t>& y) {
-            return x.first < y.first; });
-        std::vector<PairItem> citm;
-        std::vector<int32_t> ctasks(bt.size());
-        for (size_t k = 0; k < bt.size(); ++k) {
-            ctasks[k] = bt[k].second;
-            if (k == 0 || bt[k].first != bt[k - 1].first) {
-                if (!citm.empty()) citm.back().end = (int32_t)k;
-                citm.push_back({ptasks[bt[k].second].slot, ptasks[bt[k].second].slotT, (int32_t)k, 0});
-            }
-        }
-        citm.back().end = (int32_t)bt.size();
-        // device records: a wave takes a contiguous run of the segment's tasks (their words are contiguous), runs balanced by
-        // product passes
-        std::vector<PoseSegW> psegw(psegs.size());
-        for (size_t q = 0; q < psegs.size(); ++q) {
-            const PoseSeg& sg = psegs[q];
-            PoseSegW& o = psegw[q];
-            o.row_start = sg.row_start; o.row_count = sg.row_count;
-            const long w0 = sg.task_start < sg.task_end ? ptasks[sg.task_start].start : 0;
-            const long wn = sg.task_start < sg.task_end ? ptasks[sg.task_end - 1].end - w0 : 0;
-            int tcur = sg.task_start;
-            o.wt[0] = tcur;
-            for (int w = 1; w <= PS_PP_WAVES; ++w) {
-                const long target = w0 + wn * w / PS_PP_WAVES;
-                while (tcur < sg.task_end && (w == PS_PP_WAVES || ptasks[tcur].end <= target)) ++tcur;
-                // (a task that straddles the target goes to the next wave; the last wave takes the rest)
-                o.wt[w] = tcur;
-            }
-        }
-        h->pp_per_xcd = (int)mx; h->pp_ntasks = (int)ptasks.size(); h->pp_ncomb = (int)citm.size();
-        if (h->upload(&h->pp_order, order) || h->upload(&h->pp_segs, psegw) || h->upload(&h->pp_rows, pseg_rows) ||
-            h->upload(&h->pp_tasks, ptasks) || h->upload(&h->pp_pairs, ppairs) || h->upload(&h->pp_comb_items, citm) ||
-            h->upload(&h->pp_comb_tasks, ctasks) || h->alloc(&h->pp_part, ptasks.size() * 36)) return -1;
-        h->pose_mode = true;
-    }
-    h->gather_lists = gather_lists;
 
     lap("pair items + XCD lists");
-    // ---- streaming Schur kernel (k_schur_stream): landmark tiles, per-tile block tables, per-lane-pair entry lists
-    {
-        // OFF unless PS_SCHUR_STREAM=1: measured slower than the gather kernel on MI355X (C3 0.112-0.137 ms against 0.060,
-        // C4 0.79 against 0.57 ms): 57 MB of partial blocks written and read back plus 28 MB of padded entry words
-        // outweigh the 9x fewer L2 requests, which L2 / Infinity Cache absorb well enough.
-        const char* env = ps_create_env("PS_SCHUR_STREAM");
-        h->stream_mode = env ? atoi(env) : 0;                   // 0 off (default), 1 on whenever it can be built
-        if (h->stream_mode != 0 && total_pairs > 0 && D == 6) {
-            std::vector<StreamTile> tiles;
-            std::vector<StreamSub> subs;
-            std::vector<uint32_t> ents;
-            std::vector<std::pair<int32_t, int32_t>> part_of;   // (block slot, partial index): combine lists
-            std::vector<int32_t> part_slotT;
-            bool ok = true;
-            struct KV { uint64_t key; int32_t val; };
-            std::vector<KV> table(4096, KV{~0ULL, -1});
-            std::vector<uint32_t> used;
-            auto find_or_add = [&](uint64_t key, int32_t next) -> int32_t {
-                size_t i = (size_t)((key * 0x9E3779B97F4A7C15ULL) >> 52) & 4095;
-                for (;;) {
-                    if (table[i].key == key) return table[i].val;
-                    if (table[i].key == ~0ULL) { table[i] = KV{key, next}; used.push_back((uint32_t)i); return next; }
-                    i = (i + 1) & 4095;
-                }
-            };
-            auto rid_of = [&](int row) { return d->pose_rid[PS_POSE_OF(lobs[row])]; };
-            long part_total = 0, ent_pairs = 0;
-            // Tiles are cut by the accumulator capacity (PS_ST_CAP blocks) AND by a landmark count that leaves the chip
-            // enough workgroups: a multiple of its 256 CUs, about 5 M pairs per round of 256 tiles (C3: 256 tiles of 196
-            // landmarks, C4: 1 024 of 489).  Fewer, larger tiles would write fewer partial blocks but leave CUs idle.
-            long ttarget = 256L * std::max<long>(1, std::lround((double)total_pairs / 5.0e6));
-            if (const char* e2 = ps_create_env("PS_ST_TILES")) ttarget = std::max(1L, atol(e2));
-            const int tile_lm_cap = std::max(32, cdiv(nv, ttarget));
-            int v = 0;
-            while (v < nv && ok) {
-                // grow the tile landmark by landmark while its block set fits the accumulators of one workgroup
-                for (uint32_t i : used) table[i] = KV{~0ULL, -1};
-                used.clear();
-                int nblk = 0;
-                const int v0 = v;
-                std::vector<uint64_t> keys_local;
-                for (; v < nv && v - v0 < tile_lm_cap; ++v) {
-                    const int a0 = lm_ptr[v], a1 = lm_ptr[v + 1];
-                    if (a1 - a0 >= 65536) { ok = false; break; }
-                    const size_t used_before = used.size();
-                    int added = 0;
-                    // (stop inserting as soon as the landmark overflows the accumulators: the 4 096-slot table holds at most
-                    //  PS_ST_CAP + 1 keys that way -- a landmark seen by ~90 variable poses used to fill it and spin, ADVICE)
-                    for (int a = a0; a < a1 && nblk + added <= PS_ST_CAP; ++a) {
-                        const int ra = rid_of(a);
-                        if (ra < 0) continue;
-                        for (int b = a + 1; b < a1 && nblk + added <= PS_ST_CAP; ++b) {
-                            const int rb = rid_of(b);
-                            if (rb < 0) continue;
-                            const uint64_t key = ((uint64_t)std::min(ra, rb) << 32) | (uint32_t)std::max(ra, rb);
-                            if (find_or_add(key, nblk + added) == nblk + added) { keys_local.push_back(key); ++added; }
-                        }
-                    }
-                    if (nblk + added > PS_ST_CAP) {              // this landmark does not fit any more: undo it, close the tile
-                        for (size_t q = used_before; q < used.size(); ++q) table[used[q]] = KV{~0ULL, -1};
-                        used.resize(used_before);
-                        keys_local.resize(nblk);
-                        if (v == v0) ok = false;                  // a single landmark with more pairs than accumulators
-                        break;
-                    }
-                    nblk += added;
-                }
-                if (!ok) break;
-                if (nblk == 0) continue;                          // landmarks without a pair (seen by < 2 variable poses)
-                const int v1 = v;
-                // local block numbering: ascending key (fixed, independent of the hash order)
-                std::vector<int32_t> order(nblk), local_of(nblk);
-                for (int b = 0; b < nblk; ++b) order[b] = b;
-                std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return keys_local[x] < keys_local[y]; });
-                for (int b = 0; b < nblk; ++b) local_of[order[b]] = b;
-                StreamTile tl{};
-                tl.row0 = lm_ptr[v0]; tl.sub0 = (int32_t)subs.size(); tl.part0 = (int32_t)part_total; tl.nblk = nblk;
-                for (int b = 0; b < nblk; ++b) {
-                    const uint64_t key = keys_local[order[b]];
-                    const int ra = (int)(key >> 32), rb = (int)(uint32_t)key;
-                    part_of.push_back({slot_of(ra, rb), (int32_t)(part_total + b)});
-                    part_slotT.push_back(slot_of(rb, ra));
-                    if (ra == rb) h->has_diag_tasks = true;
-                }
-                part_total += nblk;
-                // sub-tiles: <= PS_ST_SUBROWS rows each, cut at landmark boundaries, about equal
-                const int nrows_t = lm_ptr[v1] - lm_ptr[v0];
-                const int nsub = std::max(1, cdiv(nrows_t, PS_ST_SUBROWS));
-                const int target = cdiv(nrows_t, nsub);            // rows per sub-tile aimed at
-                int vs = v0;
-                while (vs < v1) {
-                    int ve = vs + 1;
-                    while (ve < v1 && lm_ptr[ve] - lm_ptr[vs] < target && lm_ptr[ve + 1] - lm_ptr[vs] <= PS_ST_SUBROWS) ++ve;
-                    if (lm_ptr[ve] - lm_ptr[vs] > PS_ST_SUBROWS) { ok = false; break; }     // one landmark longer than a sub-tile
-                    StreamSub sb{};
-                    sb.row = lm_ptr[vs]; sb.nrows = lm_ptr[ve] - lm_ptr[vs];
-                    // per (slot q, lane pair): the row pairs of its block inside this sub-tile, in landmark order
-                    std::vector<std::vector<uint32_t>> lists((size_t)PS_ST_SLOTS * PS_ST_PAIRS);
-                    for (int vv = vs; vv < ve; ++vv)
-                        for (int a = lm_ptr[vv]; a < lm_ptr[vv + 1]; ++a) {
-                            const int ra = rid_of(a);
-                            if (ra < 0) continue;
-                            for (int b = a + 1; b < lm_ptr[vv + 1]; ++b) {
-                                const int rb = rid_of(b);
-                                if (rb < 0) continue;
-                                const uint64_t key = ((uint64_t)std::min(ra, rb) << 32) | (uint32_t)std::max(ra, rb);
-                                const int lb = local_of[find_or_add(key, -1)];
-                                const int la = (ra <= rb ? a : b) - sb.row, lbr = (ra <= rb ? b : a) - sb.row;
-                                lists[(size_t)(lb / PS_ST_PAIRS) * PS_ST_PAIRS + lb % PS_ST_PAIRS].push_back((uint32_t)la | ((uint32_t)lbr << 16));
-                                ++ent_pairs;
-                            }
-                        }
-                    for (int q = 0; q < PS_ST_SLOTS; ++q)
-                        for (int w = 0; w < PS_ST_THREADS / 64; ++w) {
-                            size_t steps = 0;
-                            for (int l = 0; l < 64; ++l) steps = std::max(steps, lists[(size_t)q * PS_ST_PAIRS + w * 64 + l].size());
-                            const size_t nbatch = (steps + 7) / 8;           // batches of 8 steps, lane major inside a batch
-                            sb.off[q][w] = (int32_t)(ents.size() / 4); sb.steps[q][w] = (int32_t)nbatch;
-                            for (size_t bt = 0; bt < nbatch; ++bt)
-                                for (int l = 0; l < 64; ++l) {
-                                    const auto& li = lists[(size_t)q * PS_ST_PAIRS + w * 64 + l];
-                                    for (size_t k = 0; k < 8; ++k) ents.push_back(bt * 8 + k < li.size() ? li[bt * 8 + k] : PS_ST_NONE);
-                                }
-                        }
-                    subs.push_back(sb);
-                    vs = ve;
-                }
-                if (!ok) break;
-                tl.nsub = (int32_t)subs.size() - tl.sub0;
-                tiles.push_back(tl);
-                if (ents.size() / 4 >= (1UL << 31) - (1UL << 20)) ok = false;
-            }
-            // worth it only if a partial block collects several pairs (else the partials outweigh the gathers)
-            const double pairs_per_partial = part_total ? (double)total_pairs / (double)part_total : 0.0;
-            if (ok && !tiles.empty() && (h->stream_mode == 1 || pairs_per_partial >= 4.0)) {
-                // combine lists: per block slot its partials in tile order
-                std::stable_sort(part_of.begin(), part_of.end(), [](const std::pair<int32_t, int32_t>& x, const std::pair<int32_t, int32_t>& y) {
-                    return x.first < y.first; });
-                std::vector<PairItem> citm;
-                std::vector<int32_t> ctasks(part_of.size());
-                for (size_t k = 0; k < part_of.size(); ++k) {
-                    ctasks[k] = part_of[k].second;
-                    if (k == 0 || part_of[k].first != part_of[k - 1].first) {
-                        if (!citm.empty()) citm.back().end = (int32_t)k;
-                        citm.push_back({part_of[k].first, part_slotT[part_of[k].second], (int32_t)k, 0});
-                    }
-                }
-                citm.back().end = (int32_t)part_of.size();
-                h->st_ntiles = (int)tiles.size(); h->st_ncomb = (int)citm.size();
-                if (h->upload(&h->st_tiles, tiles) || h->upload(&h->st_subs, subs) || h->upload(&h->st_entries, ents) ||
-                    h->upload(&h->st_comb_items, citm) || h->upload(&h->st_comb_tasks, ctasks) ||
-                    h->alloc(&h->st_part, (size_t)part_total * 36)) return -1;
-                h->use_stream = true;
-                if (timing) fprintf(stderr, "ps_problem_create: streaming Schur: %d tiles, %zu sub-tiles, %ld partial blocks (%.1f pairs each), "
-                                            "%.1f MB of entry words (%.2fx the pairs)\n", h->st_ntiles, subs.size(), part_total, pairs_per_partial,
-                                    ents.size() * 4e-6, (double)ents.size() / (double)std::max<long>(1, ent_pairs));
-            }
-        }
-    }
-    lap("streaming Schur lists");
     // ---- factor contribution lists
     {
         struct C { int32_t slot, off, tr; };

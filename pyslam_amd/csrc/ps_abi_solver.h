@@ -16,7 +16,6 @@ int ps_get_info(ps_problem* h, ps_problem_info* info) {
     info->cg_persist_refused = h->cp_refused; info->persist_cus = h->persist_cus;
     info->persist_cus_needed = h->cp_ok ? h->cp_cus_needed : (h->xp_ok ? h->xp_cus_needed : 0);
     info->landmark_passes_taken_over = h->prelm_used;
-    info->xcg_persist4_solves = h->xp4_launches;
     return 0;
 }
 
@@ -787,7 +786,7 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
         {h->point_vid, (size_t)h->L * 4}, {h->lobs, (size_t)h->N * sizeof(LObs)}, {h->lorig, (size_t)h->N * 4},
         {h->lm_ptr, ((size_t)h->nv + 1) * 4}, {h->lm_point, (size_t)h->nv * 4}, {h->pose_of_rid, (size_t)std::max(h->nr, 1) * 4},
         {h->pitems, (size_t)h->npitems * sizeof(PItem)}, {h->pitem_ptr, ((size_t)h->nr + 1) * 4}, {h->pobs, (size_t)h->Np * sizeof(LObs)},
-        {h->gather_lists ? h->pairs : nullptr, (size_t)h->npairs * 8}, {h->pair_xitems, (size_t)8 * h->pair_per_xcd * sizeof(PairItem)},
+        {h->pairs, (size_t)h->npairs * 8}, {h->pair_xitems, (size_t)8 * h->pair_per_xcd * sizeof(PairItem)},
         {tiled ? h->comb_items : nullptr, (size_t)h->ncomb * sizeof(PairItem)}, {tiled ? h->comb_tasks : nullptr, (size_t)h->npair_items * 4},
         {h->row_ptr, ((size_t)h->nr + 1) * 4}, {h->col_idx, (size_t)h->nnzb * 4}, {h->diag_slot, (size_t)h->nr * 4}};
     *count = 16;
@@ -838,21 +837,12 @@ int ps_set_option(ps_problem* h, const char* name, double value) {
     }
 #endif
     else if (n == "schur_pipeline") h->schur_pipeline = value != 0.0;
-    else if (n == "schur_mode") {
-        if (value != 0.0 && value != 1.0) return fail("schur_mode must be 0 (gather kernels) or 1 (pose-stationary kernel)");
-        if (value == 0.0 && !h->gather_lists) return fail("schur_mode 0: the gather kernels' pair lists were not built for this handle (create it under PS_SCHUR_MODE=0 or 2)");
-        h->schur_mode = (int)value;
-    }
-    else if (n == "schur_stream") { if (value != 0.0 && !h->st_tiles) return fail("schur_stream: the streaming lists were not built for this problem"); h->use_stream = value != 0.0; }
     else if (n == "coarse_lag") h->coarse_lag = value != 0.0;
     else if (n == "cg_force_restart") h->cg_force_restart = value != 0.0;
     else if (n == "xcg_restrict_fused") h->xcg_rt = value != 0;
     else if (n == "band_chol") { h->band_chol = value != 0; h->lci_next = -1; }
     else if (n == "lm_packed") h->lm_packed = value != 0;
-    else if (n == "pose_async") h->pose_async = (int)value;
     else if (n == "pose_xcd") h->pose_xcd = value != 0;
-    else if (n == "xcg_persist4") h->xcg_persist4 = value != 0;
-    else if (n == "cg_pipelined") { if (value != 0 && value != 1 && value != 2) return fail("cg_pipelined must be 0, 1 or 2"); h->cg_pipelined = (int)value; }
     else if (n == "fuse_cost") h->fuse_cost = (int)value;       // 0 off, 1 on, 2 = in the tails only (not the start cost / ps_eval_cost)
     else if (n == "sync_refactor") h->sync_refactor = value != 0;
     else if (n == "hold_across_steps") h->hold_across_steps = value != 0;

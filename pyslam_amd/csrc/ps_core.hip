@@ -208,27 +208,6 @@ struct ps_problem {
     double* Spart = nullptr;
     PairItem* comb_items = nullptr;     // slot, slotT, [start, end) into comb_tasks
     int32_t* comb_tasks = nullptr;
-    // pose-stationary Schur kernel (k_schur_pose, ps_k_schur3.h): segments of a pose's Z rows, tasks (segment, partner), packed pairs
-    int schur_mode = 1;             // option "schur_mode": 1 = pose-stationary kernel when its lists exist (PS_SCHUR_MODE=1 / 2 at create), 0 = the gather kernels
-    bool gather_lists = true;       // the pair lists of the gather kernels exist (not built in pose mode unless PS_SCHUR_MODE=2)
-    bool pose_mode = false;         // the lists exist and the kernel is in use (option "schur_mode": 0 = gather kernels, if their lists exist)
-    int pp_per_xcd = 0, pp_ntasks = 0, pp_ncomb = 0;
-    int32_t *pp_order = nullptr, *pp_rows = nullptr, *pp_comb_tasks = nullptr;
-    PoseSegW* pp_segs = nullptr;
-    PairItem *pp_tasks = nullptr, *pp_comb_items = nullptr;
-    uint32_t* pp_pairs = nullptr;
-    double* pp_part = nullptr;
-    // streaming Schur kernel (k_schur_stream): landmark tiles, sub-tiles, entry words, partial blocks + their combine lists
-    int stream_mode = 0;            // PS_SCHUR_STREAM: 0 off (default: measured slower than the gather kernel), 1 whenever it can be built
-    bool use_stream = false;
-    int st_ntiles = 0, st_ncomb = 0;
-    StreamTile* st_tiles = nullptr;
-    StreamSub* st_subs = nullptr;
-    uint32_t* st_entries = nullptr;
-    double* st_part = nullptr;
-    PairItem* st_comb_items = nullptr;
-    int32_t* st_comb_tasks = nullptr;
-    bool st_attr_set = false;
     // factors
     FactorGroup* fgroups = nullptr;
     int32_t *f_i = nullptr, *f_j = nullptr, *f_grp = nullptr;
@@ -350,19 +329,10 @@ struct ps_problem {
     double *xf_tq[2] = {}, *xf_ts[2] = {}, *xf_t[2] = {};
     int xf_rmax = 1, xf_nwg = 0, xf_pf = 2;
     size_t xf_nrec = 0;
-    int xf_ymax = 0;
-    int xcg_persist4 = 0;           // option "xcg_persist4": the one-launch explicit PCG as four waves per workgroup where its conditions hold (ps_k_xcg_persist4.h; measured slower: off)
-    long xp4_launches = 0;
     long xf_solves = 0, xf_fallbacks = 0;
     int cg_lds = 1;                 // small systems: k_cg_fused_lds (whole vector through LDS)
     // the folded CG in ONE launch (ps_k_cg_persist.h): option "cg_persist"; task table built with the coarse level
     int cg_persist = 1;
-    // option "cg_pipelined": the one-launch folded CG with the PIPELINED recurrences (ps_k_cg_persist.h, round 6; measured, OFF by
-    // default).  Always on (2) they take 2.8 % off a C3 iteration (0.4 us per CG iteration) and cost iterations and digits on
-    // ill-conditioned systems (pose graphs: 74 CG iterations where Chronopoulos-Gear takes 60, the step 4e-9 off); restricted to
-    // solves whose predecessor on the handle took at most 32 iterations (1) the gain is gone (the first call of every solve is
-    // excluded and two instantiations alternate): 0.3074 against 0.3038 ms.  0 (default) = Chronopoulos-Gear everywhere
-    int cg_pipelined = 0;
     bool cp_ok = false;             // the augmented system fits the kernel's layout
     bool cp_recovered = false;      // the launch just enqueued recovers x itself when it converges
     int cp_ntasks = 0, cg_max_launches = 0;
@@ -463,11 +433,7 @@ struct ps_problem {
     int32_t* lmw_first = nullptr;
     int lmw_nwaves = 0;
     int lm_packed = 1;              // option "lm_packed"
-    // option "pose_async": the pose pass beside the Schur pair kernel (both read what the landmark pass left: nothing of each
-    // other's) -- 1: on a second stream, joined by events in front of the finalisation
-    int pose_async = 0;
     int pose_xcd = 1;               // option "pose_xcd": the pose pass's items in eight contiguous ranges, one per XCD (round 6)
-    hipStream_t aux = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; 
     // lagged dense inverse of the reduced system as the CG preconditioner (ps_k_ldi.h / ps_host_ldi.h)
     int ldi_enable = 1;             // option "lagged_inverse"
     int ldi_max_n = 2048;           // option "ldi_max_unknowns": reduced systems up to this many unknowns

@@ -437,9 +437,8 @@ int build_coarse(ps_problem* h) {
         const bool cp_ne6 = (long)tasks.size() * D <= 6L * PS_CP_NT;
         int cp_per_cu = 0;
         {
-            // (the Chronopoulos-Gear instantiation: it holds more registers than the pipelined one, so its answer covers both)
-            const void* kfn = D == 6 ? (cp_ne6 ? (const void*)k_cg_persist<6, 6, false> : (const void*)k_cg_persist<6, 12, false>)
-                                     : (cp_ne6 ? (const void*)k_cg_persist<3, 6, false> : (const void*)k_cg_persist<3, 12, false>);
+            const void* kfn = D == 6 ? (cp_ne6 ? (const void*)k_cg_persist<6, 6> : (const void*)k_cg_persist<6, 12>)
+                                     : (cp_ne6 ? (const void*)k_cg_persist<3, 6> : (const void*)k_cg_persist<3, 12>);
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&cp_per_cu, kfn, PS_CP_NT, 0) != hipSuccess) { (void)hipGetLastError(); cp_per_cu = 0; }
         }
         h->cp_cus_needed = cp_per_cu > 0 ? cdiv(cp_nwg, cp_per_cu) : 0;
@@ -553,8 +552,6 @@ int build_coarse(ps_problem* h) {
             HIP_OK(hipMemsetAsync(h->xf_tq[0], 0, nrec * sizeof(double), h->stream));
             HIP_OK(hipMemsetAsync(h->xf_tq[1], 0, nrec * sizeof(double), h->stream));
             h->xf_rmax = rmax; h->xf_nwg = nwg; h->xf_nrec = nrec;
-            h->xf_ymax = 0;                                 // most rows of y = A_c^-1 t any workgroup needs (k_xcg_persist4 keeps them in registers)
-            for (int g = 0; g < nwg; ++g) h->xf_ymax = std::max(h->xf_ymax, (nhi[g] - nlo[g] + 1) * D);
             h->xf_pf = maxlen <= 16 ? 2 : (maxlen <= 48 ? 6 : 8);
             h->xf_ok = true;
             // one launch per SOLVE (ps_k_xcg_persist.h): all workgroups at once (one per compute unit), the records of a node
@@ -873,17 +870,13 @@ void cg_fused_launch(ps_problem* h, double tol, int count) {
             hipMemsetAsync(h->cp_exch, 0, (size_t)4 * h->cp_ntasks * D * sizeof(unsigned long long), h->stream);
             h->cp_salt = 1;
         }
-#define PS_CP_LAUNCH_(NE, PIPE) hipLaunchKernelGGL((k_cg_persist<D, NE, PIPE>), dim3(cdiv(h->cp_ntasks, PS_CP_NT / 64)), dim3(PS_CP_NT), 0, h->stream, h->nr_aug * D, \
+#define PS_CP_LAUNCH(NE) hipLaunchKernelGGL((k_cg_persist<D, NE>), dim3(cdiv(h->cp_ntasks, PS_CP_NT / 64)), dim3(PS_CP_NT), 0, h->stream, h->nr_aug * D, \
                            h->cp_ntasks, (const CpTask*)h->cp_tasks, h->cp_row_task0, h->acol_idx, h->Saug, h->cg_r[0], h->cg_w[0], h->cg_s[0], h->cg_p, \
                            h->cg_xh, h->hist, cap, nl, tol2, h->status, h->scalars, h->cp_exch, h->cp_salt, h->cp_spin, h->cp_dbg,                  \
                            CpRecover{h->nr, h->ncb, h->pnode, h->pw0, h->pw1, h->Linv, h->Lci2[h->lci_cur], h->Bmat, h->x})
         // (two instantiations by the number of exchanged sums per thread: the small one keeps 40 registers and 24 KB of LDS free)
-        // pipelined recurrences only where the last solve was an easy one (ps_core.hip: cg_pipelined)
-        const bool pipe = h->cg_pipelined == 2 || (h->cg_pipelined == 1 && h->last_pcg_iters > 0 && h->last_pcg_iters <= 32);
-#define PS_CP_LAUNCH(NE) do { if (pipe) PS_CP_LAUNCH_(NE, true); else PS_CP_LAUNCH_(NE, false); } while (0)
         if ((long)h->cp_ntasks * D <= 6L * PS_CP_NT) PS_CP_LAUNCH(6); else PS_CP_LAUNCH(12);
 #undef PS_CP_LAUNCH
-#undef PS_CP_LAUNCH_
         h->cg_launched = nl; h->cg_kernel_launches += 1; ++h->cp_launches;
         h->cp_recovered = true;                               // (a converged solve leaves x behind: the gated k_coarse_recover is not needed)
         return;
@@ -1059,66 +1052,27 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
     }
     bool fin_in_combine = false, fin_in_pairs = false;
     static const bool schur_split_env = ps_env("PS_SCHUR_SPLIT") != nullptr;      // (measurement build only; read once)
-    // option "pose_async" = 1: the pose pass on a second stream beside the pair kernel, joined in front of the finalisation
-    const bool pose_side = h->pose_async == 1 && h->npitems > 0 && h->npair_items > 0 && h->D == 6 && !(h->pose_mode && h->schur_mode != 0) &&
-                           !h->use_stream && !h->has_diag_tasks && h->schur_pipeline;
-    if (pose_side && !h->aux) {
-        if (!ps_pool().take(ps_pool().side_streams, &h->aux)) HIP_OK(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
-        HIP_OK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    }
     if (h->npitems > 0) {
         StageTimer t(h, PS_ST_POSE);
         const ObsWide wp{h->sidx_p, h->stiff_tab};
-        hipStream_t pst = h->stream;
-        if (pose_side) {
-            HIP_OK(hipEventRecord(h->ev_fork, h->stream));       // (the landmark pass -- here or in the previous tail -- is in front of it)
-            HIP_OK(hipStreamWaitEvent(h->aux, h->ev_fork, 0));
-            pst = h->aux;
-        }
         // (option "pose_xcd", default on: the pose-ordered items in eight contiguous ranges, one per XCD -- ps_k_linearize.h)
         const int per_xcd = h->pose_xcd ? cdiv(h->npitems, 8) : 0;
         const int nblk = per_xcd ? 8 * per_xcd : h->npitems;
         if (h->wide_obs)
-            hipLaunchKernelGGL(k_pose_pass<true>, dim3(nblk), dim3(256), 0, pst, h->pitems, h->pobs,
+            hipLaunchKernelGGL(k_pose_pass<true>, dim3(nblk), dim3(256), 0, h->stream, h->pitems, h->pobs,
                                h->poses, h->points, h->ogroups, h->Cinv, h->cvec, h->ppartial, lambda != 0.0 ? 1 : 0, wp, h->npitems, per_xcd);
         else
-            hipLaunchKernelGGL(k_pose_pass<false>, dim3(nblk), dim3(256), 0, pst, h->pitems, h->pobs,
+            hipLaunchKernelGGL(k_pose_pass<false>, dim3(nblk), dim3(256), 0, h->stream, h->pitems, h->pobs,
                                h->poses, h->points, h->ogroups, h->Cinv, h->cvec, h->ppartial, lambda != 0.0 ? 1 : 0, wp, h->npitems, per_xcd);
-        if (pose_side) HIP_OK(hipEventRecord(h->ev_join, h->aux));
-        const bool pose_schur = h->pose_mode && h->schur_mode != 0;
         // tiled Schur: the combine launch also finalizes the poses (unless a task writes a diagonal block)
-        fin_in_combine = pose_schur ? h->D == 6
-                                    : ((h->Spart || h->use_stream) && h->npair_items > 0 && !h->has_diag_tasks && h->D == 6);
+        fin_in_combine = h->Spart && h->npair_items > 0 && !h->has_diag_tasks && h->D == 6;
         // untiled Schur with the pipelined pair kernel: its trailing workgroups finalize the poses
-        fin_in_pairs = !pose_schur && !h->Spart && !h->use_stream && h->schur_pipeline && h->npair_items > 0 && !h->has_diag_tasks && h->D == 6 &&
-                       !schur_split_env && !pose_side;
-        if (!fin_in_combine && !fin_in_pairs && !pose_side)
+        fin_in_pairs = !h->Spart && h->schur_pipeline && h->npair_items > 0 && !h->has_diag_tasks && h->D == 6 && !schur_split_env;
+        if (!fin_in_combine && !fin_in_pairs)
             hipLaunchKernelGGL(k_pose_finalize, dim3(h->nr), dim3(64), 0, h->stream, h->nr, h->pitem_ptr,
                                h->ppartial, h->diag_slot, lambda, h->S, h->g);
     }
-    if (h->pose_mode && h->schur_mode != 0) {
-        // pose-stationary pair products (ps_k_schur3.h) + the combine launch (partials in segment order; it also finalizes the poses)
-        StageTimer t(h, PS_ST_SCHUR, 1);
-        if (ensure_dynamic_lds((const void*)k_schur_pose, (size_t)PS_PP_LDS_BYTES)) return -1;
-        hipLaunchKernelGGL(k_schur_pose, dim3(8 * h->pp_per_xcd), dim3(PS_PP_THREADS), PS_PP_LDS_BYTES, h->stream, h->pp_per_xcd, h->pp_order, h->pp_segs,
-                           h->pp_rows, h->pp_tasks, h->pp_pairs, h->Z, h->pp_part, h->schur_ablate);
-        hipLaunchKernelGGL(k_schur_combine, dim3(cdiv(h->pp_ncomb, 4) + (fin_in_combine ? cdiv(h->nr, 4) : 0)), dim3(256), 0,
-                           h->stream, h->pp_ncomb, h->pp_comb_items, h->pp_comb_tasks, h->pp_part, h->S,
-                           fin_in_combine ? h->nr : 0, h->pitem_ptr, h->ppartial, h->diag_slot, lambda, h->g);
-    } else if (h->npair_items > 0 && h->use_stream) {
-        StageTimer t(h, PS_ST_SCHUR, 1);
-        const size_t lds = (size_t)PS_ST_SUBROWS * PS_ST_ROWD * sizeof(double);
-        if (!h->st_attr_set) {
-            if (ensure_dynamic_lds((const void*)k_schur_stream, (size_t)(lds))) return -1;
-            h->st_attr_set = true;
-        }
-        hipLaunchKernelGGL(k_schur_stream, dim3(h->st_ntiles), dim3(PS_ST_THREADS), lds, h->stream, h->st_tiles, h->st_subs,
-                           reinterpret_cast<const uint4*>(h->st_entries), h->Z, h->st_part, h->schur_ablate);
-        hipLaunchKernelGGL(k_schur_combine, dim3(cdiv(h->st_ncomb, 4) + (fin_in_combine ? cdiv(h->nr, 4) : 0)), dim3(256), 0,
-                           h->stream, h->st_ncomb, h->st_comb_items, h->st_comb_tasks, h->st_part, h->S,
-                           fin_in_combine ? h->nr : 0, h->pitem_ptr, h->ppartial, h->diag_slot, lambda, h->g);
-    } else if (h->npair_items > 0) {
+    if (h->npair_items > 0) {
         StageTimer t(h, PS_ST_SCHUR, 1);
         // PS_SCHUR_SPLIT=1 (measurement switch): the same work as two launches over the two halves of
         // every XCD's list -- what splitting the Schur build into two bands for an overlapped all-reduce would cost
@@ -1145,13 +1099,6 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
         };
         launch_pairs(8 * (halfp / 4), lds_pad, 0, halfp);
         if (split2 && halfp < h->pair_per_xcd) launch_pairs(8 * ((h->pair_per_xcd - halfp + 3) / 4), 0, halfp, h->pair_per_xcd);
-        if (pose_side) {                                     // the pose pass ran beside the pair kernel: its partials are needed from here
-            HIP_OK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-            if (!fin_in_combine)
-                hipLaunchKernelGGL(k_pose_finalize, dim3(h->nr), dim3(64), 0, h->stream, h->nr, h->pitem_ptr,
-                                   h->ppartial, h->diag_slot, lambda, h->S, h->g);
-        }
-
         if (h->Spart)
             hipLaunchKernelGGL(k_schur_combine, dim3(cdiv(h->ncomb, 4) + (fin_in_combine ? cdiv(h->nr, 4) : 0)), dim3(256), 0,
                                h->stream, h->ncomb, h->comb_items, h->comb_tasks, h->Spart, h->S,

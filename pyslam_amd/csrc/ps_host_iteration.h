@@ -280,28 +280,8 @@ void xcg_launch(ps_problem* h, double tol, int count) {
         const size_t ovf_bytes = (size_t)PS_XF_ROWS * 8 * (D * sizeof(double) + sizeof(int32_t));      // (the kk = 0 lanes' one block more)
         const size_t room = 160 * 1024 - fixed - ovf_bytes - std::min<size_t>(lds0, 120 * 1024);
         const int pl = h->xf_pf == 8 ? (room >= 4 * per_pl ? 4 : (room >= 2 * per_pl ? 2 : 0)) : 0;
-        bool launched = true, four_done = false;
-        // four waves per workgroup, the rows of A_c^-1 and seven blocks per lane and row in registers (ps_k_xcg_persist4.h): BA-like
-        // rows (pf 8) whose coarse level fits its register arrays
-        if constexpr (D == 6) {
-            constexpr int X4_NYW = 11, X4_NQ = 5, PF4 = 6, PL4 = 4;
-            const size_t lds4 = lds0 + (size_t)PL4 * PS_X4_RPW * PS_X4_NT * (D * sizeof(double) + sizeof(int32_t));
-            if (h->xcg_persist4 && h->xf_pf == 8 && (nc & 1) == 0 && nc <= 128 * X4_NQ && nc <= 3 * PS_X4_NT && h->xf_ymax <= PS_X4_NW * X4_NYW &&
-                h->xf_nrec <= (size_t)PS_X4_NR * PS_X4_NT && lds4 + fixed <= 160 * 1024) {
-                auto k4 = k_xcg_persist4<6, PF4, PL4, 3, X4_NYW, X4_NQ>;
-                int per_cu_ = 0;
-                if (!ensure_dynamic_lds((const void*)k4, lds4) &&
-                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_, (const void*)k4, PS_X4_NT, lds4) == hipSuccess && per_cu_ >= 1 &&
-                    cdiv(h->xf_nwg, per_cu_) <= h->persist_capacity()) {
-                    hipLaunchKernelGGL(k4, dim3(h->xf_nwg), dim3(PS_X4_NT), lds4, h->stream, nr, h->arow_ptr, h->ell_wf, h->Saug, a, h->xf_cnt,
-                                       nl, tol * tol, h->hist, h->hist_cap, h->status, h->scalars, h->xstate, h->xp_exch, h->xp_salt, h->cp_spin, h->xp_dbg);
-                    ++h->xp_dbg_launches; ++h->xp4_launches;
-                    four_done = true;
-                } else (void)hipGetLastError();
-            }
-        }
-        if (four_done) { }
-        else if (h->xf_pf == 2) { if (ne2) PS_XP_LAUNCH(2, 0, 2); else PS_XP_LAUNCH(2, 0, 4); }
+        bool launched = true;
+        if (h->xf_pf == 2) { if (ne2) PS_XP_LAUNCH(2, 0, 2); else PS_XP_LAUNCH(2, 0, 4); }
         else if (pl == 4) { if (ne2) PS_XP_LAUNCH(6, 4, 2); else PS_XP_LAUNCH(6, 4, 4); }
         else if (pl == 2) { if (ne2) PS_XP_LAUNCH(6, 2, 2); else PS_XP_LAUNCH(6, 2, 4); }
         else { if (ne2) PS_XP_LAUNCH(6, 0, 2); else PS_XP_LAUNCH(6, 0, 4); }

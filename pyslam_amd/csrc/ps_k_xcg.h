@@ -564,8 +564,8 @@ __global__ void k_lag_status_check(const int32_t* __restrict__ lag_status, int32
 // 512 contiguous bytes; no segment sums in LDS, one barrier less.  (Rounds 4-5 gave a THREAD 64 consecutive entries of a row.)  The
 // phase is a chain of L2 round trips either way -- C4: 42 rows of 600 entries per interior workgroup, 5.2 us of k_xcg_persist's
 // 17.6 us per iteration in both forms; three rows of a wave requested together cost 200 B per lane of scratch in kernels that have
-// no register to spare -- which is why k_xcg_persist4 keeps its rows of the inverse in registers (ps_k_xcg_persist4.h).
-// A lane sums its columns in ascending order, the lanes by the wave's fixed tree: the same sums in all three kernels, run to run.
+// no register to spare.
+// A lane sums its columns in ascending order, the lanes by the wave's fixed tree: the same sums in both kernels, run to run.
 template <int RB = 1 /* rows of a wave requested together: the phase is a chain of L2 round trips, RB of them in flight */>
 PS_DEV void xcg_coarse_rows(const float* __restrict__ Ainv, int nc, int row_first, int nrows_y, const double* __restrict__ tl /* LDS */,
                             double* __restrict__ yl /* LDS */, int wv, int lane, int nwaves)

@@ -520,34 +520,6 @@ def test_per_observation_stiffness_motion_only_and_losses():
         assert rel_err(dev.get_dx()[0].ravel(), dx_ref) < 1e-8
 
 
-def test_streaming_schur_kernel_builds_the_same_reduced_system(monkeypatch):
-    """k_schur_stream (landmark tiles, block accumulators in registers, Z rows read once; off by default -- measured
-    slower than the gather kernel, DESIGN.md section 5 -- and enabled with PS_SCHUR_STREAM=1) against the default
-    k_schur_pairs: same reduced system to rounding (the partial sums group differently), duplicate observations of
-    one pose included, and bitwise reproducible run to run."""
-    lp, _ = synthetic.stereo_ba(num_kf=70, num_lm=6000, obs_per_lm=7, half_window=10, seed=13)
-    dup = np.arange(0, lp.num_obs, 97)                        # a few landmarks seen twice from the same pose
-    lp.obs_pose = np.concatenate([lp.obs_pose, lp.obs_pose[dup]])
-    lp.obs_point = np.concatenate([lp.obs_point, lp.obs_point[dup]])
-    lp.obs_uvd = np.concatenate([lp.obs_uvd, lp.obs_uvd[dup] + 0.3])
-    lp.obs_grp = np.concatenate([lp.obs_grp, lp.obs_grp[dup]])
-    lp = lp.finalize()
-    monkeypatch.setenv('PS_SCHUR_MODE', '0')                  # (the gather / streaming kernels' lists; round 4's default is k_schur_pose)
-    ref = device(lp)
-    ref.linearize(0.)
-    _, _, vals, g = ref.reduced_system()
-    monkeypatch.setenv('PS_SCHUR_STREAM', '1')
-    monkeypatch.setenv('PS_ST_TILES', '24')
-    out = []
-    for _ in range(2):
-        dev = device(lp)
-        dev.linearize(0.)
-        out.append(dev.reduced_system())
-        dev.close()
-    assert np.array_equal(out[0][2], out[1][2])
-    assert np.abs(out[0][2] - vals).max() <= 1e-12 * np.abs(vals).max() and np.array_equal(out[0][3], g)
-
-
 @pytest.mark.parametrize('shape', ['ba', 'pg_se3', 'pg_se2'])
 def test_explicit_pcg_three_launch_form_equals_the_four_launch_form(shape):
     """Explicit two-level PCG: the restriction folded into the SpMV epilogue + the recurrence t -= alpha P^T q (three
@@ -760,7 +732,6 @@ def test_pipelined_schur_kernel_equals_the_one_chunk_kernel_bit_for_bit(monkeypa
     0): the same pairs in the same order through the same accumulators, so the reduced system is equal to the last bit --
     tasks of 1 to 40 chunks, ragged last chunks, tasks shorter than one chunk, duplicate observations of a pose (tasks
     that write a diagonal block), with and without landmark tiles; and both equal the oracle's Schur complement."""
-    monkeypatch.setenv('PS_SCHUR_MODE', '0')                  # (the gather kernels' pair lists; round 4's default is k_schur_pose)
     if tiling == 'tiled':
         monkeypatch.setenv('PS_SCHUR_TILE_KB', '256')
         monkeypatch.setenv('PS_SCHUR_TILE_MIN_MB', '0')
@@ -800,7 +771,8 @@ def test_pipelined_schur_kernel_equals_the_one_chunk_kernel_bit_for_bit(monkeypa
 
 
 def test_option_values_out_of_range_are_refused():
-    """ps_set_option: the options added in round 3 reject values outside their range (and leave the handle usable)."""
+    """ps_set_option: the options added in round 3 reject values outside their range, and the names of the removed solver
+    variants are unknown options (and the handle stays usable)."""
     from pyslam_amd import synthetic, _native as nat
     from pyslam_amd.device import DeviceProblem
     lp, _ = synthetic.stereo_ba(num_kf=8, num_lm=200, obs_per_lm=4, half_window=4, seed=1)
@@ -808,6 +780,9 @@ def test_option_values_out_of_range_are_refused():
     for name, bad in (('xcg_fused', 3), ('ldi_seed_lag', 0), ('ldi_max_unknowns', 5000), ('ldi_seed_steps', 0), ('ldi_cap', 0)):
         with pytest.raises(nat.NativeError):
             dev.set_option(name, bad)
+    for name in ('schur_mode', 'schur_stream', 'xcg_persist4', 'cg_pipelined', 'pose_async'):
+        with pytest.raises(nat.NativeError):
+            dev.set_option(name, 0)
     for name, ok in (('xcg_fused', 2), ('ldi_seed_lag', 1), ('ldi_max_unknowns', 3328), ('ldi_direct', 1), ('direct_fused', 0), ('coarse_auto_hold', 0)):
         dev.set_option(name, ok)
     out = dev.gn_iteration(0., 1e-12, 500, True)
@@ -815,15 +790,11 @@ def test_option_values_out_of_range_are_refused():
 
 
 @pytest.mark.parametrize('case', ['multi_segment', 'sparse', 'constants', 'duplicates'])
-def test_pose_stationary_schur_kernel_against_the_gather_kernels_and_the_oracle(monkeypatch, case):
-    """k_schur_pose (round 4, csrc/ps_k_schur3.h: a workgroup holds a segment of one pose's Z rows in LDS and gathers only the
-    partner rows; one partial per (segment, partner) task, summed in segment order) against the gather kernel on the same
-    handle (PS_SCHUR_MODE=2 builds both list sets; option "schur_mode") -- same reduced system to rounding (the sums group
-    differently), bit-reproducible run to run -- and against the oracle's Schur complement.  Poses with several segments
-    (more than 512 observations), tasks of one pair, constant landmarks and poses; a landmark seen twice from one pose
-    leaves the handle on the gather kernels (a diagonal-block task)."""
+def test_gather_schur_kernel_against_the_oracle(case):
+    """The Schur stage (k_schur_pairs_db, with k_schur_combine where the pair list is tiled): bit-reproducible run to run, the
+    oracle's Schur complement, and a converging Gauss-Newton iteration.  Poses with more than 512 observations, tasks of
+    one pair, constant landmarks and poses, a landmark seen twice from one pose (a diagonal-block task)."""
     import scipy.sparse.linalg as spla
-    monkeypatch.setenv('PS_SCHUR_MODE', '2')
     if case == 'multi_segment':
         lp, _ = synthetic.stereo_ba(num_kf=14, num_lm=9000, obs_per_lm=6, half_window=5, seed=21)     # ~3 900 observations per pose
     elif case == 'sparse':
@@ -851,19 +822,9 @@ def test_pose_stationary_schur_kernel_against_the_gather_kernels_and_the_oracle(
         lp = lp.finalize()
     dev = device(lp)
     dev.linearize(0.)
-    _, _, v1, g1 = dev.reduced_system()
+    v1 = dev.reduced_system()[2]
     dev.linearize(0.)
     assert np.array_equal(dev.reduced_system()[2], v1)             # reproducible
-    dev.set_option('schur_mode', 0)
-    dev.linearize(0.)
-    _, _, v0, g0 = dev.reduced_system()
-    assert np.array_equal(g0, g1)
-    if case == 'duplicates':
-        assert np.array_equal(v0, v1)                              # the pose-stationary lists were not built: the same kernel both times
-    else:
-        assert np.abs(v0 - v1).max() <= 1e-13 * np.abs(v0).max()
-    dev.set_option('schur_mode', 1)
-    dev.linearize(0.)
     S, gd = dev.reduced_dense()
     P, b, _ = orc.normal_equations(lp, points_first=False)
     n = S.shape[0]
