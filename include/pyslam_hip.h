@@ -146,6 +146,25 @@ int ps_warm_up(void);
    creates a host thread, and none is alive between calls.  (SURVEY section 8b asked for "no internal host threads": true
    of the iteration path; at create time the device build is the single-threaded route.) */
 int ps_problem_create(const ps_problem_desc* desc, void* stream, ps_problem** out);
+
+/* Pose factors whose blocks the CALLER evaluates (Problem with Options.hybrid_blocks: user-defined residual blocks on poses).
+   Row k stands for poses (i[k], j[k]) -- pose indices, i[k] = -1 for a row on one pose -- and enters the pair structure as a
+   pose-pose edge does.  Its values, one scratch row [H11 | H12 | H22 | g1 | g2] (3 D^2 + 2 D doubles, g = -J~^T e~) per row,
+   come from ps_set_host_rows before each linearisation and are assembled into S and g with the edges and priors (the
+   Marquardt (1 + lambda) scaling included).  A handle made here is a HYBRID handle: its own cost passes see only the typed
+   blocks, so everything that would decide from a cost inside one call is off (ps_solve and ps_motion_only_solve return 1,
+   option "expect_next" is ignored, the one-launch motion-only iteration and the lagged dense inverse are not used). */
+typedef struct ps_host_rows_desc {
+    int64_t num;
+    const int32_t* i;
+    const int32_t* j;
+} ps_host_rows_desc;
+int ps_problem_create_hybrid(const ps_problem_desc* desc, const ps_host_rows_desc* rows, void* stream, ps_problem** out);
+/* Values of the host rows (num rows of 3 D^2 + 2 D doubles, host memory, num = the create call's) at the current
+   parameters, and the caller's cost of its blocks at the same point (blocks whose poses are all constant excluded).  A
+   following ps_gn_iteration without line search returns the typed cost plus this cost; with line search the cost after
+   the step is the typed blocks' only and the caller adds its own.  Copied on the solver's stream before this returns. */
+int ps_set_host_rows(ps_problem* h, const double* rows, int64_t num, double cost);
 int ps_problem_destroy(ps_problem* h);
 int ps_get_info(ps_problem* h, ps_problem_info* info);
 

@@ -40,6 +40,10 @@ class ProblemDesc(C.Structure):
 PS_DESC_DEVICE_PARAMS, PS_DESC_DEVICE_TABLES = 1, 2
 
 
+class HostRowsDesc(C.Structure):
+    _fields_ = [('num', C.c_int64), ('i', c_i32p), ('j', c_i32p)]
+
+
 class SolveOptions(C.Structure):
     _fields_ = [('max_iters', C.c_int32), ('allow_nondecreasing_steps', C.c_int32), ('max_nondecreasing_steps', C.c_int32),
                 ('linesearch', C.c_int32), ('min_update_norm', C.c_double), ('min_cost', C.c_double),
@@ -76,6 +80,8 @@ SIGNATURES = {
     'ps_device_count': (C.c_int, []),
     'ps_warm_up': (C.c_int, []),
     'ps_problem_create': (C.c_int, [C.POINTER(ProblemDesc), C.c_void_p, C.POINTER(H)]),
+    'ps_problem_create_hybrid': (C.c_int, [C.POINTER(ProblemDesc), C.POINTER(HostRowsDesc), C.c_void_p, C.POINTER(H)]),
+    'ps_set_host_rows': (C.c_int, [H, c_f64p, C.c_int64, C.c_double]),
     'ps_problem_destroy': (C.c_int, [H]),
     'ps_get_info': (C.c_int, [H, C.POINTER(ProblemInfo)]),
     'ps_eval_cost': (C.c_int, [H, C.c_int, c_f64p]),

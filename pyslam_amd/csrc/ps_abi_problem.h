@@ -159,7 +159,7 @@ struct DescStage {
     }
 };
 
-int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** out) {
+static int problem_create(const ps_problem_desc* d_in, const ps_host_rows_desc* hrows, void* stream, ps_problem** out) {
     const bool timing = ps_env("PS_CREATE_TIMING") != nullptr;
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
@@ -428,8 +428,17 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
             return fail("pose factor index out of range");
     if (h->upload(&h->fgroups, fg) || h->upload(&h->f_i, f_i) || h->upload(&h->f_j, f_j) ||
         h->upload(&h->f_grp, f_grp) || h->upload(&h->f_Tinv, f_T)) return -1;
+    // host rows (ps_problem_create_hybrid): pose pairs of the caller's blocks, numbered F, F + 1, ... after the edges and priors
+    const long FH = h->FH = hrows ? std::max<int64_t>(0, hrows->num) : 0;
+    h->hybrid = hrows != nullptr;
+    if (FH > 0 && (!hrows->i || !hrows->j)) return fail("null host row table");
+    for (long k = 0; k < FH; ++k)
+        if (hrows->j[k] < 0 || hrows->j[k] >= P || hrows->i[k] < -1 || hrows->i[k] >= P || hrows->i[k] == hrows->j[k])
+            return fail("host row pose index out of range");
+    auto fac_i = [&](long f) -> int { return f < F ? f_i[f] : hrows->i[f - F]; };
+    auto fac_j = [&](long f) -> int { return f < F ? f_j[f] : hrows->j[f - F]; };
     const int FROW = 3 * DD + 2 * D;
-    if (h->alloc(&h->fscratch, (size_t)F * FROW)) return -1;
+    if (h->alloc(&h->fscratch, (size_t)(F + FH) * FROW)) return -1;
 
     lap("pose factors");
     // ---- Schur pairs per landmark (upper-triangle block keys)
@@ -653,12 +662,17 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
     }
     // ---- block pattern of the reduced system
     std::vector<uint64_t> keys;                 // upper keys (ri <= rj)
-    keys.reserve(task_keyv.size() + nr + F + d->num_extra_pairs);
+    keys.reserve(task_keyv.size() + nr + F + FH + d->num_extra_pairs);
     for (int r = 0; r < nr; ++r) keys.push_back(((uint64_t)r << 32) | (uint32_t)r);
     keys.insert(keys.end(), task_keyv.begin(), task_keyv.end());
     for (long f = 0; f < E; ++f) {
         const int ra = d->pose_rid[f_i[f]], rb = d->pose_rid[f_j[f]];
         if (ra >= 0 && rb >= 0 && ra != rb)
+            keys.push_back(((uint64_t)std::min(ra, rb) << 32) | (uint32_t)std::max(ra, rb));
+    }
+    for (long k = 0; k < FH; ++k) {
+        const int ra = hrows->i[k] >= 0 ? d->pose_rid[hrows->i[k]] : -1, rb = d->pose_rid[hrows->j[k]];
+        if (ra >= 0 && rb >= 0)
             keys.push_back(((uint64_t)std::min(ra, rb) << 32) | (uint32_t)std::max(ra, rb));
     }
     for (long k = 0; k < d->num_extra_pairs; ++k) {
@@ -777,8 +791,8 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
         struct C { int32_t slot, off, tr; };
         std::vector<C> cs;
         std::vector<std::vector<int32_t>> gl(nr);
-        for (long f = 0; f < F; ++f) {
-            const int ra = f_i[f] >= 0 ? d->pose_rid[f_i[f]] : -1, rb = d->pose_rid[f_j[f]];
+        for (long f = 0; f < F + FH; ++f) {
+            const int ra = fac_i(f) >= 0 ? d->pose_rid[fac_i(f)] : -1, rb = d->pose_rid[fac_j(f)];
             const int32_t base = (int32_t)(f * FROW);
             if ((size_t)f * FROW >= (1UL << 31)) return fail("too many pose factors for 32-bit scratch offsets");
             if (ra >= 0) { cs.push_back({diag_slot[ra], base, 0}); gl[ra].push_back(base + 3 * DD); }
@@ -907,5 +921,31 @@ int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** ou
     lap("scalars + final sync");
     guard.ok = true;
     *out = h;
+    return 0;
+}
+
+int ps_problem_create(const ps_problem_desc* d_in, void* stream, ps_problem** out) {
+    return problem_create(d_in, nullptr, stream, out);
+}
+
+int ps_problem_create_hybrid(const ps_problem_desc* d_in, const ps_host_rows_desc* rows, void* stream, ps_problem** out) {
+    if (!rows) return fail("null argument");
+    return problem_create(d_in, rows, stream, out);
+}
+
+int ps_set_host_rows(ps_problem* h, const double* rows, int64_t num, double cost) {
+    if (!h) return fail("null argument");
+    if (!h->hybrid) return fail("ps_set_host_rows: the handle has no host rows (ps_problem_create_hybrid)");
+    if (num != h->FH) return fail("ps_set_host_rows: row count differs from the create call's");
+    if (num > 0 && !rows) return fail("null argument");
+    const size_t FROW = 3 * (size_t)h->D * h->D + 2 * (size_t)h->D;
+    if (num > 0) {
+        // behind whatever the stream holds (k_factor_pass writes the rows before these, never these)
+        HIP_OK(hipMemcpyAsync(h->fscratch + (size_t)h->F * FROW, rows, (size_t)num * FROW * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_OK(hipStreamSynchronize(h->stream));
+    }
+    h->host_cost = cost;
+    h->prelin_valid = false;                                 // (a linearisation enqueued ahead would lack these rows)
+    h->last_cost = h->prev_cost = -1.0;                      // the core's own costs miss the caller's blocks: no cost history
     return 0;
 }

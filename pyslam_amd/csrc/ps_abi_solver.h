@@ -28,7 +28,7 @@ int ps_eval_cost(ps_problem* h, int include_all_constant, double* cost) {
     else if (cost_pass(h, include_all_constant, SC_COST)) return -1;
     if (read_scalars(h)) return -1;
     *cost = h->h_scalars[SC_COST];
-    if (include_all_constant) h->last_cost = *cost;         // the cost AT the current parameters (what ps_gn_iteration's line-search
+    if (include_all_constant && !h->hybrid) h->last_cost = *cost;         // the cost AT the current parameters (what ps_gn_iteration's line-search
     return 0;                                               // cost is for the parameters it leaves behind)
 }
 
@@ -308,6 +308,7 @@ static int exchange_reduced_system(ps_problem* h) {
 
 int ps_set_collective(ps_problem* h, void* nccl_all_reduce_fn, void* nccl_comm) {
     if (!h) return fail("null argument");
+    if (h->hybrid && nccl_comm) return fail("a hybrid handle (host rows) is not landmark-sharded");
     h->nccl_allreduce = (ps_problem::allreduce_fn)nccl_all_reduce_fn;
     h->nccl_comm = nccl_comm;
     return 0;
@@ -397,7 +398,7 @@ static int gn_iteration_impl(ps_problem* h, double lambda, double pcg_tol, int p
     h->lmfail_check = 0;
     if (start_cost_out) {
         const bool published_path = !(h->nccl_allreduce && h->nccl_comm) && h->nr > 0 && h->pcg_variant == 1 &&
-                                    !(h->mo_fused && h->nv == 0 && h->F == 0 && h->D == 6 && h->N == h->Np && h->max_pose_obs <= 2048);
+                                    !(h->mo_fused && !h->hybrid && h->nv == 0 && h->F == 0 && h->D == 6 && h->N == h->Np && h->max_pose_obs <= 2048);
         if (!published_path) {                              // paths that end otherwise: a call of its own
             if (ps_eval_cost(h, 1, start_cost_out)) return -1;
             start_cost_out = nullptr;
@@ -475,7 +476,7 @@ static int gn_iteration_impl(ps_problem* h, double lambda, double pcg_tol, int p
         h->prev_cost = h->last_cost; h->last_cost = sb[0];      // (all-reduced: the same on every rank)
         return 0;
     }
-    if (h->mo_fused && h->nv == 0 && h->F == 0 && h->nr > 0 && h->D == 6 && h->N == h->Np && h->pcg_variant == 1 &&
+    if (h->mo_fused && !h->hybrid && h->nv == 0 && h->F == 0 && h->nr > 0 && h->D == 6 && h->N == h->Np && h->pcg_variant == 1 &&
         h->max_pose_obs <= 2048) {
         // motion-only: block-diagonal reduced system, the whole iteration is ONE launch (one workgroup per pose;
         // beyond ~2 000 observations per pose one workgroup is slower than the multi-kernel path)
@@ -537,7 +538,7 @@ static int gn_iteration_impl(ps_problem* h, double lambda, double pcg_tol, int p
     }
     if (!h->guards.empty()) { hipStreamSynchronize(h->stream); if (h->side) hipStreamSynchronize(h->side); if (h->ldi_stream) hipStreamSynchronize(h->ldi_stream); h->check_guards("after ps_gn_iteration"); }
     if (h->h_status[ST_LM_FAIL]) return fail("a landmark block H_ll is not positive definite");
-    if (cost_out) *cost_out = linesearch ? h->h_scalars[SC_COST] : h->h_scalars[SC_LINCOST];
+    if (cost_out) *cost_out = linesearch ? h->h_scalars[SC_COST] : h->h_scalars[SC_LINCOST] + (h->hybrid ? h->host_cost : 0.0);
     if (start_cost_out) {                                    // (last_cost: what ps_eval_cost would have left, if no wait took it over)
         *start_cost_out = h->h_scalars[SC_STARTCOST];
         if (h->start_cost_pending) { h->start_cost_pending = false; h->last_cost = *start_cost_out; }
@@ -545,6 +546,7 @@ static int gn_iteration_impl(ps_problem* h, double lambda, double pcg_tol, int p
     // (without a line search the cost returned is the cost at the START point: what the parameters left behind cost is unknown,
     //  and the tags that compare linearisation points by their cost must not take one for the other -- round-3 ADVICE)
     h->prev_cost = h->last_cost; h->last_cost = linesearch ? h->h_scalars[SC_COST] : -1.0;
+    if (h->hybrid) h->last_cost = h->prev_cost = -1.0;       // (the typed blocks' cost alone: no history to decide from)
     // a slot whose reduction did not run (no reduced poses / no variable landmarks) is stale: count it as 0
     if (dx_norm_out) *dx_norm_out = std::sqrt((h->nr > 0 ? h->h_scalars[SC_DXP2] : 0.0) + (h->nv > 0 ? h->h_scalars[SC_DXL2] : 0.0));
     return 0;
@@ -561,6 +563,7 @@ int ps_solve(ps_problem* h, const ps_solve_options* o, double pcg_tol, int pcg_m
              int32_t* n_history, int32_t* iterations, double* last_dx_norm, int32_t* pcg_iters, double* pcg_relres, double* iter_ms) {
     if (!h || !o || !cost_history || !n_history) return fail("null argument");
     if (h->nccl_allreduce && h->nccl_comm) return 1;          // sharded: every rank's start cost needs the all-reduce (the caller loops)
+    if (h->hybrid) return 1;                                  // the stopping rules need the caller's blocks' cost (the caller loops)
     if (o->max_iters < 0 || (long)o->max_iters + 2 > cap) return 1;
     if (ps_reset_solver_state(h)) return -1;
     int n = 0, it = 0, nd = 0;
@@ -610,7 +613,7 @@ int ps_motion_only_solve(ps_problem* h, const ps_solve_options* o, double* cost_
                          int32_t* iterations, double* last_dx_norm, double* pose12_out) {
     if (!h || !o || !cost_history || !n_history) return fail("null argument");
     h->prelin_valid = h->prelm_valid = false;
-    const bool eligible = h->mo_fused && h->nv == 0 && h->F == 0 && h->nr == 1 && h->P == 1 && h->D == 6 && h->N == h->Np &&
+    const bool eligible = h->mo_fused && !h->hybrid && h->nv == 0 && h->F == 0 && h->nr == 1 && h->P == 1 && h->D == 6 && h->N == h->Np &&
                           h->pcg_variant == 1 && h->max_pose_obs <= 2048;
     const int need = o->max_iters + 2;                        // the start cost + at most max_iters + 1 iterations
     if (!eligible || need + 16 > PS_MO_HIST_WORDS || need > cap) return 1;       // not an error: the caller iterates itself
@@ -819,7 +822,7 @@ int ps_set_option(ps_problem* h, const char* name, double value) {
     if (!h || !name) return fail("null argument");
     const std::string n(name);
     // what a caller's own loop says about its next call leaves what was computed ahead in place
-    if (n == "expect_next") { h->expect_next = value != 0; return 0; }
+    if (n == "expect_next") { h->expect_next = value != 0 && !h->hybrid; return 0; }      // (hybrid: see ps_problem_create_hybrid)
     if (n == "solve_horizon") { h->solve_horizon = value < 0 ? -1 : (int)std::min(value, 1e6); return 0; }
     h->prelin_valid = h->prelm_valid = false;
     if (n == "pcg_variant") { if (value != 0 && value != 1) return fail("pcg_variant must be 0 or 1"); h->pcg_variant = (int)value; }

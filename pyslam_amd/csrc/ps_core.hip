@@ -160,6 +160,9 @@ struct ps_problem {
     int P = 0, nr = 0, L = 0, nv = 0;
     long N = 0, Nl = 0, Np = 0;     // observations: all / on variable points / on variable poses
     long F = 0;                     // pose factors (edges + priors)
+    long FH = 0;                    // host rows (ps_problem_create_hybrid): pose factors after the F in fscratch, values from the caller
+    bool hybrid = false;            // made by ps_problem_create_hybrid: the core's cost passes do not see every block
+    double host_cost = 0.0;         // the caller's cost at the point of its last ps_set_host_rows
     long npairs = 0;
     int nnzb = 0;
     size_t dev_bytes = 0;

@@ -144,9 +144,10 @@ struct PairRec { uint64_t key; int32_t a, b, tile; };
 
 template <int D>
 int launch_factor_pass(ps_problem* h, double lambda, double* dbg = nullptr) {
-    if (h->F == 0) return 0;
-    hipLaunchKernelGGL(k_factor_pass<D>, dim3(cdiv(h->F, PS_FP_FACTORS)), dim3(256), 0, h->stream, (int)h->F, h->f_i,
-                       h->f_j, h->f_Tinv, h->f_grp, h->fgroups, h->poses, h->fscratch, dbg);
+    if (h->F == 0 && h->FH == 0) return 0;
+    if (h->F > 0)                                             // (host rows: ps_set_host_rows has put them behind these)
+        hipLaunchKernelGGL(k_factor_pass<D>, dim3(cdiv(h->F, PS_FP_FACTORS)), dim3(256), 0, h->stream, (int)h->F, h->f_i,
+                           h->f_j, h->f_Tinv, h->f_grp, h->fgroups, h->poses, h->fscratch, dbg);
     if (dbg) return 0;                                        // parity tap: blocks only, S and g stay untouched
     const long threads = (long)h->nes * D * D + (long)h->nr * D;
     hipLaunchKernelGGL(k_factor_assemble<D>, dim3(cdiv(threads, 256)), dim3(256), 0, h->stream, h->nes,
@@ -1104,7 +1105,7 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
                                h->stream, h->ncomb, h->comb_items, h->comb_tasks, h->Spart, h->S,
                                fin_in_combine ? h->nr : 0, h->pitem_ptr, h->ppartial, h->diag_slot, lambda, h->g);
     }
-    if (h->F > 0 && h->nr > 0) {
+    if ((h->F > 0 || h->FH > 0) && h->nr > 0) {
         StageTimer t(h, PS_ST_EDGES);
         if (h->D == 6) launch_factor_pass<6>(h, lambda); else launch_factor_pass<3>(h, lambda);
     }

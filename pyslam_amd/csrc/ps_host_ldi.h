@@ -14,7 +14,7 @@ namespace {
 
 bool ldi_eligible(const ps_problem* h) {
     const long n = (long)h->nr * h->D;
-    return h->ldi_enable && h->pcg_variant == 1 && !h->cg_explicit && !h->cg_split && h->G > 0 && n > h->direct_max &&
+    return h->ldi_enable && !h->hybrid && h->pcg_variant == 1 && !h->cg_explicit && !h->cg_split && h->G > 0 && n > h->direct_max &&
            n <= h->ldi_max_n && n <= PS_LDI_MAXN && !(h->nccl_allreduce && h->nccl_comm);
 }
 

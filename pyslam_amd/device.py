@@ -59,7 +59,15 @@ class DeviceProblem:
             d.num_extra_pairs = len(extra_pairs[0])
             d.extra_pair_i, d.extra_pair_j = I(extra_pairs[0]), I(extra_pairs[1])
         self._h = nat.H()
-        nat.check(lib.ps_problem_create(C.byref(d), C.c_void_p(stream or 0), C.byref(self._h)))
+        self.host = None                # hybrid.HostBlocks (attach_host): user blocks evaluated on the host
+        if lp.hybrid:
+            hr = nat.HostRowsDesc()
+            hi, hj = np.ascontiguousarray(lp.h_i, dtype=np.int32), np.ascontiguousarray(lp.h_j, dtype=np.int32)
+            keep.extend((hi, hj))
+            hr.num, hr.i, hr.j = hi.shape[0], (nat.i32p(hi) if hi.shape[0] else None), (nat.i32p(hj) if hj.shape[0] else None)
+            nat.check(lib.ps_problem_create_hybrid(C.byref(d), C.byref(hr), C.c_void_p(stream or 0), C.byref(self._h)))
+        else:
+            nat.check(lib.ps_problem_create(C.byref(d), C.c_void_p(stream or 0), C.byref(self._h)))
         info = nat.ProblemInfo()
         nat.check(lib.ps_get_info(self._h, C.byref(info)))
         self.info = {k: getattr(info, k) for k, _ in nat.ProblemInfo._fields_}
@@ -77,18 +85,56 @@ class DeviceProblem:
         except Exception:
             pass
 
+    # ---- user blocks on the host (Options.hybrid_blocks) ------------------
+    def attach_host(self, host):
+        """The user blocks of a hybrid handle (pyslam_amd/hybrid.py: HostBlocks).  From here on every linearisation uploads their
+        rows at the current poses first, and every cost this object returns includes theirs."""
+        if not self.lp.hybrid:
+            raise ValueError('attach_host: the tables have no host rows')
+        self.host = host
+        self._hposes = self._read_poses()
+        self.host_seconds = [0., 0.]      # (host evaluation, row upload) since attach: tools/hybrid_bench.py
+
+    def _read_poses(self):
+        poses = np.zeros((self.lp.num_poses, self.lp.pose_width))
+        nat.check(self._lib.ps_get_params(self._h, nat.f64p(poses), None))
+        return poses
+
+    def set_host_rows(self, rows, cost):
+        """Values of the host rows (ps_set_host_rows) and the cost of their blocks at the same point."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        nat.check(self._lib.ps_set_host_rows(self._h, nat.f64p(rows) if rows.size else None, rows.shape[0], float(cost)))
+
+    def _upload_host_rows(self):
+        import time
+        t0 = time.perf_counter()
+        rows, cost = self.host.evaluate(self._hposes)
+        t1 = time.perf_counter()
+        self.set_host_rows(rows, cost)
+        self.host_seconds[0] += t1 - t0
+        self.host_seconds[1] += time.perf_counter() - t1
+
     # ---- hot path ------------------------------------------------------
     def eval_cost(self, include_all_constant=True):
         c = C.c_double()
         nat.check(self._lib.ps_eval_cost(self._h, int(include_all_constant), C.byref(c)))
+        if self.host is not None:
+            return c.value + self.host.cost(self._hposes, include_all_constant)
         return c.value
 
     def gn_iteration(self, lm_lambda=0., pcg_tol=1e-12, pcg_max_iters=1000, linesearch=True):
         """-> (cost, ||dx||, pcg iterations, pcg relative residual); parameters are updated."""
+        if self.host is not None:
+            self._upload_host_rows()
         cost, nrm, rel, it = C.c_double(), C.c_double(), C.c_double(), C.c_int()
         nat.check(self._lib.ps_gn_iteration(self._h, lm_lambda, pcg_tol or 0., pcg_max_iters, int(linesearch),
                                             C.byref(cost), C.byref(nrm), C.byref(it), C.byref(rel)))
-        return cost.value, nrm.value, it.value, rel.value
+        c = cost.value
+        if self.host is not None:
+            self._hposes = self._read_poses()
+            if linesearch:                # (without a line search the core returned the linearisation point's cost, rows' included)
+                c += self.host.cost(self._hposes, True)
+        return c, nrm.value, it.value, rel.value
 
     def motion_only_solve(self, opt, linesearch):
         """Problem.solve's whole loop in one launch (ps_motion_only_solve) for a one-pose motion-only problem.
@@ -100,7 +146,7 @@ class DeviceProblem:
         o.min_update_norm, o.min_cost = float(opt.min_update_norm), float(opt.min_cost)
         o.min_cost_decrease, o.lm_lambda = float(opt.min_cost_decrease), float(getattr(opt, 'lm_lambda', 0.))
         cap = o.max_iters + 2
-        if cap < 2 or cap > 238:
+        if cap < 2 or cap > 238 or self.host is not None:
             return None
         hist, pose = np.zeros(cap), np.zeros(12)
         n, its, dxn = C.c_int32(), C.c_int32(), C.c_double()
@@ -120,7 +166,7 @@ class DeviceProblem:
         o.min_update_norm, o.min_cost = float(opt.min_update_norm), float(opt.min_cost)
         o.min_cost_decrease, o.lm_lambda = float(opt.min_cost_decrease), float(getattr(opt, 'lm_lambda', 0.))
         cap = o.max_iters + 2
-        if cap < 2 or cap > 100000:
+        if cap < 2 or cap > 100000 or self.host is not None:
             return None
         buf = getattr(self, '_solve_buf', None)              # (result buffers kept on the object: four allocations less per solve)
         if buf is None or buf[0].size < cap:
@@ -182,6 +228,8 @@ class DeviceProblem:
         return done.value != 0, sb[0], sb[1], dxp2.value, it.value, rel.value
 
     def linearize(self, lm_lambda=0.):
+        if self.host is not None:
+            self._upload_host_rows()
         nat.check(self._lib.ps_linearize(self._h, lm_lambda))
 
     def solve_reduced(self, tol=1e-12, max_iters=1000):
@@ -194,6 +242,8 @@ class DeviceProblem:
 
     def apply_update(self, step=1.0):
         nat.check(self._lib.ps_apply_update(self._h, step))
+        if self.host is not None:
+            self._hposes = self._read_poses()
 
     def step_norm(self):
         n2 = C.c_double()
@@ -205,6 +255,8 @@ class DeviceProblem:
 
     def restore(self):
         nat.check(self._lib.ps_restore_params(self._h))
+        if self.host is not None:
+            self._hposes = self._read_poses()
 
     def reset_solver_state(self):
         """A new solve starts here: nothing the solver carried over from earlier calls is used (ps_reset_solver_state)."""
@@ -223,6 +275,8 @@ class DeviceProblem:
     # ---- covariance by columns (reference problem.py:196-216) ------------
     def covariance_begin(self):
         """Linearise at the current parameters and prepare the reduced solver."""
+        if self.host is not None:
+            self._upload_host_rows()
         nat.check(self._lib.ps_covariance_begin(self._h))
 
     def covariance_column(self, kind, index, comp, tol=1e-13, max_iters=4000):
@@ -256,6 +310,8 @@ class DeviceProblem:
         p = poses if poses is None or nat.is_resident(poses) else np.ascontiguousarray(poses, dtype=np.float64)
         q = points if points is None or nat.is_resident(points) else np.ascontiguousarray(points, dtype=np.float64)
         nat.check(self._lib.ps_set_params(self._h, nat.f64p(p), nat.f64p(q)))
+        if self.host is not None and poses is not None:
+            self._hposes = self._read_poses()
 
     def reduce_buffer(self):
         """(device pointer, number of doubles) of the exchange buffer [upper(S) | g | cost | flag] the

@@ -19,6 +19,10 @@ Table layout (all fp64 / int32, C-contiguous):
 * ``e_*``        binary pose-pose edges: i, j, T_obs^-1 (same packing as poses), group idx
 * ``u_*``        unary pose priors:      i,    T_obs^-1,                        group idx
 * ``edge_groups``(G, 3) [stiffness idx, loss id, loss k]
+* ``h_*``        user blocks evaluated on the host (``lower(..., hybrid=True)``, pyslam_amd/hybrid.py): block indices
+                 ``h_blocks`` (B,) in the problem's order, their pose indices ``h_pose`` (one per key, ``h_pose_ptr`` (B+1,)),
+                 and one pose-pair row per pair of distinct variable poses ``h_i``, ``h_j`` (i = -1: a row on one pose),
+                 rows of block b at ``h_ptr[b]:h_ptr[b + 1]``
 """
 from dataclasses import dataclass, field
 
@@ -62,6 +66,12 @@ class LoweredProblem:
     u_grp: np.ndarray = None
     stiffd: np.ndarray = None
     edge_groups: np.ndarray = None
+    h_blocks: np.ndarray = None
+    h_pose: np.ndarray = None
+    h_pose_ptr: np.ndarray = None
+    h_i: np.ndarray = None
+    h_j: np.ndarray = None
+    h_ptr: np.ndarray = None
     pose_keys: list = field(default_factory=list)
     point_keys: list = field(default_factory=list)
 
@@ -89,6 +99,19 @@ class LoweredProblem:
     @property
     def num_priors(self):
         return 0 if self.u_i is None else self.u_i.shape[0]
+
+    @property
+    def num_host_blocks(self):
+        return 0 if self.h_blocks is None else self.h_blocks.shape[0]
+
+    @property
+    def num_host_rows(self):
+        return 0 if self.h_i is None else self.h_i.shape[0]
+
+    @property
+    def hybrid(self):
+        """True when user blocks are evaluated on the host beside the tables (ps_problem_create_hybrid)."""
+        return self.num_host_blocks > 0
 
     @property
     def num_reduced(self):
@@ -122,6 +145,12 @@ class LoweredProblem:
         self.u_grp = _i(self.u_grp if self.u_grp is not None else np.zeros(self.u_i.shape[0]))
         self.stiffd = _f(self.stiffd if self.stiffd is not None else [], (-1, d * d))
         self.edge_groups = _f(self.edge_groups if self.edge_groups is not None else [], (-1, 3))
+        self.h_blocks = _i(self.h_blocks if self.h_blocks is not None else [])
+        self.h_pose = _i(self.h_pose if self.h_pose is not None else [])
+        self.h_pose_ptr = _i(self.h_pose_ptr if self.h_pose_ptr is not None else [0])
+        self.h_i = _i(self.h_i if self.h_i is not None else [])
+        self.h_j = _i(self.h_j if self.h_j is not None else [])
+        self.h_ptr = _i(self.h_ptr if self.h_ptr is not None else [0])
         self.validate()
         return self
 
@@ -140,12 +169,18 @@ class LoweredProblem:
             assert self.e_grp.max() < self.edge_groups.shape[0]
         if self.num_priors:
             assert self.u_grp.max() < self.edge_groups.shape[0]
+        B = self.num_host_blocks
+        assert self.h_ptr.shape == (B + 1,) and self.h_pose_ptr.shape == (B + 1,) and self.h_i.shape == self.h_j.shape
+        assert self.h_ptr[-1] == self.h_i.shape[0] and self.h_pose_ptr[-1] == self.h_pose.shape[0]
+        for idx, lo in ((self.h_pose, 0), (self.h_i, -1), (self.h_j, 0)):
+            if idx.size:
+                assert idx.min() >= lo and idx.max() < P, "index out of range"
 
     # everything except the parameter VALUES (poses, points): measurements, stiffness / loss / camera
     # groups, connectivity, constant masks, key order
     STRUCTURE_FIELDS = ('pose_rid', 'point_vid', 'obs_pose', 'obs_point', 'obs_uvd', 'obs_grp', 'cams', 'stiff3',
                         'obs_groups', 'e_i', 'e_j', 'e_Tobs_inv', 'e_grp', 'u_i', 'u_Tobs_inv', 'u_grp', 'stiffd',
-                        'edge_groups')
+                        'edge_groups', 'h_blocks', 'h_pose', 'h_pose_ptr', 'h_i', 'h_j', 'h_ptr')
 
     def same_tables(self, other):
         """True when `other` differs from this problem at most in the parameter values: the tables
@@ -339,8 +374,11 @@ def _load_fast_walk(rebuild=False):
 
 
 def lower(param_dict, residual_blocks, block_param_keys, block_loss_functions,
-          constant_param_keys):
-    """Build a LoweredProblem from the registries of a Problem."""
+          constant_param_keys, hybrid=False):
+    """Build a LoweredProblem from the registries of a Problem.  `hybrid` (Options.hybrid_blocks): a block without a typed
+    ``KIND`` on at most hybrid.MAX_BLOCK_POSES poses (and nothing else) goes into the ``h_*`` fields, to be evaluated on the
+    host, instead of raising NotLowerable."""
+    from pyslam_amd.hybrid import MAX_BLOCK_POSES, block_rows
     const = set(constant_param_keys)
     pose_keys, point_keys, pose_ix, point_ix = [], [], {}, {}
     dof = None
@@ -409,6 +447,7 @@ def lower(param_dict, residual_blocks, block_param_keys, block_loss_functions,
     c_pose, c_pt, c_uvd, c_g = [], [], [], []      # batch blocks, one array each (appended after the single ones)
     e_i, e_j, e_T, e_g = [], [], [], []
     u_i, u_T, u_g = [], [], []
+    h_blocks, h_pose, h_pose_ptr = [], [], [0]
     L0 = len(point_keys)
     ogrp_cache, egrp_cache = {}, {}   # keyed by object identity: O(1) per block
 
@@ -513,6 +552,16 @@ def lower(param_dict, residual_blocks, block_param_keys, block_loss_functions,
             e_j.append(pose_ix[keys[1]])
             e_T.append(Tinv)
             e_g.append(g)
+        elif kind == 'generic' and hybrid:
+            pix = [pose_ix.get(k) for k in keys]
+            if any(p is None for p in pix):
+                raise NotLowerable("block {} has no typed device kernel and a parameter that is not a pose".format(type(block).__name__))
+            if len(set(pix)) > MAX_BLOCK_POSES:
+                raise NotLowerable("block {} has no typed device kernel and more than {} poses".format(type(block).__name__,
+                                                                                                         MAX_BLOCK_POSES))
+            h_blocks.append(i)
+            h_pose.extend(pix)
+            h_pose_ptr.append(len(h_pose))
         else:
             raise NotLowerable("block {} has no typed device kernel".format(type(block).__name__))
     if len(ogrp.rows) > MAX_OBS_GROUPS:
@@ -538,4 +587,16 @@ def lower(param_dict, residual_blocks, block_param_keys, block_loss_functions,
     lp.u_i, lp.u_grp = u_i, u_g
     lp.u_Tobs_inv = np.array(u_T).reshape(-1, pw)
     lp.stiffd, lp.edge_groups = std.table(dof * dof), egrp.table(3)
+    if h_blocks:
+        h_i, h_j, h_ptr = [], [], [0]
+        for b in range(len(h_blocks)):
+            var = []
+            for p in h_pose[h_pose_ptr[b]:h_pose_ptr[b + 1]]:
+                if rid[p] >= 0 and p not in var:
+                    var.append(p)
+            for a, c in (block_rows(var) if var else []):
+                h_i.append(a)
+                h_j.append(c)
+            h_ptr.append(len(h_i))
+        lp.h_blocks, lp.h_pose, lp.h_pose_ptr, lp.h_i, lp.h_j, lp.h_ptr = h_blocks, h_pose, h_pose_ptr, h_i, h_j, h_ptr
     return lp.finalize()

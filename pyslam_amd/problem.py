@@ -12,7 +12,9 @@ attributes the reference's tests read).  What differs is where the work runs:
   elimination, block-PCG, back-substitution, retraction, post-step cost -- runs
   on the MI355X (include/pyslam_hip.h: ps_gn_iteration); the host sees two
   scalars per iteration and runs the reference's termination logic on them;
-* problems with user-defined blocks / parameters are evaluated through the
+* with Options.hybrid_blocks, user-defined blocks on poses are evaluated on the host beside the typed tables and their
+  pose-pair blocks of J^T J join the device's reduced system (pyslam_amd/hybrid.py);
+* other problems with user-defined blocks / parameters are evaluated through the
   block protocol on the host (that is user Python code) and only the normal
   equations are formed and solved on the device (ps_dense_normal_solve; beyond 2048
   unknowns J goes up as CSR and the device runs CG on J^T J: ps_sparse_normal_solve).
@@ -66,6 +68,13 @@ class Options:
         # whole loop -- iterations, stopping rules, best-parameter bookkeeping -- in one device launch.  False: one call
         # per iteration, as every other problem shape.  Same decisions, same cost history either way.
         self.fused_solve_loop = True
+        # True: a block without a typed device kernel (no KIND) whose parameters are all poses of the problem's group, at most 8
+        # of them, no longer moves the whole problem to the host-evaluated generic path.  Those blocks alone are evaluated on the
+        # host (their evaluate(), once with Jacobians per linearisation and once more for the cost after a step); their
+        # pose-pair blocks of J~^T J~ join the typed blocks' reduced system on the device (pyslam_amd/hybrid.py).  Not for:
+        # blocks on a landmark or a non-pose parameter, photometric problems, the sharded route, mixed SE(2)/SE(3) problems --
+        # those take the generic path as with False.  False (default): every problem routes as before, bit for bit.
+        self.hybrid_blocks = False
 
 
 def solve_horizon(opt, iteration, nondecreasing_steps_taken):
@@ -120,7 +129,8 @@ def _device_solve_loop(dev, opt, use_core_loop, call_ms):
     if hasattr(dev, 'reset_solver_state'):
         dev.reset_solver_state()          # a solve is a function of (parameters, options), not of the handle's history
     horizon = getattr(dev, 'set_solve_horizon', None)
-    expect = getattr(dev, 'set_expect_next', None)
+    # (a hybrid handle's own costs miss the host blocks: the core decides nothing from them -- ps_problem_create_hybrid)
+    expect = getattr(dev, 'set_expect_next', None) if getattr(dev, 'host', None) is None else None
     linesearch = opt.linesearch_max_iters > 0
     lam = getattr(opt, 'lm_lambda', 0.)
     pcg_tol, pcg_max = (getattr(opt, 'pcg_tol', None) or 0.), getattr(opt, 'pcg_max_iters', 2000)      # (0: the core's default)
@@ -251,8 +261,17 @@ class Problem:
     # ------------------------------------------------------------------
     def _lower(self, param_dict=None):
         pd = self.param_dict if param_dict is None else param_dict
+        hybrid = getattr(self.options, 'hybrid_blocks', False) and self._route() == 'single'
         return lowering.lower(pd, self.residual_blocks, self.block_param_keys,
-                              self.block_loss_functions, self.constant_param_keys)
+                              self.block_loss_functions, self.constant_param_keys, hybrid=hybrid)
+
+    def _attach_host(self, dev):
+        """A hybrid handle gets the Problem's user blocks (evaluated on the host at the device's current poses)."""
+        if dev.lp.hybrid:
+            from pyslam_amd.hybrid import HostBlocks
+            dev.attach_host(HostBlocks(dev.lp, self.residual_blocks, self.block_param_keys, self.block_loss_functions,
+                                       self.param_dict))
+        return dev
 
     def _photometric_form(self):
         """'se3' / 'split' when the problem is ONE PhotometricResidualSE3 block on variable parameters (the dense VO
@@ -295,6 +314,8 @@ class Problem:
             poses, points = lowering.refresh_params(pd, dev.lp)
             dev.set_params(poses, points)
             dev.lp.poses, dev.lp.points = poses, points
+            if dev.lp.hybrid and dev.host is None:
+                self._attach_host(dev)
             return dev
         lp = self._lower(param_dict)
         # The resident tables are reused only if EVERYTHING but the parameter values is unchanged: measurements,
@@ -311,6 +332,7 @@ class Problem:
             self._device = self._make_device(lp)
             self._device_sig = 'tables'
             self._device_route = self._route()
+        self._attach_host(self._device)
         self._static_sig = self._cheap_sig()
         return self._device
 

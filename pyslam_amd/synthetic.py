@@ -411,3 +411,72 @@ def rgbd_sequence(h=96, w=128, n_frames=8, seed=0, step=(0.02, -0.01, 0.04, 0.01
         depth[f] = d
         T_c_w[f] = T.as_matrix()
     return dict(images=images, depth=depth, cam=(cu, cv, fu, fv, w, h), T_c_w=T_c_w)
+
+
+# ---------------------------------------------------------------------------
+# user-defined residual blocks (no KIND: no typed device kernel), as a user of Problem writes them -- the blocks
+# Options.hybrid_blocks evaluates on the host beside the typed tables (tools/gen_hybrid_golden.py, tests)
+# ---------------------------------------------------------------------------
+class TranslationPrior:
+    """r = S (t - t_obs) on one SE(3) / SE(2) pose (a GPS / position prior).  Jacobian in the pose's perturbation
+    (T <- exp(xi) T, xi = [rho | phi]): d t = rho + phi x t, i.e. S [I | -t^] (SE2: S [I | (-t_y, t_x)])."""
+
+    def __init__(self, t_obs, stiffness):
+        self.t_obs = np.asarray(t_obs, dtype=float)
+        self.stiffness = np.asarray(stiffness, dtype=float)
+
+    def evaluate(self, params, compute_jacobians=None):
+        T = params[0]
+        residual = self.stiffness.dot(T.trans - self.t_obs)
+        if not compute_jacobians:
+            return residual
+        jacobians = [None]
+        if compute_jacobians[0]:
+            jacobians[0] = self.stiffness.dot(type(T).odot(T.trans).reshape(T.trans.size, -1))
+        return residual, jacobians
+
+
+class TranslationSmoothness:
+    """r = S (t_0 - 2 t_1 + t_2) on three poses (a constant-velocity smoothness factor)."""
+
+    def __init__(self, stiffness):
+        self.stiffness = np.asarray(stiffness, dtype=float)
+
+    def evaluate(self, params, compute_jacobians=None):
+        T0, T1, T2 = params
+        residual = self.stiffness.dot(T0.trans - 2. * T1.trans + T2.trans)
+        if not compute_jacobians:
+            return residual
+        jacobians = [None, None, None]
+        for k, (T, c) in enumerate(zip(params, (1., -2., 1.))):
+            if compute_jacobians[k]:
+                jacobians[k] = c * self.stiffness.dot(type(T).odot(T.trans).reshape(T.trans.size, -1))
+        return residual, jacobians
+
+
+class Untyped:
+    """Delegates evaluate() to a typed block but carries no KIND: the same residual as a user-defined block."""
+
+    def __init__(self, inner):
+        self.inner = inner
+
+    def evaluate(self, params, compute_jacobians=None):
+        return self.inner.evaluate(params, compute_jacobians)
+
+
+def add_user_blocks(problem, lp, ns, kinds, poses, t_obs, stiffness, loss_rows):
+    """Add the user blocks of a table spec to `problem` (built by to_objects from `lp`): per block its kind (0:
+    TranslationPrior on poses[b, 0], 1: TranslationSmoothness on poses[b, :3]), t_obs (first 3 | 2 entries), the n x n
+    stiffness (row-major) and the loss row (loss id, k).  -> the blocks, in order."""
+    keys = lp.pose_keys or ['T{}'.format(i) for i in range(lp.num_poses)]
+    n = 3 if lp.dof == 6 else 2
+    out = []
+    for kind, p, t, S, lr in zip(kinds, poses, t_obs, stiffness, loss_rows):
+        S = np.asarray(S, dtype=float)[:n * n].reshape(n, n)
+        if int(kind) == 0:
+            block, bkeys = TranslationPrior(np.asarray(t, dtype=float)[:n], S), [keys[int(p[0])]]
+        else:
+            block, bkeys = TranslationSmoothness(S), [keys[int(q)] for q in p[:3]]
+        problem.add_residual_block(block, bkeys, make_loss(ns, lr[0], lr[1]))
+        out.append(block)
+    return out
