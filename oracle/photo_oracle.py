@@ -54,6 +54,21 @@ def bilinear(im, x, y):
     return out
 
 
+def bilinear_vec(im, x, y):
+    """bilinear() over whole arrays, with the same operations in the same order: truncated corners, weights from the
+    unclipped corners, corners clamped afterwards, the four products summed left to right.  Equal to the loop bit for bit
+    (tests/test_photo_oracle_host.py); fast enough for several 640 x 480 solves in one test run."""
+    h, w = im.shape
+    x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+    x0, y0 = np.trunc(x).astype(np.int64), np.trunc(y).astype(np.int64)      # int(): truncation toward zero
+    x1, y1 = x0 + 1, y0 + 1
+    wa, wb = (x1 - x) * (y1 - y), (x1 - x) * (y - y0)
+    wc, wd = (x - x0) * (y1 - y), (x - x0) * (y - y0)
+    x0, x1 = np.clip(x0, 0, w - 1), np.clip(x1, 0, w - 1)
+    y0, y1 = np.clip(y0, 0, h - 1), np.clip(y1, 0, h - 1)
+    return wa * im[y0, x0] + wb * im[y1, x0] + wc * im[y0, x1] + wd * im[y1, x1]
+
+
 def evaluate(tb, im_track, var_i, var_d, R, t):
     """evaluate() (:83-143): residual (valid pixels only), its N x 6 Jacobian ([translation | rotation]), valid mask."""
     cu, cv, fu, fv, b = tb['cam']
@@ -70,7 +85,7 @@ def evaluate(tb, im_track, var_i, var_d, R, t):
     g = np.stack([gu * fu * iz, gv * fv * iz, -(gu * fu * p[:, 0] + gv * fv * p[:, 1]) * iz * iz], axis=1)   # :110-111
     jd = np.sum((g @ R) * tb['tri_jac_d'][valid], axis=1)                                                  # :112-116
     s = 1. / np.sqrt(var_i + var_d * jd ** 2)                                                              # :120-121
-    r = s * (bilinear(np.asarray(im_track, dtype=float), u, v) - tb['im_ref'][valid])
+    r = s * (bilinear_vec(np.asarray(im_track, dtype=float), u, v) - tb['im_ref'][valid])
     J = np.empty((r.size, 6))
     J[:, :3] = g
     J[:, 3:] = np.cross(p, g)                                   # g (-p^) = p x g                          # :133-137
@@ -93,3 +108,138 @@ def gn_step(tb, im_track, var_i, var_d, R, t, loss_id=0, loss_k=1., split=False)
         return dx, orc.so3_exp(dx[None, 3:])[0] @ R, t + dx[:3], cost
     Re, te = orc.se_exp(dx, 6)                                  # T <- exp(dx) T (liegroups perturb)
     return dx, Re[0] @ R, Re[0] @ t + te[0], cost
+
+
+def normal_equations_ld(tb, im_track, var_i, var_d, R, t, loss_id=0, loss_k=1.):
+    """normal_equations() accumulated in np.longdouble from the float64 per-pixel rows (r, J, w, rho of evaluate()), so the
+    sums carry no float64 rounding of their own.  Also returns the element-wise magnitude sums that a tolerance is set from:
+    abs_H = sum |w J_i J_j|, abs_b = sum |w J_i r|, abs_cost = sum |rho|, and min |r| (the L1 weight 1 / |r| is NaN at
+    |r| <= 1e-8)."""
+    r, J, valid = evaluate(tb, im_track, var_i, var_d, R, t)
+    w = orc.loss_weight(loss_id, loss_k, r)
+    rho = orc.loss_rho(loss_id, loss_k, r)
+    L = np.longdouble
+    Jl, rl = J.astype(L), r.astype(L)
+    WJ = Jl * w.astype(L)[:, None]
+    return dict(H=WJ.T @ Jl, b=-(WJ.T @ rl), cost=np.sum(rho.astype(L)), n=int(valid.sum()),
+                abs_H=np.abs(WJ).T @ np.abs(Jl), abs_b=np.abs(WJ).T @ np.abs(rl), abs_cost=np.sum(np.abs(rho.astype(L))),
+                min_abs_r=float(np.abs(r).min()) if r.size else np.inf)
+
+
+def chol_solve_ld(H, b):
+    """H x = b by a Cholesky factorisation in np.longdouble; None when H is not positive definite (a pivot that is not > 0,
+    NaN included)."""
+    n = len(b)
+    L = np.zeros((n, n), dtype=np.longdouble)
+    for j in range(n):
+        d = H[j, j] - np.sum(L[j, :j] * L[j, :j])
+        if not d > 0:
+            return None
+        L[j, j] = np.sqrt(d)
+        for i in range(j + 1, n):
+            L[i, j] = (H[i, j] - np.sum(L[i, :j] * L[j, :j])) / L[j, j]
+    y = np.zeros(n, dtype=np.longdouble)
+    for i in range(n):
+        y[i] = (b[i] - np.sum(L[i, :i] * y[:i])) / L[i, i]
+    x = np.zeros(n, dtype=np.longdouble)
+    for i in range(n - 1, -1, -1):
+        x[i] = (y[i] - np.sum(L[i + 1:, i] * x[i + 1:])) / L[i, i]
+    return x
+
+
+class DenseSolveError(RuntimeError):
+    """The two failure exits of a level solve: fewer than 6 valid pixels, or H not positive definite."""
+
+
+def dense_level_solve(tb, im_track, var_i, var_d, opt, loss_id, loss_k, rot_only, R, t):
+    """One level of the dense pipeline's coarse-to-fine solve on the host: Problem.solve's loop (pyslam_amd/problem.py:
+    _reference_loop) over the (R_1_0, t_1_0_1) parameters with longdouble normal equations.  rot_only: H[3:, 3:] dphi =
+    b[3:], R <- exp(dphi) R, t unchanged; else dx = H^-1 b, R <- exp(dx[3:]) R, t += dx[:3].  Without a line search
+    (opt.linesearch_max_iters == 0) an iteration reports the cost of its linearisation point, with one the cost after
+    the step.  Raises DenseSolveError where the device reports a failure.
+
+    -> dict(R, t, iters, hist (float64 costs), steps (dx per iteration), margins, restores (best-pose restores)): margins lists, for every stopping
+    decision that compares a float with a threshold, its relative distance from the threshold -- cost / prev_cost against
+    min_cost_decrease, |dx| against min_update_norm, cost against min_cost -- so a caller can show that no decision is a
+    tie that a rounding difference could flip."""
+    R, t = np.array(R, dtype=float), np.array(t, dtype=float)
+    linesearch = opt.linesearch_max_iters > 0
+
+    def ne(R, t):
+        return normal_equations_ld(tb, im_track, var_i, var_d, R, t, loss_id, loss_k)
+
+    cost = float(ne(R, t)['cost'])
+    hist, steps, margins = [cost], [], []
+    iters, nd, done, best, restores = 0, 0, False, None, 0
+    while not done:
+        iters += 1
+        prev = cost
+        q = ne(R, t)
+        if q['n'] < 6:
+            raise DenseSolveError('fewer than 6 valid pixels')
+        o = 3 if rot_only else 0
+        x = chol_solve_ld(q['H'][o:, o:], q['b'][o:])
+        if x is None:
+            raise DenseSolveError('not positive definite')
+        dx = x.astype(float)
+        steps.append(dx)
+        dx_norm = float(np.sqrt(np.sum(x * x)))
+        if rot_only:
+            R = orc.so3_exp(dx[None])[0] @ R
+        else:
+            R, t = orc.so3_exp(dx[None, 3:])[0] @ R, t + dx[:3]
+        cost = float(ne(R, t)['cost']) if linesearch else float(q['cost'])
+        hist.append(cost)
+        margins.append(abs(cost / prev - opt.min_cost_decrease) / opt.min_cost_decrease)
+        if opt.min_update_norm > 0:
+            margins.append(abs(dx_norm - opt.min_update_norm) / opt.min_update_norm)
+        if opt.min_cost > 0:
+            margins.append(abs(cost - opt.min_cost) / opt.min_cost)
+        done = iters > opt.max_iters or dx_norm < opt.min_update_norm or cost < opt.min_cost
+        if opt.allow_nondecreasing_steps:
+            if nd == 0:
+                best = (R.copy(), t.copy())
+            nd = nd + 1 if cost >= opt.min_cost_decrease * prev else 0
+            if nd >= opt.max_nondecreasing_steps:
+                done = True
+                R, t = best[0].copy(), best[1].copy()
+                restores += 1
+        else:
+            done = done or cost >= opt.min_cost_decrease * prev
+    return dict(R=R, t=t, iters=iters, hist=np.array(hist), steps=steps, margins=margins, restores=restores)
+
+
+def dense_solve(levels, opt, loss_id, loss_k, R, t):
+    """The coarse-to-fine sequence: `levels` is a list of dict(tb, im_track, var_i, var_d, rot_only), solved in order, each
+    from the pose the previous one left.  -> dict(R, t, iters [per level], hists [per level], margins and restores [all levels])."""
+    its, hists, margins, restores = [], [], [], 0
+    for lv in levels:
+        out = dense_level_solve(lv['tb'], lv['im_track'], lv['var_i'], lv['var_d'], opt, loss_id, loss_k, lv['rot_only'], R, t)
+        R, t = out['R'], out['t']
+        its.append(out['iters']); hists.append(out['hist']); margins += out['margins']; restores += out['restores']
+    return dict(R=R, t=t, iters=its, hists=hists, margins=margins, restores=restores)
+
+
+def dense_levels(im_ref, depth_ref, im_track, cam, levels, rot_only, var_i, var_d, min_grad):
+    """Host inputs of dense_solve() for a frame pair, as the pipeline builds them: image pyramids by pyr_down on the raw
+    (uint8 or float64) image, level images raw / 255, gradients 0.5 * Sobel, depth depth[::2^l, ::2^l], level cameras
+    scaled by 2^-l with ceil'd sizes (pipelines/dense.py: _make_pyramid_cameras), tables(..., rgbd=True).
+    cam = (cu, cv, fu, fv, w, h).  The two OpenCV operations come from pyslam_amd/pipelines/imgproc.py, the restatement
+    the device pyramid is checked against bit for bit."""
+    from pyslam_amd.pipelines import imgproc
+    top = max(levels) + 1
+    pyr_r, pyr_t = [np.asarray(im_ref)], [np.asarray(im_track)]
+    for _ in range(1, top):
+        pyr_r.append(imgproc.pyr_down(pyr_r[-1]))
+        pyr_t.append(imgproc.pyr_down(pyr_t[-1]))
+    out = []
+    for l, ro in zip(levels, rot_only):
+        s = 2. ** -l
+        cu, cv, fu, fv, w, h = cam
+        cl = (cu * s, cv * s, fu * s, fv * s, 0., int(np.ceil(w * s)), int(np.ceil(h * s)))
+        ref = pyr_r[l].astype(float) / 255.
+        jac = np.array([0.5 * imgproc.sobel(ref, 1, 0), 0.5 * imgproc.sobel(ref, 0, 1)])
+        tb = tables(cl, ref, np.asarray(depth_ref, dtype=float)[::2 ** l, ::2 ** l], jac, min_grad, True)
+        out.append(dict(tb=tb, im_track=pyr_t[l].astype(float) / 255., var_i=var_i, var_d=var_d, rot_only=bool(ro), level=l,
+                        cam=cl, im_ref=ref, jac=jac))
+    return out
