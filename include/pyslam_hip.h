@@ -329,6 +329,23 @@ int ps_covariance_begin(ps_problem* h);
 int ps_covariance_column(ps_problem* h, int kind, int index, int comp, double tol, int max_iters,
                          int* iters_out, double* relres_out);
 
+/* Batched marginal covariances (Problem.compute_marginal_covariances), after ps_covariance_begin:
+   ps_covariance_marginals densifies the reduced system S it left behind (nr * dof unknowns, at most
+   PS_COV_DENSE_MAX_UNKNOWNS: 1.2 GB per n x n buffer there, three of them), factors it and forms
+   Sigma_pp = S^-1 in fp64 on the device.  pose_blocks (nr, dof, dof): the diagonal blocks of every reduced
+   pose, in reduced order (rid); point_blocks (nv, 3, 3): every variable landmark's marginal
+   M^T (I + sum_ij Z_i^T Sigma_pp[r_i, r_j] Z_j) M, in vid order.  Either may be NULL.  Every block is exactly
+   symmetric and bit-identical from call to call.  Errors: above the limit (the column route has none), a
+   non-positive or rounding-size pivot (gauge freedom: hold a pose constant or add a prior; nothing is
+   written).  Sigma_pp stays on the handle until the next linearisation, ps_covariance_begin or
+   ps_problem_destroy; it is not allocated unless this call is made.
+   ps_covariance_pose_blocks reads out[k] = Sigma_pp[a_k, b_k] (dof x dof, reduced indices) from it. */
+#define PS_COV_DENSE_MAX_UNKNOWNS 12288
+int ps_covariance_marginals(ps_problem* h, double* pose_blocks /* (nr, D, D) or NULL */,
+                            double* point_blocks /* (nv, 3, 3) or NULL */);
+int ps_covariance_pose_blocks(ps_problem* h, int64_t n, const int32_t* a, const int32_t* b,
+                              double* out /* (n, D, D) */);
+
 /* Parity / debug taps (device -> host). */
 int ps_get_reduced_system(ps_problem* h, int32_t* row_ptr, int32_t* col_idx,
                           double* vals, double* g);       /* BSR, dof x dof blocks */

@@ -109,6 +109,7 @@ int ps_problem_destroy(ps_problem* h) {
     h->persist_release();
     if (h->side) hipStreamSynchronize(h->side);
     if (h->ldi_stream) hipStreamSynchronize(h->ldi_stream);
+    cov_release(h);
     for (void* p : h->allocs) hipFree(p);
     h->arena_release();            // arena block, its pinned mirror and the pinned result words go back to the process-wide pool
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);

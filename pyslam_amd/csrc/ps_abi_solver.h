@@ -658,6 +658,8 @@ int ps_motion_only_solve(ps_problem* h, const ps_solve_options* o, double* cost_
 
 int ps_covariance_begin(ps_problem* h) {
     if (!h) return fail("null argument");
+    cov_release(h);
+    ++h->cov_epoch;
     h->prelin_valid = h->prelm_valid = false;
     if (linearize(h, 0.0)) return -1;
     if (h->nr > 0 && h->pcg_variant == 1 && !use_direct(h) && !h->coarse_built && build_coarse(h)) return -1;

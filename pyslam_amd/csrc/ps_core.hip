@@ -27,6 +27,7 @@
 #include "ps_photo.h"
 #include "ps_k_dense.h"
 #include "ps_sparse.h"
+#include "ps_k_covmarg.h"
 
 namespace {
 
@@ -397,6 +398,10 @@ struct ps_problem {
     long cg_kernel_launches = 0;    // kernels enqueued for CG / PCG iterations since creation (ps_problem_info)
     bool cov_ready = false;         // ps_covariance_begin has linearised and set the reduced solver up; cleared by linearize()
     std::vector<int32_t> h_slot_of_vid;
+    // batched marginals (ps_abi_cov.h): one device block [S -> Sigma (n^2) | L^-1 (n^2) | L^-T (n^2) | ...], allocated by the first
+    // ps_covariance_marginals, freed by the next linearisation, ps_covariance_begin or destroy; Sigma is valid for cov_epoch only
+    double* cov_buf = nullptr;
+    long long cov_epoch = 0, cov_sigma_epoch = -1;
     int ell_wf = 0, ell_wc = 0;     // two-class ELL widths of the CG matrix (0 = CSR)
     // scalars
     double *cost_partials = nullptr, *scalars = nullptr, *h_scalars = nullptr;
@@ -631,6 +636,16 @@ struct ps_problem {
     }
 };
 
+// the batched marginals' dense block (ps_abi_cov.h) goes when its reduced system does: at the next linearisation, the next
+// ps_covariance_begin, destroy
+inline void cov_release(ps_problem* h) {
+    if (!h->cov_buf) return;
+    hipStreamSynchronize(h->stream);
+    hipFree(h->cov_buf);
+    h->cov_buf = nullptr;
+    h->cov_sigma_epoch = -1;
+}
+
 #include "ps_host_cg.h"
 #include "ps_host_ldi.h"
 #include "ps_host_iteration.h"
@@ -643,6 +658,7 @@ extern "C" {
 
 #include "ps_abi_problem.h"
 #include "ps_abi_solver.h"
+#include "ps_abi_cov.h"
 #include "ps_abi_small.h"
 #include "ps_abi_dense.h"
 

@@ -1031,6 +1031,7 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
     h->params_moved_since_lin = false; h->z_foreign = false; // (Z, C^-1, c of THIS point: run below, or taken over from the pass run ahead here)
     ++h->prof_tick;
     h->cov_ready = false;
+    cov_release(h);
     h->status_clean = false;
     if (h->ldi_sread_pending) {         // the side stream's inverse update still converts the previous S (ps_host_ldi.h)
         HIP_OK(hipStreamWaitEvent(h->stream, h->ev_ldi_sread, 0));

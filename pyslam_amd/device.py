@@ -11,6 +11,10 @@ import numpy as np
 from pyslam_amd import _native as nat
 
 
+# reduced unknowns (nr * dof) up to which covariance_marginals forms S^-1 densely (include/pyslam_hip.h: PS_COV_DENSE_MAX_UNKNOWNS)
+COVARIANCE_MARGINALS_LIMIT = 12288
+
+
 class DeviceProblem:
     def __init__(self, lp, stream=None, extra_pairs=None):
         lib = nat.require_gpu()
@@ -286,6 +290,26 @@ class DeviceProblem:
         nat.check(self._lib.ps_covariance_column(self._h, int(kind), int(index), int(comp), tol, max_iters,
                                                  C.byref(it), C.byref(rel)))
         return self.get_dx()
+
+    # ---- batched marginals (ps_covariance_marginals) ---------------------
+    def covariance_marginals(self):
+        """Marginal covariances after covariance_begin(): (pose (nr, dof, dof), point (nv, 3, 3)) in device order (reduced pose
+        rid, variable landmark vid).  The dense Sigma_pp = S^-1 they come from stays on the handle for covariance_pose_blocks.
+        Reduced systems above COVARIANCE_MARGINALS_LIMIT unknowns raise (the column route has no limit)."""
+        pose = np.zeros((self.nr, self.dof, self.dof))
+        point = np.zeros((self.nv, 3, 3))
+        nat.check(self._lib.ps_covariance_marginals(self._h, nat.f64p(pose), nat.f64p(point)))
+        return pose, point
+
+    def covariance_pose_blocks(self, a, b):
+        """Sigma_pp[a_k, b_k] (len(a), dof, dof) for reduced pose indices a, b, from the inverse covariance_marginals() left."""
+        a = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray(b, dtype=np.int32).reshape(-1)
+        if a.shape != b.shape:
+            raise ValueError('covariance_pose_blocks: a and b differ in length')
+        out = np.zeros((a.shape[0], self.dof, self.dof))
+        nat.check(self._lib.ps_covariance_pose_blocks(self._h, a.shape[0], nat.i32p(a), nat.i32p(b), nat.f64p(out)))
+        return out
 
     # ---- data movement -------------------------------------------------
     def get_dx(self):

@@ -646,6 +646,12 @@ class ShardedProblemView:
     def covariance_column(self, kind, index, comp, tol=1e-13, max_iters=4000):
         return self._replica.covariance_column(kind, index, comp, tol, max_iters)
 
+    def covariance_marginals(self):
+        return self._replica.covariance_marginals()
+
+    def covariance_pose_blocks(self, a, b):
+        return self._replica.covariance_pose_blocks(a, b)
+
     def close(self):
         self.sharded.close()
         if self._replica is not None:

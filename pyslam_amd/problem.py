@@ -726,6 +726,82 @@ class Problem:
         return None
 
     # ------------------------------------------------------------------
+    # batched marginal covariances (no reference counterpart: the reference inverts the whole precision matrix)
+    # ------------------------------------------------------------------
+    def compute_marginal_covariances(self, keys=None, pose_pairs=()):
+        """Marginal covariance blocks at the current parameters (linearised here, lambda = 0, as compute_covariance does).
+
+        -> dict: every key of `keys` (None: every non-constant parameter) -> its (dof, dof) block, 3 x 3 for a landmark; every
+        (key_a, key_b) of `pose_pairs` -> the cross block Sigma_ab (dof_a, dof_b).  A constant or unknown key raises KeyError.
+
+        Typed problems (hybrid ones included): one device call forms S^-1 of the reduced system densely in fp64 (up to
+        pyslam_amd.device.COVARIANCE_MARGINALS_LIMIT reduced unknowns, else it raises) and every landmark's block from it;
+        pose_pairs must then name poses.  The photometric form slices the inverse of its 6 x 6 system, the host-evaluated
+        generic route the dense covariance of dense_normal_solve (beyond DENSE_GENERIC_LIMIT: CG columns, as
+        get_covariance_block).  compute_covariance's state is neither read nor written."""
+        part = self._get_update_partition_dict()
+        want = list(part) if keys is None else list(keys)
+        pairs = _check_pose_pairs(pose_pairs)
+        for k in want + [k for pr in pairs for k in pr]:
+            _check_cov_key(k, part, self.constant_param_keys)
+        try:
+            dev = self._get_device()
+        except NotLowerable:
+            dev = None
+        if dev is None:
+            return self._marginals_generic(part, want, pairs)
+        if self._photometric_form():
+            cov = self._photometric_covariance(dev, part)
+            return _slice_dense_blocks(cov, part, want, pairs)
+        dev.covariance_begin()
+        pose, point = dev.covariance_marginals()
+        out = marginal_blocks_by_key(dev.lp, pose, point, want)
+        if pairs:
+            a, b = pose_pair_indices(dev.lp, pairs)
+            for pr, blk in zip(pairs, dev.covariance_pose_blocks(a, b)):
+                out[pr] = blk
+        return out
+
+    def _photometric_covariance(self, dev, part):
+        """The photometric form's 6 x 6 inverse in the reference's unknown order (as compute_covariance forms it)."""
+        Hm = dev.normal_equations()[0]
+        keys = self.block_param_keys[0]
+        order = np.empty(6, dtype=int)
+        if len(keys) == 1:
+            order[part[keys[0]]] = np.arange(6)
+        else:
+            order[part[keys[0]]] = np.arange(3, 6)
+            order[part[keys[1]]] = np.arange(0, 3)
+        return np.linalg.inv(Hm[np.ix_(order, order)])
+
+    def _marginals_generic(self, part, want, pairs):
+        from pyslam_amd.device import dense_normal_solve, sparse_normal_solve
+        J, e, _ = self._host_jacobian()
+        if J.shape[1] <= self.DENSE_GENERIC_LIMIT:
+            _, cov = dense_normal_solve(J.toarray(), e, want_covariance=True)
+            return _slice_dense_blocks(cov, part, want, pairs)
+        cols = {}
+
+        def columns(key):            # (n, dof_key): one CG solve per unit right-hand side, as get_covariance_block
+            if key not in cols:
+                r = part[key]
+                c = np.zeros((J.shape[1], r.stop - r.start))
+                for q, k in enumerate(r):
+                    rhs = np.zeros(J.shape[1]); rhs[k] = 1.
+                    c[:, q], _, _ = sparse_normal_solve(J, rhs=rhs, tol=1e-13, max_iters=20 * J.shape[1], accept=1e-8)
+                cols[key] = c
+            return cols[key]
+        out = {}
+        for k in want:
+            r = part[k]
+            blk = columns(k)[r.start:r.stop]
+            out[k] = 0.5 * (blk + blk.T)
+        for ka, kb in pairs:
+            ra = part[ka]
+            out[(ka, kb)] = columns(kb)[ra.start:ra.stop].copy()
+        return out
+
+    # ------------------------------------------------------------------
     # reporting (reference problem.py:218-250; text format kept byte-identical)
     # ------------------------------------------------------------------
     def summary(self, format='brief'):
@@ -780,3 +856,66 @@ class Problem:
             pd[key].perturb(dx)
         except AttributeError:
             pd[key] += dx
+
+
+# ---------------------------------------------------------------------------
+# batched marginals: device order -> parameter keys (pure numpy; Problem.compute_marginal_covariances)
+# ---------------------------------------------------------------------------
+def _check_cov_key(key, part, constant_keys):
+    if key in part:
+        return
+    if key in constant_keys:
+        raise KeyError('{!r} is a constant parameter: it has no covariance'.format(key))
+    raise KeyError('{!r} is not a parameter of this problem'.format(key))
+
+
+def _check_pose_pairs(pose_pairs):
+    pairs = []
+    for pr in pose_pairs:
+        if isinstance(pr, (str, bytes)) or not hasattr(pr, '__len__') or len(pr) != 2:
+            raise ValueError('pose_pairs: every entry must be a (key_a, key_b) pair, got {!r}'.format(pr))
+        pairs.append((pr[0], pr[1]))
+    return pairs
+
+
+def marginal_blocks_by_key(lp, pose, point, keys):
+    """{key: block} for `keys` from device-order marginals: pose (nr, dof, dof) indexed by lp.pose_rid, point (nv, 3, 3) by
+    lp.point_vid.  A key that is a constant pose / fixed landmark of `lp`, or not in it, raises KeyError."""
+    where = {}
+    for k, rid in zip(lp.pose_keys, lp.pose_rid):
+        where[k] = (0, int(rid))
+    for k, vid in zip(lp.point_keys, lp.point_vid):
+        where[k] = (1, int(vid))
+    out = {}
+    for k in keys:
+        if k not in where:
+            raise KeyError('{!r} is not a parameter of this problem'.format(k))
+        kind, ix = where[k]
+        if ix < 0:
+            raise KeyError('{!r} is a constant parameter: it has no covariance'.format(k))
+        out[k] = (pose if kind == 0 else point)[ix]
+    return out
+
+
+def pose_pair_indices(lp, pairs):
+    """Reduced pose indices (a, b) (int32) of the (key_a, key_b) pairs; ValueError for a key that is not a variable pose."""
+    rid = {k: int(r) for k, r in zip(lp.pose_keys, lp.pose_rid)}
+    a, b = [], []
+    for ka, kb in pairs:
+        for k in (ka, kb):
+            if rid.get(k, -1) < 0:
+                raise ValueError('pose_pairs: {!r} is not a variable pose (cross blocks exist between poses only)'.format(k))
+        a.append(rid[ka]); b.append(rid[kb])
+    return np.array(a, dtype=np.int32), np.array(b, dtype=np.int32)
+
+
+def _slice_dense_blocks(cov, part, keys, pairs):
+    """Blocks of a dense covariance in the reference's unknown order (partition `part`)."""
+    out = {}
+    for k in keys:
+        r = part[k]
+        out[k] = cov[r.start:r.stop, r.start:r.stop].copy()
+    for ka, kb in pairs:
+        ra, rb = part[ka], part[kb]
+        out[(ka, kb)] = cov[ra.start:ra.stop, rb.start:rb.stop].copy()
+    return out
