@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """bench.py -- ms per Gauss-Newton/LM iteration on the BASELINE stereo-BA workloads.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what its headline figure needs and nothing more: it sets the problem up, runs the
+warm-up and the K timed steps, writes ``--dump-outputs`` if asked, and prints the line.  Everything
+else the line has carried -- the stage breakdown and roofline objects, the launch count of the reduced
+solve, the same-point figures of earlier rounds, the single-GPU C4 leg, the per-frame and
+``Problem.solve()`` wall clocks, the CPU baseline -- takes runs of its own after the timed region and
+comes with ``--full`` (``--no-cpu-baseline``, ``--no-c4``, ``--no-wall`` leave legs of it out).
 
 One "step" = one full iteration of the hot path: residuals + Jacobians + IRLS
 weights, J^T J assembly, Schur elimination of the landmarks, block-PCG on the
@@ -21,13 +28,13 @@ history) and the start parameters are uploaded again -- both outside the clock; 
 a solve itself does (start cost, iterations, best-parameter snapshots, the final restore)
 is inside.  value = sum of solve times / sum of iterations, over exactly K iterations (the
 last solve is cut at the K-th).  The W warm-up steps are whole untimed solves (at least one).
-Extra keys keep the figures of earlier rounds: ``steady_same_point_ms`` (every step restores
+With --full, extra keys keep the figures of earlier rounds: ``steady_same_point_ms`` (every step restores
 the same linearisation point; with the lagged inverse that is the settled phase no
 reference-terminated solve reaches), ``moving_same_point_ms`` (the same with the inverse off).
 
 N = 1: workload C3 of SURVEY.md section 8d (200 keyframes, 50 000 landmarks,
 500 000 reprojection blocks = 1.5 M residual rows), the configuration
-BASELINE.json's metric is quoted on; ``c4_single_gpu`` carries the same cold-solve
+BASELINE.json's metric is quoted on; with --full, ``c4_single_gpu`` carries the same cold-solve
 measurement of the north star's 2 000-keyframe / 500 000-landmark problem on this one
 GPU (the strong-scaling base), ``cold_solve_wall_ms`` the wall clock of ``Problem.solve()``
 through the public API (objects -> lowering -> ps_problem_create -> iterations).
@@ -39,8 +46,8 @@ shard ``rank`` of N (``shard_landmarks``); the reduced pose system [upper(S) | g
 is exchanged once per iteration by the HIP core itself on the solver's stream -- N > 1: an RCCL
 all-gather of the ranks' band segments, summed by every rank in rank order (``--exchange allreduce``:
 one sum all-reduce of the whole packed system) -- and then solved redundantly on every rank; a
-second small all-reduce sums the shards' cost and landmark step norm.  Rank 0 also times the
-unsharded C4 problem on its own GPU after the timed region (``c4_single_gpu_ms``).
+second small all-reduce sums the shards' cost and landmark step norm.  With --full, rank 0 also times
+the unsharded C4 problem on its own GPU after the timed region (``c4_single_gpu_ms``).
 
 Prints ONE JSON line (rank 0).
 
@@ -551,16 +558,18 @@ def cold_solve_wall(cfg, reps=2):
                     'not part of solve()'}
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--kf', type=int, default=None, help='override the keyframe count of the workload')
     ap.add_argument('--lm', type=int, default=None, help='override the landmark count of the workload')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-c4', action='store_true', help='skip the single-GPU C4 leg')
-    ap.add_argument('--no-wall', action='store_true', help='skip the Problem.solve() wall-clock leg (500 000 Python block objects)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also measure everything beside the headline figure (module docstring)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-c4', action='store_true', help='--full: skip the single-GPU C4 leg')
+    ap.add_argument('--no-wall', action='store_true', help='--full: skip the Problem.solve() wall-clock leg (500 000 Python block objects)')
     ap.add_argument('--force-sharded', action='store_true',
                     help='use the multi-GPU driver (RCCL all-reduce) even with one rank (testing)')
     ap.add_argument('--shard-order', default='first_pose', choices=['first_pose', 'index'],
@@ -568,6 +577,11 @@ def main():
     ap.add_argument('--exchange', default=None, choices=['allreduce', 'segments'])
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed solve returned as DIR/<name>.npy (module docstring)')
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
@@ -648,44 +662,42 @@ def main():
     ms_per_step = elapsed * 1e3 / cold['iterations']
     n_pcg_list = cold['pcg_iters']
     n_pcg = int(round(float(np.mean(n_pcg_list)))) if n_pcg_list else 0
-    # untimed: one more cold solve with an event pair around every stage, for the breakdown only
-    # (per ITERATION of that solve: a stage that does not run in every iteration -- the cost-only pass since round 5: the cost
-    #  after a step is summed by the next iteration's landmark pass, run in the tail -- is spread over the solve's iterations)
-    detail = stage_breakdown(dev, start, fence)
-    n_detail_its = detail.get('iteration_total', (0.0, 0))[1]
-    for k, v in detail.items():
-        if k not in ('schur_pairs', 'cg_kernel') and v[1] > 0:
-            stages[k] = (v[0], n_detail_its if (n_detail_its > 0 and k != 'iteration_total') else v[1])
-    i0 = problem_info(core)
-    counted = cold_solves(dev, start, 4, fence, warm_solves=1)
-    i1 = problem_info(core)
-    # launches of the reduced solve per iteration, spare (gated, no-op) launches past convergence included.  cold_solves always runs
-    # one untimed solve in front of the counted one: both are between the two counter reads.  (Rounds 3-4 divided by the counted
-    # solve's iterations only and reported twice the launches -- 47.5 for 23.8 -- hence half the time per launch.)
-    n_launch = (i1['cg_kernel_launches'] - i0['cg_kernel_launches']) / float(2 * max(counted['iterations'], 1))
+    steady = moving = ranks_stage = None
+    if args.full:
+        # untimed: one more cold solve with an event pair around every stage, for the breakdown only
+        # (per ITERATION of that solve: a stage that does not run in every iteration -- the cost-only pass since round 5: the cost
+        #  after a step is summed by the next iteration's landmark pass, run in the tail -- is spread over the solve's iterations)
+        detail = stage_breakdown(dev, start, fence)
+        n_detail_its = detail.get('iteration_total', (0.0, 0))[1]
+        for k, v in detail.items():
+            if k not in ('schur_pairs', 'cg_kernel') and v[1] > 0:
+                stages[k] = (v[0], n_detail_its if (n_detail_its > 0 and k != 'iteration_total') else v[1])
+        i0 = problem_info(core)
+        counted = cold_solves(dev, start, 4, fence, warm_solves=1)
+        i1 = problem_info(core)
+        # launches of the reduced solve per iteration, spare (gated, no-op) launches past convergence included.  cold_solves always
+        # runs one untimed solve in front of the counted one: both are between the two counter reads.  (Rounds 3-4 divided by the
+        # counted solve's iterations only and reported twice the launches -- 47.5 for 23.8 -- hence half the time per launch.)
+        n_launch = (i1['cg_kernel_launches'] - i0['cg_kernel_launches']) / float(2 * max(counted['iterations'], 1))
 
-    # the figures of rounds 1-3, kept as extra keys: the same linearisation point restored before every step
-    steady = moving = None
-    if dist is None:
-        core.reset_solver_state(); core.set_params(*start)
-        dev.eval_cost(True); dev.snapshot()
-        sec1, out1 = time_steps(dev, 20, 8, fence)
-        core.set_option('lagged_inverse', 0)
-        core.reset_solver_state(); core.set_params(*start)
-        dev.eval_cost(True); dev.snapshot()
-        sec0, out0 = time_steps(dev, 10, 3, fence)
-        core.set_option('lagged_inverse', 1)
-        steady = (sec1 * 1e3 / 20, out1[2]); moving = (sec0 * 1e3 / 10, out0[2])
-    ranks_stage = None
-    if dist is not None:                                     # every rank's stage times (incl. allreduce, pack_unpack) on rank 0
-        mine = {k: round(v[0] / max(v[1], 1), 4) for k, v in stages.items() if v[1] > 0}
-        ranks_stage = [None] * world
-        dist.all_gather_object(ranks_stage, mine)
+        # the figures of rounds 1-3, kept as extra keys: the same linearisation point restored before every step
+        if dist is None:
+            core.reset_solver_state(); core.set_params(*start)
+            dev.eval_cost(True); dev.snapshot()
+            sec1, out1 = time_steps(dev, 20, 8, fence)
+            core.set_option('lagged_inverse', 0)
+            core.reset_solver_state(); core.set_params(*start)
+            dev.eval_cost(True); dev.snapshot()
+            sec0, out0 = time_steps(dev, 10, 3, fence)
+            core.set_option('lagged_inverse', 1)
+            steady = (sec1 * 1e3 / 20, out1[2]); moving = (sec0 * 1e3 / 10, out0[2])
+        if dist is not None:                                 # every rank's stage times (incl. allreduce, pack_unpack) on rank 0
+            mine = {k: round(v[0] / max(v[1], 1), 4) for k, v in stages.items() if v[1] > 0}
+            ranks_stage = [None] * world
+            dist.all_gather_object(ranks_stage, mine)
 
     if rank == 0:
-        b_iter, b_schur, b_spmv = algorithmic_bytes(info, n_pcg)
-        stage_ms = {k: (v[0] / max(v[1], 1)) for k, v in stages.items() if v[1] > 0}
-        sch = stage_ms.get('schur_pairs', 0.0)
+        b_iter, _, _ = algorithmic_bytes(info, n_pcg)
         total_blocks = lp_full.num_obs
         hist = cold['cost_history']
         line = {
@@ -717,38 +729,42 @@ def main():
                            'per_call_note': 'host wall clock of each ps_gn_iteration call by its position in the solve (median over the '
                                             'solves); the solve time also holds the start-cost pass, the best-parameter snapshots and '
                                             'the final restore'},
-            'stage_ms': {k: round(v, 4) for k, v in name_stage_totals(stage_ms).items()},
-            'stage_ms_note': 'schur_pairs, cg_kernel (the CG launch alone): hipEvent pairs inside the timed region, each on every 8th linearisation (alternating: one pair per four iterations); the other stages from one '
-                             'more untimed cold solve with an event pair around every stage, per iteration of that solve. landmark_pass: '
-                             'since round 5 the pass of the NEXT iteration runs in the tail and sums the cost after the step on its way '
-                             '(one evaluation of every observation per iteration); cost = what is left of the cost-only pass (the last '
-                             'iteration of a solve), spread over the iterations. stages_sum = GPU time of an iteration (sum of '
-                             'the stage pairs); call_event_pair = the pair around one ps_gn_iteration call, which EXCLUDES a linearisation '
-                             'enqueued speculatively behind the previous call (every iteration of a solve but the first)',
             'metric_definition': {'version': 2, 'since_round': 4,
                                   'text': 'ms per iteration of COLD, reference-terminated solves (rounds 1-3: a steady-state step at a '
                                           'restored linearisation point, kept as steady_same_point_ms); ps_reset_solver_state and the '
                                           'parameter upload of each solve are outside the clock, everything else of the solve inside'},
             'iteration_algorithmic_GBps': round(b_iter / (ms_per_step * 1e-3) / 1e9, 2),
+            'full': args.full,
         }
-        # `roofline` = the kernel with the largest measured time per iteration (roofline_objects above); the Schur pair kernel and
-        # the CG launch keep objects of their own whichever of them that is
-        persist = i1.get('cg_persist_solves', 0) > i0.get('cg_persist_solves', 0)
-        explicit = i1.get('xcg_fused_solves', 0) > i0.get('xcg_fused_solves', 0)
-        line.update(roofline_objects(info, stage_ms, pmc_config(cfg), n_pcg, persist, explicit, n_launch))
-        pcg_ms = stage_ms.get('pcg', 0.0)
-        line['reduced_solve_stage'] = {
-            'ms_per_iteration': round(pcg_ms, 5), 'cg_kernel_ms': round(stage_ms.get('cg_kernel', 0.0), 5),
-            'launches_of_the_cg_per_iteration': round(n_launch, 2), 'cg_iterations': n_pcg,
-            'note': 'event pair around the whole reduced solve (set-up kernels + CG launch(es) + recovery) on one untimed cold solve; '
-                    'cg_kernel_ms: the pair around the CG launch(es) alone, sampled inside the timed region'}
         line['value_median'] = {
             'ms_per_iteration_median_of_solves': cold['ms_median_of_solves'],
             'sum_of_per_call_medians_over_calls': round(float(np.sum(cold['per_call_ms'])) / max(len(cold['per_call_ms']), 1), 4),
             'note': 'SURVEY 8d words the metric as a median: per-solve ms / iterations, median over the {} timed solves; and the per-call '
                     'medians (ps_gn_iteration calls only: no start cost, snapshots, restore) averaged over a solve. `value` is the MEAN over '
                     'exactly {} iterations (bench contract)'.format(cold['solves'], cold['iterations'])}
-        line['lagged_inverse'] = {k: i1[k] for k in ('ldi_solves', 'ldi_fallbacks', 'ldi_seeds')}
+        if args.full:
+            stage_ms = {k: (v[0] / max(v[1], 1)) for k, v in stages.items() if v[1] > 0}
+            line['stage_ms'] = {k: round(v, 4) for k, v in name_stage_totals(stage_ms).items()}
+            line['stage_ms_note'] = (
+                'schur_pairs, cg_kernel (the CG launch alone): hipEvent pairs inside the timed region, each on every 8th linearisation (alternating: one pair per four iterations); the other stages from one '
+                'more untimed cold solve with an event pair around every stage, per iteration of that solve. landmark_pass: '
+                'since round 5 the pass of the NEXT iteration runs in the tail and sums the cost after the step on its way '
+                '(one evaluation of every observation per iteration); cost = what is left of the cost-only pass (the last '
+                'iteration of a solve), spread over the iterations. stages_sum = GPU time of an iteration (sum of '
+                'the stage pairs); call_event_pair = the pair around one ps_gn_iteration call, which EXCLUDES a linearisation '
+                'enqueued speculatively behind the previous call (every iteration of a solve but the first)')
+            # `roofline` = the kernel with the largest measured time per iteration (roofline_objects above); the Schur pair kernel and
+            # the CG launch keep objects of their own whichever of them that is
+            persist = i1.get('cg_persist_solves', 0) > i0.get('cg_persist_solves', 0)
+            explicit = i1.get('xcg_fused_solves', 0) > i0.get('xcg_fused_solves', 0)
+            line.update(roofline_objects(info, stage_ms, pmc_config(cfg), n_pcg, persist, explicit, n_launch))
+            pcg_ms = stage_ms.get('pcg', 0.0)
+            line['reduced_solve_stage'] = {
+                'ms_per_iteration': round(pcg_ms, 5), 'cg_kernel_ms': round(stage_ms.get('cg_kernel', 0.0), 5),
+                'launches_of_the_cg_per_iteration': round(n_launch, 2), 'cg_iterations': n_pcg,
+                'note': 'event pair around the whole reduced solve (set-up kernels + CG launch(es) + recovery) on one untimed cold solve; '
+                        'cg_kernel_ms: the pair around the CG launch(es) alone, sampled inside the timed region'}
+            line['lagged_inverse'] = {k: i1[k] for k in ('ldi_solves', 'ldi_fallbacks', 'ldi_seeds')}
         if steady is not None:
             line['steady_same_point_ms'] = round(steady[0], 4)
             line['steady_same_point_note'] = ('rounds 1-3 `value`: every step restores the same linearisation point, so the lagged dense '
@@ -756,7 +772,7 @@ def main():
                                               'reference-terminated solve of this workload never reaches'.format(steady[1]))
             line['moving_same_point_ms'] = round(moving[0], 4)
             line['moving_same_point_note'] = 'the same with the lagged dense inverse off ({} CG iterations; round 3: first_iteration_ms)'.format(moving[1])
-        if not args.no_c4 and not args.kf and not args.lm:
+        if args.full and not args.no_c4 and not args.kf and not args.lm:
             if dist is None:
                 dev.close()                                      # free the C3 tables first
             c4 = c4_single_gpu(stream)
@@ -768,14 +784,14 @@ def main():
             line['stage_ms_per_rank'] = ranks_stage
             line['native_rccl'] = bool(getattr(dev, 'native', None) is not None)
             line['native_rccl_reason'] = None if line['native_rccl'] else getattr(dev, 'native_reason', None)
-        if world == 1 and not args.kf and not args.lm:
+        if args.full and world == 1 and not args.kf and not args.lm:
             line['c5_solve_wall_ms'] = c5_frames()
             if not args.no_wall:
                 line['cold_solve_wall_ms'] = {'C3': cold_solve_wall(C3)}
                 if not args.no_c4:      # once: building the 5 M block objects (not part of solve()) takes ~12 s
                     w4 = cold_solve_wall(C4, reps=1)
                     line['cold_solve_wall_ms']['C4'] = {'run': w4['first_in_process'], 'note': w4['note']}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line['cpu_baseline'] = cpu_baseline(lp)
         if outputs is not None:
             line['dumped_outputs'] = dump_outputs(args.dump_outputs, outputs)

@@ -140,3 +140,10 @@ def test_steps_below_one_are_refused():
     import sys
     r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and '--steps must be at least 1' in r.stderr
+
+
+def test_full_is_an_option_and_off_by_default():
+    """The legs beside the headline figure run only with --full (module docstring of bench.py)."""
+    import bench
+    assert bench.arg_parser().parse_args([]).full is False
+    assert bench.arg_parser().parse_args(['--full', '--no-c4']).full is True

@@ -46,3 +46,27 @@ def test_dumped_outputs_are_those_of_the_last_timed_solve(tmp_path):
     assert rel_err(got['cost_history'], last['cost_history']) < 1e-12
     assert rel_err(got['poses'], poses) < 1e-12 and rel_err(got['points'], points) < 1e-12
     assert not np.array_equal(got['points'], lp.points)          # (the solve moved them: not the start)
+
+
+def test_plain_run_is_the_headline_and_full_adds_the_other_legs():
+    """A plain run does only what its headline figure needs; --full adds the legs that take runs of their own after the timed region
+    (stage breakdown, roofline objects, launch counts, same-point figures, CPU baseline) around the same timed solves."""
+    kf, lm, steps = 12, 600, 4
+    base = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1', '--kf', str(kf),
+            '--lm', str(lm)]
+    lines = {}
+    for mode, extra in (('plain', []), ('full', ['--full'])):
+        run = subprocess.run(base + extra, cwd=REPO, capture_output=True, text=True, timeout=600)
+        assert run.returncode == 0, (mode, run.stderr[-3000:])
+        lines[mode] = json.loads(run.stdout.strip().splitlines()[-1])
+    plain, full = lines['plain'], lines['full']
+    for line in (plain, full):
+        assert line['steps'] == steps and line['cold_solve']['iterations'] == steps and line['ms_per_step'] > 0
+        assert line['value'] == line['ms_per_step'] and line['unit'] == 'ms/LM-iter'
+        assert line['higher_is_better'] is False and line['dtype'] == 'f64'
+    assert plain['metric'] == full['metric']
+    legs = ('stage_ms', 'roofline', 'roofline_schur', 'roofline_cg', 'reduced_solve_stage', 'lagged_inverse', 'steady_same_point_ms',
+            'moving_same_point_ms', 'cpu_baseline')
+    assert plain['full'] is False and [k for k in legs if k in plain] == []
+    assert full['full'] is True and [k for k in legs if k not in full] == []
+    assert rel_err(plain['config']['cost_history'], full['config']['cost_history']) < 1e-12

@@ -48,7 +48,7 @@ python tools/schur_ablate.py 2>&1 | grep ablate
 echo
 echo "# the sharded protocol at shard size on ONE GPU (bench.py --force-sharded --kf 2000 --lm L: what rank 0 of an N-GPU run executes, 1-rank RCCL; DESIGN.md section 6)"
 for L in 500000 125000 62500; do
-  python bench.py --force-sharded --kf 2000 --lm $L --steps 10 --no-cpu-baseline --no-c4 2> /dev/null | grep '^{' | python -c "
+  python bench.py --full --force-sharded --kf 2000 --lm $L --steps 10 --no-cpu-baseline --no-c4 2> /dev/null | grep '^{' | python -c "
 import json, sys
 b = json.loads(sys.stdin.read())
 print('landmarks', $L, 'iteration ms', b['value'], 'stage_ms', b.get('stage_ms'), 'native_rccl', b.get('native_rccl'))"

@@ -41,7 +41,7 @@ bash tools/cold_trace.sh 2>&1 | grep "iteration [1-4]:\|ms per iteration"
 echo
 echo "# the sharded protocol at shard size on ONE GPU, cold solves (bench.py --force-sharded --kf 2000 --lm L: what rank 0 of an N-GPU run executes, 1-rank RCCL)"
 for L in 500000 250000 125000 62500; do
-  python bench.py --force-sharded --kf 2000 --lm $L --steps 8 --no-cpu-baseline --no-c4 --no-wall 2> /dev/null | grep '^{' | python -c "
+  python bench.py --full --force-sharded --kf 2000 --lm $L --steps 8 --no-cpu-baseline --no-c4 --no-wall 2> /dev/null | grep '^{' | python -c "
 import json, sys
 b = json.loads(sys.stdin.read())
 print('landmarks', $L, 'ms per iteration (cold solves)', b['value'], 'per call', b['cold_solve']['per_call_ms'], 'stage_ms', b.get('stage_ms'), 'native_rccl', b.get('native_rccl'))"

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 EXTRA=""
 if [ -n "$1" ]; then EXTRA="--kf $1 --lm $2"; fi
-BENCH="python $PWD/bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-c4 $EXTRA"
+BENCH="python $PWD/bench.py --steps 8 --warmup 3 --full --no-cpu-baseline --no-c4 $EXTRA"
 (cd /tmp && rm -rf /tmp/gt && rocprofv3 --kernel-trace --output-format csv -d /tmp/gt -o kt -- $BENCH > /dev/null 2>&1)
 python - <<'PY'
 import csv, glob, collections

@@ -1,5 +1,5 @@
 export TMPDIR=/tmp
-BENCH="python $PWD/bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-c4"
+BENCH="python $PWD/bench.py --steps 8 --warmup 3 --full --no-cpu-baseline --no-c4"
 (cd /tmp && rm -rf /tmp/gt && rocprofv3 --kernel-trace --output-format csv -d /tmp/gt -o kt -- $BENCH > /dev/null 2>&1)
 python - <<'PY'
 import csv, glob

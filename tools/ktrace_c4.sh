@@ -1,5 +1,5 @@
 export TMPDIR=/tmp
-BENCH="python $PWD/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-c4 --kf 2000 --lm 500000"
+BENCH="python $PWD/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-c4 --kf 2000 --lm 500000"
 (cd /tmp && rm -rf /tmp/kt4 && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt4 -o kt -- $BENCH > /dev/null 2>&1)
 python - <<'PY'
 import csv, glob

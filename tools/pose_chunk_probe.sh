@@ -5,7 +5,7 @@ for tr in 1 0; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -pthread -Wno-unused-value -Wno-unused-result -DPS_POSE_TRANSPOSE=$tr \
      -Iinclude pyslam_amd/csrc/ps_core.hip -o pyslam_amd/lib/libpyslam_hip.so 2>/dev/null
   for ch in 256 512 1024; do
-    PS_POSE_CHUNK=$ch python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+    PS_POSE_CHUNK=$ch python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
