@@ -345,6 +345,17 @@ int ps_covariance_marginals(ps_problem* h, double* pose_blocks /* (nr, D, D) or 
                             double* point_blocks /* (nv, 3, 3) or NULL */);
 int ps_covariance_pose_blocks(ps_problem* h, int64_t n, const int32_t* a, const int32_t* b,
                               double* out /* (n, D, D) */);
+/* After ps_covariance_marginals, any block of the full covariance from the same Sigma_pp:
+   out[36 k ...] = Sigma[(kind_a[k], a[k]), (kind_b[k], b[k])]; kind 0 = reduced pose index (rid), 1 = variable
+   landmark index (vid, the caller's order, as point_blocks); the block row-major dof_a x dof_b in the leading
+   entries of a 36-double slot, the rest zero.  Pose-landmark: -sum_i Sigma_pp[a, r_i] Z_i M over the landmark's
+   observations on variable poses (M: its factor, C^-1 = M^T M), landmark-pose its exact transpose; landmark-landmark
+   M1^T (sum_ij Z_i^T Sigma_pp[r_i, r_j] Z_j) M2, (l2, l1) the exact transpose of (l1, l2); (l, l) bit-identical to
+   point_blocks, pose-pose to ps_covariance_pose_blocks.  Any n: pairs pass through a fixed device buffer (allocated
+   by the first call, freed by ps_problem_destroy), with results that do not depend on the chunking.  Errors: no
+   current Sigma_pp, a kind other than 0 / 1, an index out of range, landmarks on a problem whose poses are not SE(3). */
+int ps_covariance_cross_blocks(ps_problem* h, int64_t n, const int32_t* kind_a, const int32_t* a,
+                               const int32_t* kind_b, const int32_t* b, double* out /* (n, 36) */);
 
 /* Parity / debug taps (device -> host). */
 int ps_get_reduced_system(ps_problem* h, int32_t* row_ptr, int32_t* col_idx,

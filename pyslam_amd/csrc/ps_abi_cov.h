@@ -4,7 +4,8 @@
 // ps_covariance_marginals densifies the reduced system that ps_covariance_begin left in S (n = nr * D unknowns, at most
 // PS_COV_DENSE_MAX_UNKNOWNS), factors it, forms Sigma_pp = S^-1 in fp64 and keeps it on the handle; the pose blocks are its
 // diagonal blocks, the landmark blocks follow from it and the Schur elimination's Z rows / C^-1 factors of the same
-// linearisation.  ps_covariance_pose_blocks reads further D x D blocks of the kept Sigma_pp.
+// linearisation.  ps_covariance_pose_blocks reads further D x D blocks of the kept Sigma_pp; ps_covariance_cross_blocks any
+// block of the full covariance (pose-pose, pose-landmark either way, landmark-landmark) from the same Sigma_pp, Z and C^-1.
 
 // one device block: [A: S, then Sigma (n^2) | L^-1 (n^2) | L^-T (n^2) | Tinv | diag (n) | pose out (nr D^2) | landmark out (9 nv) | stat]
 static size_t cov_layout(const ps_problem* h, size_t off[8]) {
@@ -127,6 +128,59 @@ int ps_covariance_pose_blocks(ps_problem* h, int64_t n, const int32_t* a, const 
         hipLaunchKernelGGL(k_cov_gather, dim3(cdiv((long)m * DD, 256)), dim3(256), 0, h->stream, m, D, h->nr * D, da, db,
                            h->cov_buf + off[0], buf);
         HIP_OK(hipMemcpyAsync(out + (size_t)k0 * DD, buf, m * DD * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (sync(h)) return -1;
+    }
+    return 0;
+}
+
+// pairs per pass of ps_covariance_cross_blocks through its fixed buffer (36 doubles of result + four int32 per pair: 10 MiB)
+#define PS_COV_CROSS_CHUNK 32768
+
+int ps_covariance_cross_blocks(ps_problem* h, int64_t n, const int32_t* kind_a, const int32_t* a, const int32_t* kind_b,
+                               const int32_t* b, double* out) {
+    if (!h) return fail("null argument");
+    if (!h->cov_ready || !h->cov_buf || h->cov_sigma_epoch != h->cov_epoch)
+        return fail("ps_covariance_cross_blocks: no dense inverse on the handle (call ps_covariance_marginals after "
+                    "ps_covariance_begin; any linearisation invalidates it)");
+    if (n < 0 || (n > 0 && (!kind_a || !a || !kind_b || !b || !out))) return fail("ps_covariance_cross_blocks: null argument");
+    for (int64_t k = 0; k < n; ++k) {
+        const int32_t kinds[2] = {kind_a[k], kind_b[k]}, ix[2] = {a[k], b[k]};
+        for (int s2 = 0; s2 < 2; ++s2) {
+            if (kinds[s2] != 0 && kinds[s2] != 1)
+                return fail("ps_covariance_cross_blocks: pair " + std::to_string(k) + ": kind " + std::to_string(kinds[s2]) +
+                            " (0 = reduced pose, 1 = variable landmark)");
+            if (kinds[s2] == 1 && h->D != 6)
+                return fail("ps_covariance_cross_blocks: landmarks on a problem whose poses are not SE(3)");
+            if (ix[s2] < 0 || ix[s2] >= (kinds[s2] == 0 ? h->nr : h->nv))
+                return fail("ps_covariance_cross_blocks: pair " + std::to_string(k) + ": " +
+                            (kinds[s2] == 0 ? "reduced pose" : "landmark") + " index " + std::to_string(ix[s2]) + " out of range");
+        }
+    }
+    if (n == 0) return 0;
+    if (!h->cov_xbuf) {
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, (size_t)PS_COV_CROSS_CHUNK * (36 + 2) * sizeof(double));
+        if (e != hipSuccess) return fail(std::string("ps_covariance_cross_blocks: hipMalloc: ") + hipGetErrorString(e));
+        h->cov_xbuf = (double*)p;
+    }
+    size_t off[8];
+    cov_layout(h, off);
+    const double* Sigma = h->cov_buf + off[0];
+    double* dres = h->cov_xbuf;
+    int32_t* drec = reinterpret_cast<int32_t*>(h->cov_xbuf + (size_t)PS_COV_CROSS_CHUNK * 36);
+    std::vector<int32_t> rec((size_t)4 * std::min<int64_t>(n, PS_COV_CROSS_CHUNK));
+    for (int64_t k0 = 0; k0 < n; k0 += PS_COV_CROSS_CHUNK) {
+        const int m = (int)std::min<int64_t>(PS_COV_CROSS_CHUNK, n - k0);
+        for (int k = 0; k < m; ++k) {                    // landmarks: the caller's vid -> the internal slot
+            rec[4 * k] = kind_a[k0 + k];
+            rec[4 * k + 1] = kind_a[k0 + k] ? h->h_slot_of_vid[a[k0 + k]] : a[k0 + k];
+            rec[4 * k + 2] = kind_b[k0 + k];
+            rec[4 * k + 3] = kind_b[k0 + k] ? h->h_slot_of_vid[b[k0 + k]] : b[k0 + k];
+        }
+        HIP_OK(hipMemcpyAsync(drec, rec.data(), (size_t)4 * m * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_cov_cross, dim3(cdiv(m, 256 / PS_LM_GROUP)), dim3(256), 0, h->stream, m, h->nr * h->D, h->D, drec,
+                           h->lm_ptr, h->Z, h->Cinv, Sigma, dres);
+        HIP_OK(hipMemcpyAsync(out + (size_t)k0 * 36, dres, (size_t)m * 36 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         if (sync(h)) return -1;
     }
     return 0;

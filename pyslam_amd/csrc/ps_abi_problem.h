@@ -110,6 +110,7 @@ int ps_problem_destroy(ps_problem* h) {
     if (h->side) hipStreamSynchronize(h->side);
     if (h->ldi_stream) hipStreamSynchronize(h->ldi_stream);
     cov_release(h);
+    if (h->cov_xbuf) hipFree(h->cov_xbuf);
     for (void* p : h->allocs) hipFree(p);
     h->arena_release();            // arena block, its pinned mirror and the pinned result words go back to the process-wide pool
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);

@@ -401,6 +401,7 @@ struct ps_problem {
     // batched marginals (ps_abi_cov.h): one device block [S -> Sigma (n^2) | L^-1 (n^2) | L^-T (n^2) | ...], allocated by the first
     // ps_covariance_marginals, freed by the next linearisation, ps_covariance_begin or destroy; Sigma is valid for cov_epoch only
     double* cov_buf = nullptr;
+    double* cov_xbuf = nullptr;     // ps_covariance_cross_blocks' fixed pair buffer: allocated by its first call, freed by destroy
     long long cov_epoch = 0, cov_sigma_epoch = -1;
     int ell_wf = 0, ell_wc = 0;     // two-class ELL widths of the CG matrix (0 = CSR)
     // scalars

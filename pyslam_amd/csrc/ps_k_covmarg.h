@@ -7,7 +7,9 @@
 // and for a landmark with observations i, j on variable poses r_i, r_j, M = C^-1 (its packed lower factor) and Z_i the
 // observation's 6 x 3 row of the Schur elimination (zrow_expand):
 //     Sigma_ll = M^T (I + sum_{i,j} Z_i^T Sigma_pp[r_i, r_j] Z_j) M    (k_cov_landmarks)
-// -- the closed form of k_cov_rhs -> reduced solve -> k_backsub, which compute one column of the same matrix.
+// -- the closed form of k_cov_rhs -> reduced solve -> k_backsub, which compute one column of the same matrix -- and the cross
+// blocks between any two of them (k_cov_cross): Sigma_al = -sum_i Sigma_pp[a, r_i] Z_i M, Sigma_l1l2 = M1^T (sum_ij Z_i^T
+// Sigma_pp[r_i, r_j] Z_j) M2.
 #pragma once
 
 typedef double ps_f64x4 __attribute__((ext_vector_type(4)));
@@ -150,6 +152,72 @@ __global__ __launch_bounds__(256) void k_cov_gather(int nblk, int D, int n, cons
 // Observations on constant poses (reduced index -1 in their Z row) contribute nothing.  With T the (symmetrised) sum:
 // out[v] = M^T (I + T) M, lower triangle computed, mirrored (exactly symmetric).  Slot order: the host maps it to vid.
 // ---------------------------------------------------------------------------
+
+// acc (3 x 3, this lane's part) += sum over observations i = beg1 + sub, beg1 + sub + 16, ... < end1 and ALL j in [beg2, end2),
+// in index order, of Z_i^T Sigma[r_i, r_j] Z_j (both on variable poses).  beg1 == beg2: the landmark marginals' sum
+PS_DEV void cov_zsz_accumulate(int sub, int n, int beg1, int end1, int beg2, int end2, const double* __restrict__ Z,
+                               const double* __restrict__ Sigma, double* __restrict__ acc)
+{
+    for (int i = beg1 + sub; i < end1; i += PS_LM_GROUP) {
+        const double* zr = Z + PS_ZROW * (size_t)i;
+        const int ri = (int)zr[12];
+        if (ri < 0) continue;
+        double zi[18];
+        zrow_expand(zr, zr + 9, zi);
+        for (int j = beg2; j < end2; ++j) {
+            const double* zs = Z + PS_ZROW * (size_t)j;
+            const int rj = (int)zs[12];
+            if (rj < 0) continue;
+            double zj[18];
+            zrow_expand(zs, zs + 9, zj);
+            const double* sg = Sigma + (size_t)ri * 6 * n + (size_t)rj * 6;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                // row a of Sigma[r_i, r_j] Z_j, then acc += Z_i[a]^T (that row)
+                double s[6];
+#pragma unroll
+                for (int c = 0; c < 6; ++c) s[c] = sg[(size_t)a * n + c];
+                double w[3];
+#pragma unroll
+                for (int bb = 0; bb < 3; ++bb) {
+                    double x = 0.0;
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) x += s[c] * zj[3 * c + bb];
+                    w[bb] = x;
+                }
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+#pragma unroll
+                    for (int bb = 0; bb < 3; ++bb) acc[3 * k + bb] += zi[3 * a + k] * w[bb];
+            }
+        }
+    }
+}
+
+// o (3 x 3, row-major) = M^T (I + sym(T)) M for the reduced sum T (acc) and the landmark's packed factor m
+PS_DEV void cov_landmark_finish(const double* __restrict__ acc, const double* __restrict__ m, double* __restrict__ o)
+{
+    double N[9];                                           // I + sym(T)
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int bb = 0; bb < 3; ++bb) N[3 * k + bb] = 0.5 * (acc[3 * k + bb] + acc[3 * bb + k]) + (k == bb ? 1.0 : 0.0);
+    const double M[9] = {m[0], 0.0, 0.0, m[1], m[2], 0.0, m[3], m[4], m[5]};       // M00 M10 M11 M20 M21 M22 (lower)
+    double Q[9];                                           // Q = N M
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Q[3 * r + c] = N[3 * r] * M[c] + N[3 * r + 1] * M[3 + c] + N[3 * r + 2] * M[6 + c];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c <= r; ++c) {                     // (M^T Q)[r][c] = sum_a M[a][r] Q[a][c]
+            const double x = M[r] * Q[c] + M[3 + r] * Q[3 + c] + M[6 + r] * Q[6 + c];
+            o[3 * r + c] = x;
+            o[3 * c + r] = x;
+        }
+}
+
 __global__ __launch_bounds__(256) void k_cov_landmarks(
     int nv, int n, const int32_t* __restrict__ lm_ptr, const double* __restrict__ Z, const double* __restrict__ Cinv,
     const double* __restrict__ Sigma, double* __restrict__ out)
@@ -160,65 +228,115 @@ __global__ __launch_bounds__(256) void k_cov_landmarks(
     double acc[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) acc[k] = 0.0;
-    if (live) {
-        const int beg = lm_ptr[v], end = lm_ptr[v + 1];
-        for (int i = beg + sub; i < end; i += PS_LM_GROUP) {
+    if (live) cov_zsz_accumulate(sub, n, lm_ptr[v], lm_ptr[v + 1], lm_ptr[v], lm_ptr[v + 1], Z, Sigma, acc);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k] = group16_sum(acc[k]);
+    if (!live || sub != 0) return;
+    cov_landmark_finish(acc, Cinv + 6 * (size_t)v, out + 9 * (size_t)v);
+}
+
+// ---------------------------------------------------------------------------
+// Any block of the full covariance (ps_covariance_cross_blocks), one 16-lane group per pair k.  rec[4 k ..] = (kind_a, a,
+// kind_b, b): kind 0 a reduced pose index, kind 1 a landmark SLOT (the host maps vid -> slot).  out[36 k ..]: the block
+// row-major, dof_a x dof_b, in the leading entries, the rest zero.  With M the landmark's packed factor (C^-1 = M^T M):
+//   (pose a, pose b)    Sigma[a, b], copied (k_cov_gather's values)
+//   (pose a, lm l)      -sum_{i in l, r_i >= 0} Sigma[a, r_i] Z_i M  (6 x 3; lanes stride over l's observations) -- the pose
+//                       part of k_cov_rhs -> reduced solve for l's columns
+//   (lm l, pose a)      the transpose of (a, l): the same arithmetic, stored transposed
+//   (lm l, lm l)        k_cov_landmarks' marginal, the same code (bit-identical)
+//   (lm l1, lm l2)      M1^T (sum_{i in l1, j in l2} Z_i^T Sigma[r_i, r_j] Z_j) M2 for slot l1 < l2; l1 > l2 is computed as
+//                       (l2, l1) and stored transposed
+// Every group runs the same 18 fixed-order reductions, so a pair's result does not depend on its neighbours or its chunk.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_cov_cross(
+    int m, int n, int D, const int32_t* __restrict__ rec, const int32_t* __restrict__ lm_ptr, const double* __restrict__ Z,
+    const double* __restrict__ Cinv, const double* __restrict__ Sigma, double* __restrict__ out)
+{
+    const int k = blockIdx.x * (blockDim.x / PS_LM_GROUP) + threadIdx.x / PS_LM_GROUP;
+    const int sub = threadIdx.x & (PS_LM_GROUP - 1);
+    const bool live = k < m;                               // whole 16-lane groups are live or not
+    int ka = 0, a = 0, kb = 0, b = 0;
+    if (live) { ka = rec[4 * k]; a = rec[4 * k + 1]; kb = rec[4 * k + 2]; b = rec[4 * k + 3]; }
+    const bool pl = ka != kb;                              // pose-landmark, either order
+    const int p = ka == 0 ? a : b, l = ka == 0 ? b : a;    // (pose-landmark pairs)
+    const bool swap_ll = ka == 1 && kb == 1 && a > b;
+    const int l1 = swap_ll ? b : a, l2 = swap_ll ? a : b;  // (landmark pairs: canonical slot order)
+    double acc[18];
+#pragma unroll
+    for (int q = 0; q < 18; ++q) acc[q] = 0.0;
+    if (live && pl) {
+        // acc (6 x 3) = sum_i Sigma[p, r_i] Z_i
+        for (int i = lm_ptr[l] + sub; i < lm_ptr[l + 1]; i += PS_LM_GROUP) {
             const double* zr = Z + PS_ZROW * (size_t)i;
             const int ri = (int)zr[12];
             if (ri < 0) continue;
             double zi[18];
             zrow_expand(zr, zr + 9, zi);
-            for (int j = beg; j < end; ++j) {
-                const double* zs = Z + PS_ZROW * (size_t)j;
-                const int rj = (int)zs[12];
-                if (rj < 0) continue;
-                double zj[18];
-                zrow_expand(zs, zs + 9, zj);
-                const double* sg = Sigma + (size_t)ri * 6 * n + (size_t)rj * 6;
+            const double* sg = Sigma + (size_t)p * 6 * n + (size_t)ri * 6;
 #pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    // row a of Sigma[r_i, r_j] Z_j, then acc += Z_i[a]^T (that row)
-                    double s[6];
+            for (int r = 0; r < 6; ++r) {
+                double s[6];
 #pragma unroll
-                    for (int c = 0; c < 6; ++c) s[c] = sg[(size_t)a * n + c];
-                    double w[3];
+                for (int c = 0; c < 6; ++c) s[c] = sg[(size_t)r * n + c];
 #pragma unroll
-                    for (int bb = 0; bb < 3; ++bb) {
-                        double x = 0.0;
+                for (int bb = 0; bb < 3; ++bb) {
+                    double x = 0.0;
 #pragma unroll
-                        for (int c = 0; c < 6; ++c) x += s[c] * zj[3 * c + bb];
-                        w[bb] = x;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 3; ++k)
-#pragma unroll
-                        for (int bb = 0; bb < 3; ++bb) acc[3 * k + bb] += zi[3 * a + k] * w[bb];
+                    for (int c = 0; c < 6; ++c) x += s[c] * zi[3 * c + bb];
+                    acc[3 * r + bb] += x;
                 }
             }
         }
+    } else if (live && ka == 1)
+        cov_zsz_accumulate(sub, n, lm_ptr[l1], lm_ptr[l1 + 1], lm_ptr[l2], lm_ptr[l2 + 1], Z, Sigma, acc);
+#pragma unroll
+    for (int q = 0; q < 18; ++q) acc[q] = group16_sum(acc[q]);
+    if (!live) return;
+    double* o = out + 36 * (size_t)k;
+    if (ka == 0 && kb == 0) {                              // pose-pose: a copy of Sigma[a, b]
+        for (int e = sub; e < 36; e += PS_LM_GROUP) {
+            const int r = e / D, c = e % D;
+            o[e] = e < D * D ? Sigma[(size_t)(a * D + r) * n + b * D + c] : 0.0;
+        }
+        return;
+    }
+    // every lane forms the whole block from the broadcast sums; lane sub stores entries sub, sub + 16, sub + 32
+    double res[36];
+#pragma unroll
+    for (int e = 0; e < 36; ++e) res[e] = 0.0;
+    if (pl) {
+        const double* mm = Cinv + 6 * (size_t)l;
+        const double M[9] = {mm[0], 0.0, 0.0, mm[1], mm[2], 0.0, mm[3], mm[4], mm[5]};
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double x = -(acc[3 * r] * M[c] + acc[3 * r + 1] * M[3 + c] + acc[3 * r + 2] * M[6 + c]);
+                if (ka == 0) res[3 * r + c] = x;           // (pose, landmark): 6 x 3
+                else res[6 * c + r] = x;                   // (landmark, pose): 3 x 6
+            }
+    } else if (l1 == l2) {
+        cov_landmark_finish(acc, Cinv + 6 * (size_t)l1, res);
+    } else {
+        const double* m1 = Cinv + 6 * (size_t)l1;
+        const double* m2 = Cinv + 6 * (size_t)l2;
+        const double M1[9] = {m1[0], 0.0, 0.0, m1[1], m1[2], 0.0, m1[3], m1[4], m1[5]};
+        const double M2[9] = {m2[0], 0.0, 0.0, m2[1], m2[2], 0.0, m2[3], m2[4], m2[5]};
+        double Q[9];                                       // Q = T M2
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Q[3 * r + c] = acc[3 * r] * M2[c] + acc[3 * r + 1] * M2[3 + c] + acc[3 * r + 2] * M2[6 + c];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {                  // (M1^T Q)[r][c]
+                const double x = M1[r] * Q[c] + M1[3 + r] * Q[3 + c] + M1[6 + r] * Q[6 + c];
+                if (swap_ll) res[3 * c + r] = x;           // (static indices: the array stays in registers)
+                else res[3 * r + c] = x;
+            }
     }
 #pragma unroll
-    for (int k = 0; k < 9; ++k) acc[k] = group16_sum(acc[k]);
-    if (!live || sub != 0) return;
-    double N[9];                                           // I + sym(T)
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int bb = 0; bb < 3; ++bb) N[3 * k + bb] = 0.5 * (acc[3 * k + bb] + acc[3 * bb + k]) + (k == bb ? 1.0 : 0.0);
-    const double* m = Cinv + 6 * (size_t)v;               // M00 M10 M11 M20 M21 M22 (lower)
-    const double M[9] = {m[0], 0.0, 0.0, m[1], m[2], 0.0, m[3], m[4], m[5]};
-    double Q[9];                                           // Q = N M
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Q[3 * r + c] = N[3 * r] * M[c] + N[3 * r + 1] * M[3 + c] + N[3 * r + 2] * M[6 + c];
-    double* o = out + 9 * (size_t)v;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c <= r; ++c) {                     // (M^T Q)[r][c] = sum_a M[a][r] Q[a][c]
-            const double x = M[r] * Q[c] + M[3 + r] * Q[3 + c] + M[6 + r] * Q[6 + c];
-            o[3 * r + c] = x;
-            o[3 * c + r] = x;
-        }
+    for (int e = 0; e < 36; ++e)
+        if ((e & (PS_LM_GROUP - 1)) == sub) o[e] = res[e];
 }

@@ -311,6 +311,17 @@ class DeviceProblem:
         nat.check(self._lib.ps_covariance_pose_blocks(self._h, a.shape[0], nat.i32p(a), nat.i32p(b), nat.f64p(out)))
         return out
 
+    def covariance_cross_blocks(self, kind_a, a, kind_b, b):
+        """Sigma[(kind_a_k, a_k), (kind_b_k, b_k)] (len(a), 36) from the inverse covariance_marginals() left: kind 0 a reduced
+        pose index (rid), 1 a variable landmark index (vid); block k row-major (dof_a, dof_b) in the leading entries of row k,
+        the rest zero."""
+        arrs = [np.ascontiguousarray(x, dtype=np.int32).reshape(-1) for x in (kind_a, a, kind_b, b)]
+        if any(x.shape != arrs[0].shape for x in arrs):
+            raise ValueError('covariance_cross_blocks: kind_a, a, kind_b and b differ in length')
+        out = np.zeros((arrs[0].shape[0], 36))
+        nat.check(self._lib.ps_covariance_cross_blocks(self._h, arrs[0].shape[0], *[nat.i32p(x) for x in arrs], nat.f64p(out)))
+        return out
+
     # ---- data movement -------------------------------------------------
     def get_dx(self):
         """(dx_pose (nr, dof), dx_point (nv, 3)) in device order."""

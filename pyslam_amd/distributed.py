@@ -652,6 +652,9 @@ class ShardedProblemView:
     def covariance_pose_blocks(self, a, b):
         return self._replica.covariance_pose_blocks(a, b)
 
+    def covariance_cross_blocks(self, kind_a, a, kind_b, b):
+        return self._replica.covariance_cross_blocks(kind_a, a, kind_b, b)
+
     def close(self):
         self.sharded.close()
         if self._replica is not None:

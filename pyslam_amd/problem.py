@@ -728,31 +728,34 @@ class Problem:
     # ------------------------------------------------------------------
     # batched marginal covariances (no reference counterpart: the reference inverts the whole precision matrix)
     # ------------------------------------------------------------------
-    def compute_marginal_covariances(self, keys=None, pose_pairs=()):
+    def compute_marginal_covariances(self, keys=None, pose_pairs=(), cross_pairs=()):
         """Marginal covariance blocks at the current parameters (linearised here, lambda = 0, as compute_covariance does).
 
         -> dict: every key of `keys` (None: every non-constant parameter) -> its (dof, dof) block, 3 x 3 for a landmark; every
-        (key_a, key_b) of `pose_pairs` -> the cross block Sigma_ab (dof_a, dof_b).  A constant or unknown key raises KeyError.
+        (key_a, key_b) of `pose_pairs` or `cross_pairs` -> the cross block Sigma_ab (dof_a, dof_b), oriented as
+        get_covariance_block(key_a, key_b).  A constant or unknown key raises KeyError.
 
         Typed problems (hybrid ones included): one device call forms S^-1 of the reduced system densely in fp64 (up to
         pyslam_amd.device.COVARIANCE_MARGINALS_LIMIT reduced unknowns, else it raises) and every landmark's block from it;
-        pose_pairs must then name poses.  The photometric form slices the inverse of its 6 x 6 system, the host-evaluated
-        generic route the dense covariance of dense_normal_solve (beyond DENSE_GENERIC_LIMIT: CG columns, as
-        get_covariance_block).  compute_covariance's state is neither read nor written."""
+        pose_pairs must then name poses, cross_pairs may name any two poses or landmarks (one more device call for all of
+        them).  The photometric form slices the inverse of its 6 x 6 system, the host-evaluated generic route the dense
+        covariance of dense_normal_solve (beyond DENSE_GENERIC_LIMIT: CG columns, as get_covariance_block).
+        compute_covariance's state is neither read nor written."""
         part = self._get_update_partition_dict()
         want = list(part) if keys is None else list(keys)
         pairs = _check_pose_pairs(pose_pairs)
-        for k in want + [k for pr in pairs for k in pr]:
+        cpairs = _check_pose_pairs(cross_pairs, 'cross_pairs')
+        for k in want + [k for pr in pairs + cpairs for k in pr]:
             _check_cov_key(k, part, self.constant_param_keys)
         try:
             dev = self._get_device()
         except NotLowerable:
             dev = None
         if dev is None:
-            return self._marginals_generic(part, want, pairs)
+            return self._marginals_generic(part, want, pairs + cpairs)
         if self._photometric_form():
             cov = self._photometric_covariance(dev, part)
-            return _slice_dense_blocks(cov, part, want, pairs)
+            return _slice_dense_blocks(cov, part, want, pairs + cpairs)
         dev.covariance_begin()
         pose, point = dev.covariance_marginals()
         out = marginal_blocks_by_key(dev.lp, pose, point, want)
@@ -760,6 +763,9 @@ class Problem:
             a, b = pose_pair_indices(dev.lp, pairs)
             for pr, blk in zip(pairs, dev.covariance_pose_blocks(a, b)):
                 out[pr] = blk
+        if cpairs:
+            ka, a, kb, b = cross_pair_indices(dev.lp, cpairs)
+            out.update(cross_blocks_by_key(cpairs, ka, kb, dev.lp.dof, dev.covariance_cross_blocks(ka, a, kb, b)))
         return out
 
     def _photometric_covariance(self, dev, part):
@@ -869,11 +875,11 @@ def _check_cov_key(key, part, constant_keys):
     raise KeyError('{!r} is not a parameter of this problem'.format(key))
 
 
-def _check_pose_pairs(pose_pairs):
+def _check_pose_pairs(pose_pairs, name='pose_pairs'):
     pairs = []
     for pr in pose_pairs:
         if isinstance(pr, (str, bytes)) or not hasattr(pr, '__len__') or len(pr) != 2:
-            raise ValueError('pose_pairs: every entry must be a (key_a, key_b) pair, got {!r}'.format(pr))
+            raise ValueError('{}: every entry must be a (key_a, key_b) pair, got {!r}'.format(name, pr))
         pairs.append((pr[0], pr[1]))
     return pairs
 
@@ -907,6 +913,34 @@ def pose_pair_indices(lp, pairs):
                 raise ValueError('pose_pairs: {!r} is not a variable pose (cross blocks exist between poses only)'.format(k))
         a.append(rid[ka]); b.append(rid[kb])
     return np.array(a, dtype=np.int32), np.array(b, dtype=np.int32)
+
+
+def cross_pair_indices(lp, pairs):
+    """(kind_a, a, kind_b, b) (int32) of the (key_a, key_b) pairs for DeviceProblem.covariance_cross_blocks: kind 0 with the
+    reduced pose index (rid), kind 1 with the variable landmark index (vid).  KeyError for a constant or unknown key."""
+    where = {}
+    for k, rid in zip(lp.pose_keys, lp.pose_rid):
+        where[k] = (0, int(rid))
+    for k, vid in zip(lp.point_keys, lp.point_vid):
+        where[k] = (1, int(vid))
+    idx = np.empty((len(pairs), 4), dtype=np.int32)
+    for q, pr in enumerate(pairs):
+        for s, k in enumerate(pr):
+            if k not in where:
+                raise KeyError('{!r} is not a parameter of this problem'.format(k))
+            if where[k][1] < 0:
+                raise KeyError('{!r} is a constant parameter: it has no covariance'.format(k))
+            idx[q, 2 * s:2 * s + 2] = where[k]
+    return tuple(np.ascontiguousarray(idx[:, c]) for c in range(4))
+
+
+def cross_blocks_by_key(pairs, kind_a, kind_b, dof, blocks):
+    """{(key_a, key_b): (dof_a, dof_b) block} from covariance_cross_blocks' (n, 36) rows; a landmark's dof is 3, a pose's `dof`."""
+    out = {}
+    for pr, ka, kb, row in zip(pairs, kind_a, kind_b, blocks):
+        da, db = (dof if ka == 0 else 3), (dof if kb == 0 else 3)
+        out[pr] = row[:da * db].reshape(da, db).copy()
+    return out
 
 
 def _slice_dense_blocks(cov, part, keys, pairs):
