@@ -583,6 +583,44 @@ int ps_dense_read_tables(ps_dense* h, int32_t slot, int32_t level, int32_t num_p
 /* device memory held by the handle */
 int ps_dense_device_bytes(ps_dense* h, int64_t* bytes);
 
+/* Feature matcher of the sparse VO pipelines (pyslam/pipelines/sparse.py; definition: DESIGN.md section 7, host
+   restatement pyslam_amd/pipelines/featproc.py): corner features with 32-byte gradient descriptors and circular
+   matching between the previous and the current frame, all on the device.  A handle holds three frames of at most
+   max_height x max_width (one uint8 image, or a left / right pair) and at most max_features features per image; its
+   device memory is fixed at create time. */
+typedef struct ps_feat ps_feat;
+typedef struct ps_feat_params {
+    int64_t response_threshold;      /* a feature has R > response_threshold */
+    int32_t nms_n;                   /* non-maximum suppression over (2 nms_n + 1)^2 pixels, 1..3 */
+    int32_t max_features;            /* per image, <= the handle's; above it the strongest are kept */
+    int32_t match_radius_u, match_radius_v;   /* temporal legs: |du| <= match_radius_u, |dv| <= match_radius_v */
+    int32_t disp_max;                /* stereo legs: |dv| <= 1, 0 <= u_left - u_right <= disp_max */
+    int32_t match_cost_max;          /* a best candidate above this sum of absolute differences is no match */
+    int32_t refinement;              /* != 0: sub-pixel refinement (two-line fit of the costs at -1, 0, +1) */
+    int32_t reserved;
+} ps_feat_params;
+int ps_feat_create(int32_t max_height, int32_t max_width, int32_t max_features, void* hip_stream, ps_feat** out);
+int ps_feat_destroy(ps_feat* h);
+/* The current frame becomes the previous one and (left, right or NULL) the current one.  A frame whose bytes equal a
+   frame the handle holds (previous, current or the one cached beside them) is neither uploaded nor processed again.
+   The images are copied before the call returns. */
+int ps_feat_push(ps_feat* h, int32_t height, int32_t width, const uint8_t* left, const uint8_t* right);
+/* mode 0 flow (previous left <-> current left), 1 stereo (current left <-> current right), 2 quad (previous left ->
+   previous right -> current right -> current left -> previous left).  Computes the features of the frames that have
+   none under these parameters, matches, and waits once for the number of matches. */
+int ps_feat_match(ps_feat* h, int32_t mode, const ps_feat_params* params, int32_t* num_matches);
+/* Matches of the last ps_feat_match, in the order of their first feature: matches8 = num_matches x (u1p v1p u2p v2p
+   u1c v1c u2c v2c) (1 left, 2 right, p previous, c current; -1 where a mode has no such image), indices4 =
+   num_matches x feature index (1p 2p 1c 2c; -1 likewise).  Either may be NULL. */
+int ps_feat_read_matches(ps_feat* h, int32_t num_matches, double* matches8, int32_t* indices4);
+/* Features of an image after a match (which: 0 previous left, 1 previous right, 2 current left, 3 current right), at
+   most `capacity` of them: uv (2 x int32 each, raster order), response R, descriptors (32 bytes each).  Tests. */
+int ps_feat_read_features(ps_feat* h, int32_t which, int32_t capacity, int32_t* num_features, int32_t* uv, int64_t* response,
+                          uint8_t* descriptors);
+/* number of images whose features were computed since create (a recognised frame adds none) */
+int ps_feat_feature_passes(ps_feat* h, int64_t* passes);
+int ps_feat_device_bytes(ps_feat* h, int64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,12 @@ class PhotoDesc(C.Structure):
     ]
 
 
+class FeatParams(C.Structure):
+    _fields_ = [('response_threshold', C.c_int64), ('nms_n', C.c_int32), ('max_features', C.c_int32),
+                ('match_radius_u', C.c_int32), ('match_radius_v', C.c_int32), ('disp_max', C.c_int32),
+                ('match_cost_max', C.c_int32), ('refinement', C.c_int32), ('reserved', C.c_int32)]
+
+
 # every symbol include/pyslam_hip.h declares: name -> (restype, argtypes)
 H = C.c_void_p
 SIGNATURES = {
@@ -150,6 +156,14 @@ SIGNATURES = {
     'ps_dense_num_pixels': (C.c_int, [H, C.c_int32, C.c_int32, c_i32p]),
     'ps_dense_read_tables': (C.c_int, [H, C.c_int32, C.c_int32, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p]),
     'ps_dense_device_bytes': (C.c_int, [H, C.POINTER(C.c_int64)]),
+    'ps_feat_create': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(H)]),
+    'ps_feat_destroy': (C.c_int, [H]),
+    'ps_feat_push': (C.c_int, [H, C.c_int32, C.c_int32, c_u8p, c_u8p]),
+    'ps_feat_match': (C.c_int, [H, C.c_int32, C.POINTER(FeatParams), c_i32p]),
+    'ps_feat_read_matches': (C.c_int, [H, C.c_int32, c_f64p, c_i32p]),
+    'ps_feat_read_features': (C.c_int, [H, C.c_int32, C.c_int32, c_i32p, c_i32p, C.POINTER(C.c_int64), c_u8p]),
+    'ps_feat_feature_passes': (C.c_int, [H, C.POINTER(C.c_int64)]),
+    'ps_feat_device_bytes': (C.c_int, [H, C.POINTER(C.c_int64)]),
     'ps_dense_normal_solve': (C.c_int, [c_f64p, c_f64p, C.c_int32, C.c_int32, c_f64p, c_f64p]),
     'ps_sparse_normal_solve': (C.c_int, [C.c_int32, C.c_int32, c_i32p, c_i32p, c_f64p, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p,
                                          C.c_double, C.c_int32, c_f64p, c_i32p, c_f64p]),

@@ -1,0 +1,255 @@
+// ps_abi_feat.h -- C ABI: the feature matcher of the sparse VO pipelines (kernels in csrc/ps_k_feat.h; definition:
+// DESIGN.md section 7).  Part of ps_core.hip (one translation unit; included from there, in this order).
+//
+// A handle keeps three frames (one or two images each): the previous and the current one, as a matcher with a
+// two-frame window does, and one more as a cache.  A pushed frame whose bytes equal a frame the handle holds is not
+// uploaded and its features are not computed again: the sparse pipelines push the active keyframe in front of every
+// tracking frame.  Everything is allocated at create time; a match is a fixed sequence of launches on the handle's
+// stream with one synchronisation at its end.
+
+extern "C++" {
+struct PsFeatImage {
+    uint8_t* img = nullptr;
+    short *du = nullptr, *dv = nullptr;
+    int2* uv = nullptr;
+    long long* R = nullptr;
+    uint32_t* desc = nullptr;
+    int *row_start = nullptr, *n = nullptr;
+    FeatList list() const { return FeatList{n, uv, desc, row_start, du, dv}; }
+};
+
+struct PsFeatFrame {
+    int h = 0, w = 0, stereo = 0;
+    bool held = false, features_ok = false;
+    long long det_threshold = 0;
+    int det_nms = 0, det_max = 0;
+    uint64_t used = 0;
+    std::vector<uint8_t> host[2];           // the bytes as pushed: a frame is recognised by content
+    PsFeatImage im[2];
+};
+
+struct ps_feat {
+    hipStream_t stream = nullptr;
+    int max_h = 0, max_w = 0, max_features = 0, raw_cap = 0;
+    PsFeatFrame frame[3];
+    int prev = -1, cur = -1;
+    uint64_t clock = 0;
+    int64_t feature_passes = 0, bytes = 0;
+    std::vector<void*> allocs;
+    // scratch of a feature pass and of a match
+    long long *R = nullptr, *raw_R = nullptr;
+    uint8_t *flags = nullptr, *keep = nullptr, *mflags = nullptr;
+    int *counts = nullptr, *n_raw = nullptr, *leg[4] = {}, *visited = nullptr, *idx4 = nullptr, *n_match = nullptr;
+    int2* raw_uv = nullptr;
+    double* m8 = nullptr;
+    int h_n_match = 0;
+    int alloc_bytes(void** p, size_t b) {
+        if (hipMalloc(p, std::max<size_t>(b, 16)) != hipSuccess) return fail("hipMalloc failed");
+        allocs.push_back(*p);
+        bytes += (int64_t)std::max<size_t>(b, 16);
+        return 0;
+    }
+    template <typename T> int alloc(T** p, size_t n) { return alloc_bytes((void**)p, n * sizeof(T)); }
+    ~ps_feat() { for (void* p : allocs) hipFree(p); }
+};
+}  // extern "C++"
+
+namespace {
+// features of one image (steps 1-4 of the definition): nine launches, no synchronisation
+int feat_pass(ps_feat* f, PsFeatImage& im, int h, int w, const ps_feat_params& p) {
+    const dim3 grid(cdiv(w, PS_FEAT_TX), cdiv(h, PS_FEAT_TY));
+    const int n = h * w, nb = cdiv(n, 256), rb = cdiv(f->raw_cap, 256);
+    hipStream_t s = f->stream;
+    hipLaunchKernelGGL(k_feat_sobel, grid, dim3(256), 0, s, (const uint8_t*)im.img, h, w, im.du, im.dv);
+    hipLaunchKernelGGL(k_feat_response, grid, dim3(256), 0, s, (const short*)im.du, (const short*)im.dv, h, w, f->R);
+    hipLaunchKernelGGL(k_feat_nms, grid, dim3(256), 0, s, (const long long*)f->R, h, w, (int)p.nms_n, (long long)p.response_threshold, f->flags);
+    hipLaunchKernelGGL(k_feat_count, dim3(nb), dim3(256), 0, s, n, (const uint8_t*)f->flags, f->counts);
+    hipLaunchKernelGGL(k_dense_scan, dim3(1), dim3(1024), 0, s, nb, f->counts, f->n_raw);
+    hipLaunchKernelGGL(k_feat_compact_pix, dim3(nb), dim3(256), 0, s, n, w, (const uint8_t*)f->flags, (const int*)f->counts,
+                       (const long long*)f->R, f->raw_cap, f->raw_uv, f->raw_R);
+    hipLaunchKernelGGL(k_feat_rank, dim3(rb), dim3(256), 0, s, (const int*)f->n_raw, f->raw_cap, (const long long*)f->raw_R,
+                       (int)p.max_features, f->keep);
+    hipLaunchKernelGGL(k_feat_count, dim3(rb), dim3(256), 0, s, f->raw_cap, (const uint8_t*)f->keep, f->counts);
+    hipLaunchKernelGGL(k_dense_scan, dim3(1), dim3(1024), 0, s, rb, f->counts, im.n);
+    hipLaunchKernelGGL(k_feat_compact_feat, dim3(rb), dim3(256), 0, s, f->raw_cap, (const uint8_t*)f->keep, (const int*)f->counts,
+                       (const int2*)f->raw_uv, (const long long*)f->raw_R, (const short*)im.du, (const short*)im.dv, h, w,
+                       (int)p.max_features, im.uv, im.R, im.desc);
+    hipLaunchKernelGGL(k_feat_rowstart, dim3(cdiv(h + 1, 256)), dim3(256), 0, s, h, (const int*)im.n, (int)p.max_features,
+                       (const int2*)im.uv, im.row_start);
+    HIP_OK(hipGetLastError());
+    f->feature_passes += 1;
+    return 0;
+}
+
+int feat_frame_features(ps_feat* f, PsFeatFrame& fr, const ps_feat_params& p) {
+    if (fr.features_ok && fr.det_threshold == p.response_threshold && fr.det_nms == p.nms_n && fr.det_max == p.max_features) return 0;
+    for (int k = 0; k <= fr.stereo; ++k)
+        if (feat_pass(f, fr.im[k], fr.h, fr.w, p)) return -1;
+    fr.features_ok = true;
+    fr.det_threshold = p.response_threshold; fr.det_nms = p.nms_n; fr.det_max = p.max_features;
+    return 0;
+}
+
+void feat_leg(ps_feat* f, const PsFeatImage& A, const PsFeatImage& B, int h, const ps_feat_params& p, int kind, int* out) {
+    // kind 0 temporal, 1 left -> right (u_left - u_right in 0 .. disp_max), 2 right -> left
+    const int du_lo = kind == 0 ? -p.match_radius_u : (kind == 1 ? -p.disp_max : 0);
+    const int du_hi = kind == 0 ? p.match_radius_u : (kind == 1 ? 0 : p.disp_max);
+    const int dv = kind == 0 ? p.match_radius_v : 1;
+    hipLaunchKernelGGL(k_feat_match, dim3(cdiv((long)p.max_features * 64, 256)), dim3(256), 0, f->stream, A.list(), B.list(), h,
+                       (int)p.max_features, du_lo, du_hi, -dv, dv, (int)p.match_cost_max, out);
+}
+}  // namespace
+
+int ps_feat_create(int32_t max_height, int32_t max_width, int32_t max_features, void* stream, ps_feat** out) {
+    if (!out) return fail("null argument");
+    *out = nullptr;
+    if (max_height < 1 || max_width < 1 || (int64_t)max_height * max_width > (1 << 28)) return fail("frame size out of range");
+    if (max_features < 1 || max_features > (1 << 20)) return fail("max_features must be 1 .. 2^20");
+    if (need_device()) return -1;
+    std::unique_ptr<ps_feat> f(new ps_feat);
+    f->stream = (hipStream_t)stream;
+    f->max_h = max_height; f->max_w = max_width; f->max_features = max_features;
+    // non-maximum suppression with nms_n >= 1 leaves at most one feature in every aligned 2 x 2 block
+    f->raw_cap = cdiv(max_height, 2) * cdiv(max_width, 2);
+    const size_t P = (size_t)max_height * max_width, M = max_features, Rc = f->raw_cap;
+    for (PsFeatFrame& fr : f->frame)
+        for (PsFeatImage& im : fr.im)
+            if (f->alloc(&im.img, P) || f->alloc(&im.du, P) || f->alloc(&im.dv, P) || f->alloc(&im.uv, M) || f->alloc(&im.R, M) ||
+                f->alloc(&im.desc, 8 * M) || f->alloc(&im.row_start, (size_t)max_height + 1) || f->alloc(&im.n, 1)) return -1;
+    if (f->alloc(&f->R, P) || f->alloc(&f->raw_R, Rc) || f->alloc(&f->flags, P) || f->alloc(&f->keep, Rc) || f->alloc(&f->mflags, M) ||
+        f->alloc(&f->counts, (size_t)cdiv((long)std::max(P, std::max(Rc, M)), 256) + 1) || f->alloc(&f->n_raw, 1) ||
+        f->alloc(&f->visited, 4 * M) || f->alloc(&f->idx4, 4 * M) || f->alloc(&f->n_match, 1) || f->alloc(&f->raw_uv, Rc) ||
+        f->alloc(&f->m8, 8 * M)) return -1;
+    for (int k = 0; k < 4; ++k)
+        if (f->alloc(&f->leg[k], M)) return -1;
+    *out = f.release();
+    return 0;
+}
+
+int ps_feat_destroy(ps_feat* f) {
+    if (!f) return 0;
+    if (f->stream) hipStreamSynchronize(f->stream); else hipDeviceSynchronize();
+    delete f;
+    return 0;
+}
+
+int ps_feat_push(ps_feat* f, int32_t height, int32_t width, const uint8_t* left, const uint8_t* right) {
+    if (!f || !left) return fail("null argument");
+    if (height < 1 || width < 1 || height > f->max_h || width > f->max_w) return fail("frame size outside the handle's capacity");
+    const size_t n = (size_t)height * width;
+    const int stereo = right ? 1 : 0;
+    int s = -1;
+    for (int k = 0; k < 3 && s < 0; ++k) {
+        const PsFeatFrame& fr = f->frame[k];
+        if (fr.held && fr.h == height && fr.w == width && fr.stereo == stereo && !memcmp(fr.host[0].data(), left, n) &&
+            (!stereo || !memcmp(fr.host[1].data(), right, n))) s = k;
+    }
+    if (s < 0) {                                           // least recently used slot that is not the current frame
+        for (int k = 0; k < 3; ++k)
+            if (k != f->cur && (s < 0 || f->frame[k].used < f->frame[s].used)) s = k;
+        PsFeatFrame& fr = f->frame[s];
+        fr.h = height; fr.w = width; fr.stereo = stereo; fr.held = true; fr.features_ok = false;
+        const uint8_t* src[2] = {left, right};
+        for (int k = 0; k <= stereo; ++k) {
+            fr.host[k].assign(src[k], src[k] + n);        // the upload reads this copy: the caller's buffer is free on return
+            HIP_OK(hipMemcpyAsync(fr.im[k].img, fr.host[k].data(), n, hipMemcpyHostToDevice, f->stream));
+        }
+    }
+    f->frame[s].used = ++f->clock;
+    f->prev = f->cur;
+    f->cur = s;
+    return 0;
+}
+
+int ps_feat_match(ps_feat* f, int32_t mode, const ps_feat_params* params, int32_t* num_matches) {
+    if (!f || !params || !num_matches) return fail("null argument");
+    *num_matches = 0;
+    const ps_feat_params& p = *params;
+    if (mode < 0 || mode > 2) return fail("matching mode must be 0 (flow), 1 (stereo) or 2 (quad)");
+    if (p.nms_n < 1 || p.nms_n > 3) return fail("nms_n must be 1..3");
+    if (p.max_features < 1 || p.max_features > f->max_features) return fail("max_features outside the handle's capacity");
+    if (p.match_radius_u < 0 || p.match_radius_v < 0 || p.disp_max < 0) return fail("negative matching window");
+    if (f->cur < 0 || (mode != 1 && f->prev < 0)) return fail("push the frames before matching");
+    PsFeatFrame& C = f->frame[f->cur];
+    PsFeatFrame& P = f->frame[mode == 1 ? f->cur : f->prev];
+    if (mode != 0 && (!C.stereo || !P.stereo)) return fail("stereo and quad matching need right images");
+    if (P.h != C.h || P.w != C.w) return fail("the two frames differ in size");
+    if (feat_frame_features(f, P, p) || feat_frame_features(f, C, p)) return -1;
+    const int h = C.h, w = C.w, M = p.max_features, mb = cdiv(M, 256);
+    // the images a chain visits: flow 1p 1c, stereo 1c 2c, quad 1p 2p 2c 1c
+    const PsFeatImage* node[4];
+    FeatChain ch{};
+    if (mode == 0) {
+        ch.legs = 2; node[0] = &P.im[0]; node[1] = &C.im[0]; ch.col[0] = 0; ch.col[1] = 2; ch.temporal[1] = 1;
+        feat_leg(f, *node[0], *node[1], h, p, 0, f->leg[0]);
+        feat_leg(f, *node[1], *node[0], h, p, 0, f->leg[1]);
+    } else if (mode == 1) {
+        ch.legs = 2; node[0] = &C.im[0]; node[1] = &C.im[1]; ch.col[0] = 2; ch.col[1] = 3; ch.temporal[1] = 0;
+        feat_leg(f, *node[0], *node[1], h, p, 1, f->leg[0]);
+        feat_leg(f, *node[1], *node[0], h, p, 2, f->leg[1]);
+    } else {
+        ch.legs = 4; node[0] = &P.im[0]; node[1] = &P.im[1]; node[2] = &C.im[1]; node[3] = &C.im[0];
+        ch.col[0] = 0; ch.col[1] = 1; ch.col[2] = 3; ch.col[3] = 2; ch.temporal[1] = 0; ch.temporal[2] = 1; ch.temporal[3] = 0;
+        feat_leg(f, *node[0], *node[1], h, p, 1, f->leg[0]);
+        feat_leg(f, *node[1], *node[2], h, p, 0, f->leg[1]);
+        feat_leg(f, *node[2], *node[3], h, p, 2, f->leg[2]);
+        feat_leg(f, *node[3], *node[0], h, p, 0, f->leg[3]);
+    }
+    if (ch.legs == 2) { node[2] = node[0]; node[3] = node[1]; }
+    hipStream_t s = f->stream;
+    hipLaunchKernelGGL(k_feat_chain, dim3(mb), dim3(256), 0, s, (const int*)node[0]->n, M, ch.legs, (const int*)f->leg[0],
+                       (const int*)f->leg[1], (const int*)f->leg[2], (const int*)f->leg[3], f->mflags, f->visited);
+    hipLaunchKernelGGL(k_feat_count, dim3(mb), dim3(256), 0, s, M, (const uint8_t*)f->mflags, f->counts);
+    hipLaunchKernelGGL(k_dense_scan, dim3(1), dim3(1024), 0, s, mb, f->counts, f->n_match);
+    hipLaunchKernelGGL(k_feat_compact_match, dim3(mb), dim3(256), 0, s, M, (const uint8_t*)f->mflags, (const int*)f->counts,
+                       (const int*)f->visited, ch, f->idx4);
+    hipLaunchKernelGGL(k_feat_subpix, dim3(mb), dim3(256), 0, s, (const int*)f->n_match, M, (const int*)f->idx4, ch, node[0]->list(),
+                       node[1]->list(), node[2]->list(), node[3]->list(), h, w, (int)p.refinement, f->m8);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(&f->h_n_match, f->n_match, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    *num_matches = f->h_n_match;
+    return 0;
+}
+
+int ps_feat_read_matches(ps_feat* f, int32_t num_matches, double* matches8, int32_t* indices4) {
+    if (!f) return fail("null handle");
+    if (num_matches < 0 || num_matches > f->h_n_match) return fail("more matches asked for than the last ps_feat_match found");
+    if (matches8) HIP_OK(hipMemcpyAsync(matches8, f->m8, (size_t)num_matches * 8 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    if (indices4) HIP_OK(hipMemcpyAsync(indices4, f->idx4, (size_t)num_matches * 4 * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    HIP_OK(hipStreamSynchronize(f->stream));
+    return 0;
+}
+
+int ps_feat_read_features(ps_feat* f, int32_t which, int32_t capacity, int32_t* num_features, int32_t* uv, int64_t* response,
+                          uint8_t* descriptors) {
+    if (!f || !num_features) return fail("null argument");
+    if (which < 0 || which > 3) return fail("which must be 0 (previous left), 1 (previous right), 2 (current left) or 3 (current right)");
+    const int slot = which < 2 ? f->prev : f->cur;
+    if (slot < 0) return fail("no such frame");
+    const PsFeatFrame& fr = f->frame[slot];
+    if (!fr.features_ok || ((which & 1) && !fr.stereo)) return fail("the image has no features: match first");
+    const PsFeatImage& im = fr.im[which & 1];
+    int n = 0;
+    HIP_OK(hipMemcpyAsync(&n, im.n, sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    HIP_OK(hipStreamSynchronize(f->stream));
+    *num_features = n;
+    const size_t m = (size_t)std::min(n, capacity < 0 ? 0 : capacity);
+    if (uv) HIP_OK(hipMemcpyAsync(uv, im.uv, m * 2 * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    if (response) HIP_OK(hipMemcpyAsync(response, im.R, m * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
+    if (descriptors) HIP_OK(hipMemcpyAsync(descriptors, im.desc, m * 32, hipMemcpyDeviceToHost, f->stream));
+    HIP_OK(hipStreamSynchronize(f->stream));
+    return 0;
+}
+
+int ps_feat_feature_passes(ps_feat* f, int64_t* passes) {
+    if (!f || !passes) return fail("null argument");
+    *passes = f->feature_passes;
+    return 0;
+}
+
+int ps_feat_device_bytes(ps_feat* f, int64_t* bytes) {
+    if (!f || !bytes) return fail("null argument");
+    *bytes = f->bytes;
+    return 0;
+}

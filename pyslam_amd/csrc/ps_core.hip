@@ -26,6 +26,7 @@
 #include "ps_ransac.h"
 #include "ps_photo.h"
 #include "ps_k_dense.h"
+#include "ps_k_feat.h"
 #include "ps_sparse.h"
 #include "ps_k_covmarg.h"
 
@@ -662,5 +663,6 @@ extern "C" {
 #include "ps_abi_cov.h"
 #include "ps_abi_small.h"
 #include "ps_abi_dense.h"
+#include "ps_abi_feat.h"
 
 }  // extern "C"

@@ -1,0 +1,149 @@
+"""The feature matcher of the sparse VO pipelines, on the device.
+
+``Matcher_parameters`` and ``Matcher`` are the two names reference pyslam/pipelines/sparse.py takes from ``viso2``;
+the three calls it makes -- ``pushBack(left[, right])``, ``matchFeatures(mode)``, ``getMatches()`` -- behave as a
+pipeline written for the reference expects, and a match has the attributes ``u1p v1p u2p v2p u1c v1c u2c v2c``.
+The matcher is NOT libviso2: it is a front end of this project with an exact integer definition (DESIGN.md section 7;
+numpy restatement: pipelines/featproc.py) that runs in the HIP core (include/pyslam_hip.h: ps_feat_*).  There is no
+CPU path.
+
+A pushed frame whose bytes equal a frame the matcher holds -- the previous one, the current one or one cached beside
+them -- is not processed again: the pipelines push the active keyframe in front of every tracking frame.
+``feature_passes`` counts the images whose features were computed.  ``matches_array()`` returns the matches as arrays
+(the pipelines use it instead of building one Python object per match).
+"""
+import ctypes as C
+
+import numpy as np
+
+from pyslam_amd import _native as nat
+
+__all__ = ['Matcher_parameters', 'Matcher', 'Match']
+
+_FIELDS = (('response_threshold', 1 << 36), ('nms_n', 2), ('max_features', 4096), ('match_radius_u', 200),
+           ('match_radius_v', 50), ('disp_max', 160), ('match_cost_max', 1200), ('refinement', 1))
+
+
+class Matcher_parameters:
+    """Constants of the matcher's definition (the same fields and defaults as featproc.Params)."""
+
+    def __init__(self, **kw):
+        for k, v in _FIELDS:
+            setattr(self, k, kw.pop(k, v))
+        if kw:
+            raise TypeError('unknown matcher parameters: {}'.format(sorted(kw)))
+
+    def _native(self):
+        return nat.FeatParams(*[int(getattr(self, k)) for k, _ in _FIELDS], 0)
+
+
+class Match:
+    """One match: pixel positions in the previous (p) and current (c) left (1) and right (2) images."""
+    __slots__ = ('u1p', 'v1p', 'u2p', 'v2p', 'u1c', 'v1c', 'u2c', 'v2c', 'i1p', 'i2p', 'i1c', 'i2c')
+
+    def __init__(self, row, idx):
+        self.u1p, self.v1p, self.u2p, self.v2p, self.u1c, self.v1c, self.u2c, self.v2c = (float(x) for x in row)
+        self.i1p, self.i2p, self.i1c, self.i2c = (int(x) for x in idx)
+
+
+def _image(img, what):
+    img = np.asarray(img)
+    if img.ndim != 2 or img.dtype != np.uint8:
+        raise TypeError('Matcher: {} must be a single-channel uint8 image, got {} {}'.format(what, img.dtype, img.shape))
+    return np.ascontiguousarray(img)
+
+
+class Matcher:
+    def __init__(self, params=None, stream=None):
+        self.params = params if params is not None else Matcher_parameters()
+        self._stream = stream
+        self._h = None
+        self._shape = None
+        self._lib = None
+        self._n = 0
+        self._passes_before = 0
+
+    def setIntrinsics(self, *args):
+        """Accepted and ignored (libviso2 uses the calibration for its 3-D outlier checks; RANSAC follows here)."""
+
+    def close(self):
+        if self._h is not None:
+            self._passes_before = self.feature_passes
+            self._lib.ps_feat_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001
+            pass
+
+    def _handle(self, h, w):
+        cap = int(self.params.max_features)
+        if self._h is None or h > self._shape[0] or w > self._shape[1] or cap > self._shape[2]:
+            self.close()
+            self._lib = nat.require_gpu()
+            hh = nat.H()
+            shape = (max(h, self._shape[0]) if self._shape else h, max(w, self._shape[1]) if self._shape else w, cap)
+            nat.check(self._lib.ps_feat_create(shape[0], shape[1], shape[2], C.c_void_p(self._stream or 0), C.byref(hh)))
+            self._h, self._shape, self._n = hh, shape, 0
+        return self._h
+
+    def pushBack(self, left, right=None):
+        left = _image(left, 'the left image')
+        if right is not None:
+            right = _image(right, 'the right image')
+            if right.shape != left.shape:
+                raise ValueError('Matcher: left and right images differ in size')
+        h, w = left.shape
+        hd = self._handle(h, w)
+        nat.check(self._lib.ps_feat_push(hd, h, w, left.ctypes.data_as(nat.c_u8p),
+                                         right.ctypes.data_as(nat.c_u8p) if right is not None else None))
+        self._n = 0
+
+    def matchFeatures(self, mode):
+        if self._h is None:
+            raise nat.NativeError('Matcher: push the frames before matching')
+        n = C.c_int32()
+        p = self.params._native()
+        nat.check(self._lib.ps_feat_match(self._h, int(mode), C.byref(p), C.byref(n)))
+        self._n = n.value
+
+    def matches_array(self):
+        """(m, idx): (n, 8) float64 u1p v1p u2p v2p u1c v1c u2c v2c and (n, 4) int32 feature indices (1p 2p 1c 2c)."""
+        m = np.zeros((self._n, 8))
+        idx = np.zeros((self._n, 4), dtype=np.int32)
+        if self._n:
+            nat.check(self._lib.ps_feat_read_matches(self._h, self._n, nat.f64p(m), nat.i32p(idx)))
+        return m, idx
+
+    def getMatches(self):
+        m, idx = self.matches_array()
+        return [Match(m[k], idx[k]) for k in range(m.shape[0])]
+
+    def features(self, which):
+        """(uv (n, 2) int32, R (n,) int64, descriptors (n, 32) uint8) of image `which` after a match: 0 previous left,
+        1 previous right, 2 current left, 3 current right."""
+        cap = self._shape[2]
+        uv = np.zeros((cap, 2), dtype=np.int32)
+        R = np.zeros(cap, dtype=np.int64)
+        d = np.zeros((cap, 32), dtype=np.uint8)
+        n = C.c_int32()
+        nat.check(self._lib.ps_feat_read_features(self._h, int(which), cap, C.byref(n), nat.i32p(uv),
+                                                  R.ctypes.data_as(C.POINTER(C.c_int64)), d.ctypes.data_as(nat.c_u8p)))
+        return uv[:n.value].copy(), R[:n.value].copy(), d[:n.value].copy()
+
+    @property
+    def feature_passes(self):
+        """Number of images whose features were computed (a frame the matcher already holds adds none)."""
+        if self._h is None:
+            return self._passes_before
+        n = C.c_int64()
+        nat.check(self._lib.ps_feat_feature_passes(self._h, C.byref(n)))
+        return self._passes_before + n.value
+
+    @property
+    def device_bytes(self):
+        n = C.c_int64()
+        nat.check(self._lib.ps_feat_device_bytes(self._h, C.byref(n)))
+        return n.value

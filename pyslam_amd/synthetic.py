@@ -413,6 +413,87 @@ def rgbd_sequence(h=96, w=128, n_frames=8, seed=0, step=(0.02, -0.01, 0.04, 0.01
     return dict(images=images, depth=depth, cam=(cu, cv, fu, fv, w, h), T_c_w=T_c_w)
 
 
+
+def stereo_sequence(h=96, w=128, n_frames=8, seed=0, step=(0.02, -0.01, 0.04, 0.012, 0.015, -0.006), baseline=0.12,
+                    cell=0.16, edge=0.):
+    """A stereo sequence of the scene of rgbd_sequence (back wall, floor, slanted side wall), rendered the same exact
+    way (every pixel is the intensity of the point its ray meets first) from a left camera on rgbd_sequence's
+    trajectory and a right camera ``baseline`` metres along the left camera's x axis.
+
+    The texture has corners: each plane carries a seeded random piecewise-constant pattern, squares of ``cell`` metres
+    in the plane's own coordinates (the smooth sinusoids of rgbd_sequence give a corner detector nothing to find).
+    With ``edge`` = 0 the cells have step edges: point-sampled, every edge then falls on a whole pixel in each image and
+    the images hold no sub-pixel edge position.  With ``edge`` > 0 the last ``edge`` of every cell ramps linearly into
+    its neighbour (an edge of finite width, as a camera's blur gives), still evaluated exactly at the ray's point.
+
+    Returns ``left``, ``right`` (n, h, w) uint8, ``depth`` (n, h, w) float64 (true camera z of every left pixel, no
+    holes), ``cam`` = (cu, cv, fu, fv, b, w, h) and ``T_c_w`` (n, 4, 4) world-to-left-camera poses; with the depth and
+    the poses ``stereo_correspondence`` gives the true position of every left pixel in the other images."""
+    rng = np.random.default_rng(seed)
+    fu = fv = 0.9 * w
+    cu, cv = 0.5 * w - 0.5, 0.5 * h - 0.5
+    n2 = np.array([1., 0., 0.35]) / np.linalg.norm([1., 0., 0.35])
+    planes = [(np.array([0., 0., 1.]), 5.0, np.array([1., 0., 0.]), np.array([0., 1., 0.])),
+              (np.array([0., 1., 0.]), 1.0, np.array([1., 0., 0.]), np.array([0., 0., 1.])),
+              (n2, -1.2, np.array([0., 1., 0.]), np.cross(n2, [0., 1., 0.]))]
+    N = 64
+    tables = rng.integers(30, 226, size=(len(planes), N, N))
+    u, v = np.meshgrid(np.arange(w, dtype=float), np.arange(h, dtype=float), indexing='xy')
+    rays = np.stack([(u - cu) / fu, (v - cv) / fv, np.ones_like(u)], axis=-1)
+    step = np.asarray(step, dtype=float)
+
+    def render(R, t):
+        s_best = np.full((h, w), np.inf)
+        which = np.zeros((h, w), dtype=int)
+        for k, (n, c, _, _) in enumerate(planes):
+            Rn = R @ n
+            with np.errstate(divide='ignore', invalid='ignore'):
+                s = (c + Rn @ t) / (rays @ Rn)
+            hit = (s > 0.05) & (s < s_best)
+            s_best = np.where(hit, s, s_best)
+            which = np.where(hit, k, which)
+        P_w = (rays * s_best[..., None] - t) @ R
+        img = np.zeros((h, w), dtype=np.uint8)
+        for k, (_, _, e1, e2) in enumerate(planes):
+            a, b = P_w @ e1 / cell, P_w @ e2 / cell
+            i, j = np.floor(a).astype(np.int64), np.floor(b).astype(np.int64)
+            if edge > 0:                                 # the last `edge` of a cell ramps linearly into its neighbour
+                sa, sb = np.clip((a - i - (1. - edge)) / edge, 0., 1.), np.clip((b - j - (1. - edge)) / edge, 0., 1.)
+            else:
+                sa = sb = np.zeros_like(a)
+            t = tables[k]
+            val = ((1. - sa) * (1. - sb) * t[i % N, j % N] + sa * (1. - sb) * t[(i + 1) % N, j % N] +
+                   (1. - sa) * sb * t[i % N, (j + 1) % N] + sa * sb * t[(i + 1) % N, (j + 1) % N])
+            img = np.where(which == k, np.round(val), img).astype(np.uint8)
+        return img, s_best
+
+    left = np.zeros((n_frames, h, w), dtype=np.uint8)
+    right = np.zeros((n_frames, h, w), dtype=np.uint8)
+    depth = np.zeros((n_frames, h, w))
+    T_c_w = np.zeros((n_frames, 4, 4))
+    for f in range(n_frames):
+        xi = step * f + 0.3 * step * np.sin(0.7 * f)
+        T = SE3.exp(xi)
+        R, t = T.rot.as_matrix(), np.asarray(T.trans, dtype=float)
+        left[f], depth[f] = render(R, t)
+        right[f], _ = render(R, t - np.array([baseline, 0., 0.]))
+        T_c_w[f] = T.as_matrix()
+    return dict(left=left, right=right, depth=depth, cam=(cu, cv, fu, fv, baseline, w, h), T_c_w=T_c_w)
+
+
+def stereo_correspondence(seq, f0, f1, uv):
+    """True positions of the left pixels ``uv`` (n, 2; integer) of frame f0 of a stereo_sequence in the other images:
+    (n, 8) with the columns u1p v1p u2p v2p u1c v1c u2c v2c (1 left, 2 right; p frame f0, c frame f1)."""
+    cu, cv, fu, fv, b = seq['cam'][:5]
+    uv = np.asarray(uv)
+    ui, vi = uv[:, 0].astype(int), uv[:, 1].astype(int)
+    z = seq['depth'][f0][vi, ui]
+    P = np.stack([(ui - cu) * z / fu, (vi - cv) * z / fv, z], axis=1)
+    T = seq['T_c_w'][f1] @ np.linalg.inv(seq['T_c_w'][f0])
+    Q = P @ T[:3, :3].T + T[:3, 3]
+    u1c, v1c = fu * Q[:, 0] / Q[:, 2] + cu, fv * Q[:, 1] / Q[:, 2] + cv
+    return np.stack([ui, vi, ui - fu * b / z, vi, u1c, v1c, u1c - fu * b / Q[:, 2], v1c], axis=1).astype(float)
+
 # ---------------------------------------------------------------------------
 # user-defined residual blocks (no KIND: no typed device kernel), as a user of Problem writes them -- the blocks
 # Options.hybrid_blocks evaluates on the host beside the typed tables (tools/gen_hybrid_golden.py, tests)
