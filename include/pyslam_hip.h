@@ -277,6 +277,39 @@ int ps_solve(ps_problem* h, const ps_solve_options* options, double pcg_tol, int
              int32_t cap, int32_t* n_history, int32_t* iterations, double* last_dx_norm, int32_t* pcg_iters,
              double* pcg_relres, double* iter_ms);
 
+/* Adaptive Levenberg-Marquardt (Nielsen 1999; Madsen, Nielsen, Tingleff, algorithm 3.16).
+   ps_lm_iteration is ps_gn_iteration at the damping `lambda` whose tail also sums, on the device,
+       model_decrease = 0.5 h^T (lambda D h + g),   D = diag(J~^T J~) undamped,   (J~^T J~ + lambda D) h = g = -J~^T e~
+   for the step h it has just applied; the scalar arrives with the cost and ||dx|| in the block the call's ONE synchronisation
+   reads.  The caller forms rho = (cost before - cost after) / model_decrease and, to reject the step, restores a snapshot it took
+   in front of the call (ps_snapshot_params / ps_restore_params); the next call linearises again at the restored point.
+   linesearch must be non-zero (the cost returned is the cost AFTER the step).  For such a call the tail starts none of the next
+   iteration's work ahead, and the one-launch motion-only kernel and the lagged dense inverse are not used.  A hybrid handle
+   returns the typed blocks' cost, as ps_gn_iteration does; a landmark-sharded handle is an error. */
+int ps_lm_iteration(ps_problem* h, double lambda, double pcg_tol, int pcg_max_iters, int linesearch, double* cost_out,
+                    double* dx_norm_out, double* model_decrease_out, int* pcg_iters_out, double* pcg_relres_out);
+
+/* The adaptive loop in one call, as ps_solve is the default loop in one call: ps_reset_solver_state, the start cost in front of
+   the first iteration, then per iteration: snapshot, ps_lm_iteration at the current lambda, rho;
+       rho > 0: accept, lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2;    else: reject (the parameter tables are exchanged with
+       the snapshot's: no copy), lambda *= nu, nu *= 2;                   lambda clamped to [lambda_min, lambda_max];
+   a model_decrease that is not positive and finite is a rejection.  cost_history receives the cost after every iteration (the
+   unchanged previous cost after a rejection: it never increases).  Stops when iterations > max_iters, ||dx|| < min_update_norm,
+   cost < min_cost, an ACCEPTED step has cost >= min_cost_decrease * previous cost, or a rejection asks for lambda > lambda_max.
+   lambda0 <= 0 means 1e-3.  allow_nondecreasing_steps, max_nondecreasing_steps and lm_lambda are ignored; linesearch must be
+   non-zero.  Outputs as ps_solve, plus lm_rows (may be NULL): (lambda used, rho, accepted 1 / 0, model_decrease) per iteration,
+   4 * (max_iters + 1) doubles at most.  Returns 0 = solved, 1 = not offered for this handle (landmark-sharded; hybrid: the
+   caller loops with ps_lm_iteration and adds its blocks' cost) or `cap` too small, <0 = error.
+   sizeof(ps_lm_options) == 72. */
+typedef struct ps_lm_options {
+    int32_t max_iters, allow_nondecreasing_steps, max_nondecreasing_steps, linesearch;
+    double min_update_norm, min_cost, min_cost_decrease, lm_lambda;
+    double lambda0, lambda_min, lambda_max;
+} ps_lm_options;
+int ps_solve_lm(ps_problem* h, const ps_lm_options* options, double pcg_tol, int pcg_max_iters, double* cost_history,
+                int32_t cap, int32_t* n_history, int32_t* iterations, double* last_dx_norm, int32_t* pcg_iters,
+                double* pcg_relres, double* iter_ms, double* lm_rows);
+
 /* Second half of an iteration for a landmark-sharded (multi-GPU) caller, after
    ps_linearize -> all-reduce -> ps_solve_reduced: back-substitution, update, cost, ONE
    synchronisation.  Returns this shard's cost and ||dx_pose||^2, ||dx_point||^2 separately

@@ -50,6 +50,10 @@ class SolveOptions(C.Structure):
                 ('min_cost_decrease', C.c_double), ('lm_lambda', C.c_double)]
 
 
+class LmOptions(C.Structure):           # ps_lm_options: 72 bytes
+    _fields_ = SolveOptions._fields_ + [('lambda0', C.c_double), ('lambda_min', C.c_double), ('lambda_max', C.c_double)]
+
+
 class ProblemInfo(C.Structure):
     _fields_ = [
         ('dof', C.c_int32), ('num_poses', C.c_int32), ('num_reduced', C.c_int32),
@@ -112,6 +116,10 @@ SIGNATURES = {
                            C.POINTER(C.c_int32), C.POINTER(C.c_double), c_i32p, c_f64p, c_f64p]),
     'ps_gn_iteration': (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.c_int, c_f64p, c_f64p,
                                   C.POINTER(C.c_int), c_f64p]),
+    'ps_lm_iteration': (C.c_int, [H, C.c_double, C.c_double, C.c_int, C.c_int, c_f64p, c_f64p, c_f64p,
+                                  C.POINTER(C.c_int), c_f64p]),
+    'ps_solve_lm': (C.c_int, [H, C.POINTER(LmOptions), C.c_double, C.c_int, c_f64p, C.c_int32, C.POINTER(C.c_int32),
+                              C.POINTER(C.c_int32), C.POINTER(C.c_double), c_i32p, c_f64p, c_f64p, c_f64p]),
     'ps_gn_finish': (C.c_int, [H, C.c_int, c_f64p, c_f64p, c_f64p]),
     'ps_gn_solve_finish': (C.c_int, [H, C.c_double, C.c_int, C.c_int, c_f64p, c_f64p, c_f64p,
                                      C.POINTER(C.c_int), c_f64p]),

@@ -437,6 +437,10 @@ struct ps_problem {
     double* shard_buf = nullptr;    // {cost, ||dx_point||^2} of this landmark shard, for the caller's all-reduce
     bool shard_out = false;         // k_reduce3 writes cost / ||dx_point||^2 there instead of into scalars
     double *sq_part_l = nullptr, *sq_part_p = nullptr;   // per-workgroup partials of ||dx_point||^2, ||dx_pose||^2
+    // adaptive LM (ps_lm_iteration): the running call's tail also sums the model decrease (csrc/ps_k_lm.h); its partials
+    bool lm_md = false;
+    double *md_part_p = nullptr, *md_part_l = nullptr;
+    int nmd_p = 0;
     int nsq_l = 0 /* partials allocated */, nsq_l16 = 0 /* workgroups of the 16-lane back-substitution */, nsq_p = 0;
     // landmark pass / back-substitution with the lanes packed by observation (ps_k_packed.h): the first landmark of every wave's run
     // (lmw_nwaves + 1 entries; 0 waves: the 16-lane kernels -- a track longer than 16 observations, or an unobserved landmark)

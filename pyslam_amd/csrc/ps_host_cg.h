@@ -1168,29 +1168,56 @@ int cost_pass(ps_problem* h, int include_all, int scalar_slot) {
 // workgroups (= partials of ||dx_l||^2) of the back-substitution as it is launched now
 inline int nsq_l_now(const ps_problem* h) { return (h->lm_packed && h->lmw_nwaves > 0) ? cdiv(h->lmw_nwaves, 4) : h->nsq_l16; }
 
+// adaptive LM (ps_lm_iteration): the partials of the model decrease, allocated at the first such call
+int lm_md_ensure(ps_problem* h) {
+    if (h->md_part_p) return 0;
+    h->nmd_p = std::max(1, cdiv((long)h->nr * h->D + (long)h->nes * h->D, 256));
+    return (h->alloc(&h->md_part_p, (size_t)h->nmd_p) || h->alloc(&h->md_part_l, (size_t)std::max({h->nsq_l, h->nsq_l16, 1}))) ? -1 : 0;
+}
+
+// (h->lm_md: the MD instantiations, which also leave the landmark terms of the model decrease in md_part_l)
 int backsub(ps_problem* h, const int32_t* gate = nullptr, bool fuse_update = false, long long* hearly = nullptr, long long eseq = 0) {
     if (h->nv == 0) return 0;
     StageTimer t(h, PS_ST_BACKSUB);
+    const double lam_ratio = h->lin_lambda / (1.0 + h->lin_lambda);
     if (h->lm_packed && h->lmw_nwaves > 0) {                // lanes packed by observation (ps_k_packed.h)
         const int nbl = cdiv(h->lmw_nwaves, 4);               // (= nsq_l_now(h): the partials of ||dx_l||^2 k_reduce3 sums)
-        if (fuse_update)
-            hipLaunchKernelGGL(k_backsub_packed, dim3(nbl + h->nsq_p), dim3(256), 0, h->stream, h->lmw_nwaves, h->lmw_first, h->lm_ptr, h->Z,
-                               h->Cinv, h->cvec, h->x, h->dxl, h->sq_part_l, gate, nbl, h->lm_point, h->points, h->P, h->pose_rid, h->poses,
-                               h->sq_part_p, hearly, eseq);
+#define PS_BSP_LAUNCH(MD, ...) hipLaunchKernelGGL(k_backsub_packed<MD>, dim3(nbl + (fuse_update ? h->nsq_p : 0)), dim3(256), 0, h->stream, h->lmw_nwaves, \
+                               h->lmw_first, h->lm_ptr, h->Z, h->Cinv, h->cvec, h->x, h->dxl, h->sq_part_l, gate, nbl, __VA_ARGS__)
+        if (h->lm_md) {
+            if (fuse_update) PS_BSP_LAUNCH(true, h->lm_point, h->points, h->P, h->pose_rid, h->poses, h->sq_part_p, hearly, eseq, h->md_part_l, lam_ratio);
+            else PS_BSP_LAUNCH(true, (const int32_t*)nullptr, (double*)nullptr, 0, (const int32_t*)nullptr, (double*)nullptr, (double*)nullptr, hearly, eseq,
+                               h->md_part_l, lam_ratio);
+        } else if (fuse_update)
+            PS_BSP_LAUNCH(false, h->lm_point, h->points, h->P, h->pose_rid, h->poses, h->sq_part_p, hearly, eseq);
         else
-            hipLaunchKernelGGL(k_backsub_packed, dim3(nbl), dim3(256), 0, h->stream, h->lmw_nwaves, h->lmw_first, h->lm_ptr, h->Z,
-                               h->Cinv, h->cvec, h->x, h->dxl, h->sq_part_l, gate, nbl, (const int32_t*)nullptr, (double*)nullptr, 0,
-                               (const int32_t*)nullptr, (double*)nullptr, (double*)nullptr, hearly, eseq);
+            PS_BSP_LAUNCH(false, (const int32_t*)nullptr, (double*)nullptr, 0, (const int32_t*)nullptr, (double*)nullptr, (double*)nullptr, hearly, eseq);
+#undef PS_BSP_LAUNCH
         return 0;
     }
-    if (fuse_update)       // + full-step landmark update + SE(3) retraction of the poses in the same launch
-        hipLaunchKernelGGL(k_backsub, dim3(h->nsq_l16 + h->nsq_p), dim3(256), 0, h->stream, h->nv, h->lm_ptr, h->lobs,
-                           h->pose_rid, h->Z, h->Cinv, h->cvec, h->x, h->dxl, h->sq_part_l, gate,
-                           h->nsq_l16, h->lm_point, h->points, h->P, h->poses, h->sq_part_p, hearly, eseq);
+#define PS_BS_LAUNCH(MD, ...) hipLaunchKernelGGL(k_backsub<MD>, dim3(h->nsq_l16 + (fuse_update ? h->nsq_p : 0)), dim3(256), 0, h->stream, h->nv, h->lm_ptr, \
+                               h->lobs, h->pose_rid, h->Z, h->Cinv, h->cvec, h->x, h->dxl, h->sq_part_l, gate, h->nsq_l16, __VA_ARGS__)
+    if (h->lm_md) {
+        if (fuse_update) PS_BS_LAUNCH(true, h->lm_point, h->points, h->P, h->poses, h->sq_part_p, hearly, eseq, h->md_part_l, lam_ratio);
+        else PS_BS_LAUNCH(true, (const int32_t*)nullptr, (double*)nullptr, 0, (double*)nullptr, (double*)nullptr, hearly, eseq, h->md_part_l, lam_ratio);
+    } else if (fuse_update)       // + full-step landmark update + SE(3) retraction of the poses in the same launch
+        PS_BS_LAUNCH(false, h->lm_point, h->points, h->P, h->poses, h->sq_part_p, hearly, eseq);
     else
-        hipLaunchKernelGGL(k_backsub, dim3(h->nsq_l16), dim3(256), 0, h->stream, h->nv, h->lm_ptr, h->lobs,
-                           h->pose_rid, h->Z, h->Cinv, h->cvec, h->x, h->dxl, h->sq_part_l, gate,
-                           h->nsq_l16, (const int32_t*)nullptr, (double*)nullptr, 0, (double*)nullptr, (double*)nullptr, hearly, eseq);
+        PS_BS_LAUNCH(false, (const int32_t*)nullptr, (double*)nullptr, 0, (double*)nullptr, (double*)nullptr, hearly, eseq);
+#undef PS_BS_LAUNCH
+    return 0;
+}
+
+// the pose terms of the model decrease and its total into scalars[SC_MODELDEC] (behind the back-substitution, which left the
+// landmark terms; in front of k_reduce3, which publishes the slot with the cost and ||dx||)
+int lm_md_enqueue(ps_problem* h, const int32_t* gate) {
+    const int32_t* pip = h->npitems > 0 ? h->pitem_ptr : nullptr;
+#define PS_LMP_SUMS(DD) hipLaunchKernelGGL(k_lm_pose_sums<DD>, dim3(h->nmd_p), dim3(256), 0, h->stream, h->nr, h->x, h->g, pip, h->ppartial, h->nes,   \
+                               h->eslots, h->eptr, h->eitems, h->eslot_diag, h->brow_of, h->fscratch, h->lin_lambda, gate, h->md_part_p)
+    if (h->D == 6) PS_LMP_SUMS(6); else PS_LMP_SUMS(3);
+#undef PS_LMP_SUMS
+    hipLaunchKernelGGL(k_lm_total, dim3(1), dim3(256), 0, h->stream, h->nmd_p, h->md_part_p, h->nv > 0 ? nsq_l_now(h) : 0, h->md_part_l, gate,
+                       h->scalars + SC_MODELDEC);
     return 0;
 }
 
@@ -1287,7 +1314,9 @@ int gn_tail(ps_problem* h, int linesearch, const int32_t* gate, bool publish = f
     const long long eseq = hearly ? ++h->early_seq : 0;
     h->early_armed = hearly != nullptr;
     const bool stamp_in_backsub = h->nv > 0;
+    if (h->lm_md && lm_md_ensure(h)) return -1;
     if (backsub(h, gate, fused, stamp_in_backsub ? hearly : nullptr, eseq)) return -1;
+    if (h->lm_md && lm_md_enqueue(h, gate)) return -1;       // (reads x, g, the pose partials and the factor rows: nothing below writes them)
     int ncost = 0;
     if (!linesearch) { StageTimer t(h, PS_ST_COST); ncost = cost_partials_pass(h, 0, gate); }
     if (!fused && apply_update(h, 1.0, gate, true, stamp_in_backsub ? nullptr : hearly, eseq)) return -1;

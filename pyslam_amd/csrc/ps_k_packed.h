@@ -240,6 +240,9 @@ __global__ __launch_bounds__(256) void k_cost_packed(
 }
 
 // back-substitution, the same packing: one Z row per lane, the landmark's three sums by its head lane
+// MD (adaptive LM, ps_lm_iteration): the head lane also forms its landmark's terms of the model decrease (lm_landmark_terms,
+// ps_k_lm.h), one partial per workgroup into md_part; false: the kernel as it was, the two last arguments unused
+template <bool MD>
 __global__ __launch_bounds__(256) void k_backsub_packed(
     int nwaves, const int32_t* __restrict__ lmw_first, const int32_t* __restrict__ lm_ptr,
     const double* __restrict__ Z, const double* __restrict__ Cinv, const double* __restrict__ cvec,
@@ -249,7 +252,7 @@ __global__ __launch_bounds__(256) void k_backsub_packed(
     // fused full-step update (NULL points: back-substitution only); workgroups >= nblk_l retract the SE(3) poses (as k_backsub)
     int nblk_l, const int32_t* __restrict__ lm_point, double* __restrict__ points,
     int P, const int32_t* __restrict__ pose_rid, double* __restrict__ poses, double* __restrict__ sq_part_p,
-    long long* __restrict__ hearly, long long eseq)
+    long long* __restrict__ hearly, long long eseq, double* __restrict__ md_part = nullptr, double lam_ratio = 0.0)
 {
     __shared__ double lds[16];
     __shared__ double sm3[4][64 * 3];
@@ -273,7 +276,7 @@ __global__ __launch_bounds__(256) void k_backsub_packed(
         return;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, gw = blockIdx.x * 4 + wv;
-    double sq = 0.0;
+    double sq = 0.0, md = 0.0;
     const int v0 = gw < nwaves ? lmw_first[gw] : 0, v1 = gw < nwaves ? lmw_first[gw + 1] : 0;
     if (v1 > v0) {                                            // (wave-uniform)
         const LmwSeg sg = lmw_segment(v0, v1, lm_ptr, lane, flags[wv]);
@@ -302,13 +305,14 @@ __global__ __launch_bounds__(256) void k_backsub_packed(
             double b0 = 0.0, b1 = 0.0, b2 = 0.0;
             for (int l = lane; l < sg.lane1; ++l) { b0 += sm[3 * l]; b1 += sm[3 * l + 1]; b2 += sm[3 * l + 2]; }
             const size_t v = (size_t)sg.v;
-            b0 += cvec[3 * v]; b1 += cvec[3 * v + 1]; b2 += cvec[3 * v + 2];
             const double* m = Cinv + 6 * v;        // dx = M^T a
+            b0 += cvec[3 * v]; b1 += cvec[3 * v + 1]; b2 += cvec[3 * v + 2];
             const double d0 = m[0] * b0 + m[1] * b1 + m[3] * b2;
             const double d1 = m[2] * b1 + m[4] * b2;
             const double d2 = m[5] * b2;
             dxl[3 * v] = d0; dxl[3 * v + 1] = d1; dxl[3 * v + 2] = d2;
             sq = d0 * d0 + d1 * d1 + d2 * d2;
+            if (MD) md = lm_landmark_terms(m, cvec + 3 * v, d0, d1, d2, lam_ratio);
             if (points) {
                 double* pt = points + 3 * (size_t)lm_point[v];
                 pt[0] += d0; pt[1] += d1; pt[2] += d2;
@@ -317,4 +321,8 @@ __global__ __launch_bounds__(256) void k_backsub_packed(
     }
     sq = block_sum(sq, lds);
     if (threadIdx.x == 0) sq_part[blockIdx.x] = sq;
+    if (MD) {
+        md = block_sum(md, lds);
+        if (threadIdx.x == 0) md_part[blockIdx.x] = md;
+    }
 }

@@ -366,6 +366,8 @@ __global__ __launch_bounds__(64) void k_cov_rhs(
     }
 }
 
+// MD: as k_backsub_packed's (ps_k_packed.h) -- the landmark terms of the adaptive LM's model decrease, one partial per workgroup
+template <bool MD>
 __global__ __launch_bounds__(256) void k_backsub(
     int nv, const int32_t* __restrict__ lm_ptr, const LObs* __restrict__ lobs,
     const int32_t* __restrict__ pose_rid, const double* __restrict__ Z,
@@ -379,7 +381,7 @@ __global__ __launch_bounds__(256) void k_backsub(
     int P, double* __restrict__ poses, double* __restrict__ sq_part_p,
     // early word (pinned host memory; NULL: none): has the reduced solve in front of this tail converged?  +seq / -seq.  The
     // host, which is only waiting for the end of the iteration, may enqueue the NEXT linearisation behind the tail on it
-    long long* __restrict__ hearly, long long eseq)
+    long long* __restrict__ hearly, long long eseq, double* __restrict__ md_part = nullptr, double lam_ratio = 0.0)
 {
     __shared__ double lds[16];
     const bool closed = gate && gate[ST_PCG_DONE] != 1;
@@ -428,7 +430,7 @@ __global__ __launch_bounds__(256) void k_backsub(
         }
     }
     a0 = group16_sum(a0); a1 = group16_sum(a1); a2 = group16_sum(a2);
-    double sq = 0.0;
+    double sq = 0.0, md = 0.0;
     if (live && sub == 0) {
         a0 += cvec[3 * (size_t)v]; a1 += cvec[3 * (size_t)v + 1]; a2 += cvec[3 * (size_t)v + 2];
         const double* m = Cinv + 6 * (size_t)v;    // dx = M^T a
@@ -437,6 +439,7 @@ __global__ __launch_bounds__(256) void k_backsub(
         const double d2 = m[5] * a2;
         dxl[3 * (size_t)v] = d0; dxl[3 * (size_t)v + 1] = d1; dxl[3 * (size_t)v + 2] = d2;
         sq = d0 * d0 + d1 * d1 + d2 * d2;
+        if (MD) md = lm_landmark_terms(m, cvec + 3 * (size_t)v, d0, d1, d2, lam_ratio);
         if (points) {
             double* pt = points + 3 * (size_t)lm_point[v];
             pt[0] += d0; pt[1] += d1; pt[2] += d2;
@@ -444,6 +447,10 @@ __global__ __launch_bounds__(256) void k_backsub(
     }
     sq = block_sum(sq, lds);
     if (threadIdx.x == 0) sq_part[blockIdx.x] = sq;
+    if (MD) {
+        md = block_sum(md, lds);
+        if (threadIdx.x == 0) md_part[blockIdx.x] = md;
+    }
 }
 
 template <int D>

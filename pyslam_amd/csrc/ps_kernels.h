@@ -13,6 +13,7 @@
 //                        <= 90 unknowns: k_bsr_to_dense + k_coarse_chol + k_direct_apply;
 //                        classic k_pcg_* (two launches per iteration) kept as an independent variant
 //   k_backsub            16 lanes / landmark  : dx_l = C^-T (c_l - sum Z_i^T dx_p) (+ fused update of points, poses)
+//   k_lm_pose_sums / k_lm_total (ps_k_lm.h)   : adaptive LM's model decrease 0.5 h^T (lambda D h + g); landmark terms by k_backsub*<true>
 //   k_cost_*, k_reduce3  robust cost, final reductions, results published to pinned host memory
 //   k_motion_only_iteration  WG / pose        : problems without landmarks / factors: the whole iteration
 // Every reduction has a fixed order: results are bitwise reproducible run to run.
@@ -36,7 +37,7 @@ struct FactorGroup { double S[36]; int32_t loss_id; int32_t pad; double loss_k; 
 // status words
 enum { ST_LM_FAIL = 0, ST_DIAG_FAIL = 1, ST_PCG_DONE = 2, ST_PCG_ITERS = 3, ST_PERSIST_FAIL = 4 /* k_cg_persist: an exchange timed out */, ST_NWORDS = 8 };
 // scalar slots
-enum { SC_COST = 0, SC_DXP2 = 1, SC_LINCOST = 2, SC_RR0 = 3, SC_RRFINAL = 4, SC_THRESH = 5, SC_DXL2 = 6, SC_STARTCOST = 7, SC_NWORDS = 8 };
+enum { SC_COST = 0, SC_DXP2 = 1, SC_LINCOST = 2, SC_RR0 = 3, SC_RRFINAL = 4, SC_THRESH = 5, SC_DXL2 = 6, SC_STARTCOST = 7, SC_MODELDEC = 8, SC_NWORDS = 9 };
 
 // Wave-wide sum with DPP row operations instead of ds_bpermute shuffles (each __shfl_xor of a
 // double is two LDS-crossbar permutes, ~100+ cycles of latency; a DPP add is a plain VALU op).
@@ -101,5 +102,6 @@ PS_DEV void block_sum2(double& a, double& b, double* lds /* >= 32 doubles */) {
 #include "ps_k_coarse.h"
 #include "ps_k_band.h"
 #include "ps_k_bandpart.h"
+#include "ps_k_lm.h"
 #include "ps_k_tail.h"
 #include "ps_k_packed.h"

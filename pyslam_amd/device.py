@@ -187,6 +187,44 @@ class DeviceProblem:
         k = iters.value
         return hist[:n.value].tolist(), [(int(a), float(b)) for a, b in zip(its[:k], rel[:k])], ms[:k].tolist()
 
+    def lm_iteration(self, lm_lambda, pcg_tol=1e-12, pcg_max_iters=1000, linesearch=True):
+        """gn_iteration at the damping lm_lambda that also returns the decrease its quadratic model predicted (ps_lm_iteration).
+        -> (cost, ||dx||, model_decrease, pcg iterations, pcg relative residual); parameters are updated."""
+        if self.host is not None:
+            self._upload_host_rows()
+        cost, nrm, md, rel, it = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_int()
+        nat.check(self._lib.ps_lm_iteration(self._h, lm_lambda, pcg_tol or 0., pcg_max_iters, int(linesearch),
+                                            C.byref(cost), C.byref(nrm), C.byref(md), C.byref(it), C.byref(rel)))
+        c = cost.value
+        if self.host is not None:
+            self._hposes = self._read_poses()
+            c += self.host.cost(self._hposes, True)
+        return c, nrm.value, md.value, it.value, rel.value
+
+    def solve_lm_loop(self, opt):
+        """The adaptive LM loop of Problem.solve in one C call (ps_solve_lm).  -> (cost history, [(pcg iterations, relative
+        residual)], [ms per iteration call], lm rows (n, 4)) or None when the core does not offer it for this handle."""
+        from pyslam_amd.problem import lm_options
+        o = nat.LmOptions()
+        o.max_iters, o.linesearch = int(opt.max_iters), int(opt.linesearch_max_iters > 0)
+        o.allow_nondecreasing_steps, o.max_nondecreasing_steps = 0, 0
+        o.min_update_norm, o.min_cost, o.min_cost_decrease = float(opt.min_update_norm), float(opt.min_cost), float(opt.min_cost_decrease)
+        o.lm_lambda = 0.
+        o.lambda0, o.lambda_min, o.lambda_max = lm_options(opt)
+        cap = o.max_iters + 2
+        if cap < 2 or cap > 100000 or self.host is not None:
+            return None
+        hist, rel, ms, its, rows = np.zeros(cap), np.zeros(cap), np.zeros(cap), np.zeros(cap, dtype=np.int32), np.zeros((cap, 4))
+        n, iters, dxn = C.c_int32(), C.c_int32(), C.c_double()
+        rc = self._lib.ps_solve_lm(self._h, C.byref(o), float(getattr(opt, 'pcg_tol', None) or 0.), int(getattr(opt, 'pcg_max_iters', 2000)),
+                                   nat.f64p(hist), cap, C.byref(n), C.byref(iters), C.byref(dxn), nat.i32p(its), nat.f64p(rel),
+                                   nat.f64p(ms), nat.f64p(rows))
+        if rc == 1:
+            return None
+        nat.check(rc)
+        k = iters.value
+        return (hist[:n.value].tolist(), [(int(a), float(b)) for a, b in zip(its[:k], rel[:k])], ms[:k].tolist(), rows[:k].copy())
+
     def gn_finish(self, linesearch=True):
         """-> (shard cost, ||dx_pose||^2, ||dx_point||^2); parameters are updated."""
         c, a, b = C.c_double(), C.c_double(), C.c_double()

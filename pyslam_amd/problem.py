@@ -75,6 +75,38 @@ class Options:
         # blocks on a landmark or a non-pose parameter, photometric problems, the sharded route, mixed SE(2)/SE(3) problems --
         # those take the generic path as with False.  False (default): every problem routes as before, bit for bit.
         self.hybrid_blocks = False
+        # True: solve() runs the adaptive Levenberg-Marquardt loop (Nielsen's rule) instead of the reference's:
+        # every step is judged by its gain ratio rho = (cost before - cost after) / (decrease the quadratic model predicted), a
+        # step with rho <= 0 is taken back and retried under a larger damping, and lambda follows rho between lm_lambda_min and
+        # lm_lambda_max.  lm_lambda is then the STARTING value (0, its default: 1e-3).  The cost history never increases;
+        # allow_nondecreasing_steps / max_nondecreasing_steps are ignored; linesearch_max_iters must be > 0 (rho needs the cost
+        # after the step).  Single-GPU typed and hybrid routes only: Options.devices and the generic host path raise ValueError.
+        # False (default): nothing changes, bit for bit.
+        self.lm_adaptive = False
+        self.lm_lambda_min = 1e-12
+        self.lm_lambda_max = 1e12
+
+
+def lm_options(opt):
+    """(lambda0, lambda_min, lambda_max) of an adaptive solve, lambda0 clamped as the loop clamps every lambda."""
+    lo, hi = float(getattr(opt, 'lm_lambda_min', 1e-12)), float(getattr(opt, 'lm_lambda_max', 1e12))
+    if not (0. < lo <= hi):
+        raise ValueError('Options.lm_adaptive: 0 < lm_lambda_min <= lm_lambda_max expected, got {!r}, {!r}'.format(lo, hi))
+    lam = float(getattr(opt, 'lm_lambda', 0.) or 0.)
+    return min(max(lam if lam > 0. else 1e-3, lo), hi), lo, hi
+
+
+def check_lm_route(opt, what=None):
+    """Options.lm_adaptive on a route that does not offer it is an error, never the fixed-lambda loop in silence."""
+    if not getattr(opt, 'lm_adaptive', False):
+        return
+    if what is not None:
+        raise ValueError('Options.lm_adaptive is not offered on {} (single-GPU typed and hybrid routes only)'.format(what))
+    if getattr(opt, 'devices', None) not in (None, 1, 'single'):
+        raise ValueError('Options.lm_adaptive is not offered on the landmark-sharded route (Options.devices = {!r})'.format(opt.devices))
+    if not opt.linesearch_max_iters > 0:
+        raise ValueError('Options.lm_adaptive needs the cost after the step: Options.linesearch_max_iters must be > 0')
+    lm_options(opt)
 
 
 def solve_horizon(opt, iteration, nondecreasing_steps_taken):
@@ -119,6 +151,8 @@ def device_solve(dev, opt, use_core_loop=True, call_ms=None):
 
 def _device_solve_loop(dev, opt, use_core_loop, call_ms):
     """device_solve's body (the wrapper reports a one-launch CG that timed out)."""
+    if getattr(opt, 'lm_adaptive', False):
+        return _lm_solve_loop(dev, opt, use_core_loop, call_ms)
     loop = getattr(dev, 'solve_loop', None) if use_core_loop else None
     if loop is not None:
         out = loop(opt)
@@ -183,6 +217,65 @@ def _reference_loop(dev, opt, expect, horizon, cost, lam, pcg_tol, pcg_max, line
         else:
             done_optimization = done_optimization or cost >= opt.min_cost_decrease * prev_cost
     return history, stats
+
+
+def _lm_solve_loop(dev, opt, use_core_loop, call_ms):
+    """Options.lm_adaptive: the core's loop (ps_solve_lm) where the device offers it, else the same statements here on
+    ps_lm_iteration (hybrid handles: the host blocks' cost is part of every cost below).  The per-iteration rows
+    (lambda used, rho, accepted, model_decrease) are left on the device object as `lm_history`."""
+    check_lm_route(opt)
+    if not hasattr(dev, 'lm_iteration'):
+        check_lm_route(opt, type(dev).__name__)
+    loop = getattr(dev, 'solve_lm_loop', None) if use_core_loop else None
+    if loop is not None:
+        out = loop(opt)
+        if out is not None:
+            if call_ms is not None:
+                call_ms.extend(out[2])
+            dev.lm_history = out[3]
+            return out[0], out[1]
+    dev.reset_solver_state()
+    history, stats, rows = _lm_loop(dev, opt, dev.eval_cost(True), call_ms)
+    dev.lm_history = np.array(rows, dtype=np.float64).reshape(-1, 4)
+    return history, stats
+
+
+def _lm_loop(dev, opt, cost, call_ms):
+    """Nielsen's damping rule around whole iterations (csrc/ps_abi_solver.h: ps_solve_lm is this, statement for statement)."""
+    lam, lam_min, lam_max = lm_options(opt)
+    nu = 2.
+    pcg_tol, pcg_max = (getattr(opt, 'pcg_tol', None) or 0.), getattr(opt, 'pcg_max_iters', 2000)
+    history, stats, rows = [cost], [], []
+    iters = 0
+    done = False
+    while not done:
+        iters += 1
+        prev_cost = cost
+        dev.snapshot()
+        t0 = time.perf_counter()
+        new_cost, dx_norm, md, its, rel = dev.lm_iteration(lam, pcg_tol, pcg_max, True)
+        if call_ms is not None:
+            call_ms.append((time.perf_counter() - t0) * 1e3)
+        stats.append((its, rel))
+        ok = np.isfinite(md) and md > 0. and np.isfinite(new_cost)
+        rho = (prev_cost - new_cost) / md if ok else -1.
+        used, raw = lam, lam * nu
+        accepted = rho > 0.
+        if accepted:
+            q = 2. * rho - 1.
+            cost, lam, nu = new_cost, lam * max(1. / 3., 1. - q * q * q), 2.
+        else:
+            lam, nu = raw, nu * 2.
+            dev.restore()
+        lam = min(max(lam, lam_min), lam_max)
+        rows.append((used, rho, 1. if accepted else 0., md))
+        history.append(cost)
+        done = iters > opt.max_iters or dx_norm < opt.min_update_norm or cost < opt.min_cost
+        if accepted:
+            done = done or cost >= opt.min_cost_decrease * prev_cost
+        else:
+            done = done or raw > lam_max
+    return history, stats, rows
 
 
 def solve_tables(lp, options=None, stream=None, device=None):
@@ -454,16 +547,21 @@ class Problem:
         # (reference problem.py:132 rebuilds the partition here; the device path below never reads it -- it is rebuilt on first
         #  use instead: one Python statement per parameter, 0.15 s for the 500 000 landmarks of C4)
         self._partition = None
+        opt = self.options
+        lm = bool(getattr(opt, 'lm_adaptive', False))
+        check_lm_route(opt)
         try:
             dev = self._get_device()
         except NotLowerable:
             dev = None
-        opt = self.options
+            check_lm_route(opt, 'the generic host path (a block without a typed kernel; see Options.hybrid_blocks)')
         self.solver_stats = []
+        self.lm_history = None
 
         # a single pose against constant landmarks (the per-frame Problem of pipelines/sparse.py): this whole loop runs on
         # the device in one launch; identical decisions, identical cost history
-        fused = getattr(dev, 'motion_only_solve', None) if dev is not None and opt.fused_solve_loop else None
+        # (not under lm_adaptive: the one-launch kernel has no step rejection, a one-pose problem takes the general loop)
+        fused = getattr(dev, 'motion_only_solve', None) if dev is not None and opt.fused_solve_loop and not lm else None
         if fused is not None:
             out = fused(opt, opt.linesearch_max_iters > 0)
             if out is not None:
@@ -474,6 +572,8 @@ class Problem:
 
         if dev is not None:
             self._cost_history, self.solver_stats = device_solve(dev, opt)
+            if lm:
+                self.lm_history = dev.lm_history
             self._write_back(dev)
             return self.param_dict
 
@@ -813,16 +913,19 @@ class Problem:
     def summary(self, format='brief'):
         if not self._cost_history:
             raise ValueError('solve has not yet been called')
+        lm = getattr(self, 'lm_history', None)
+        lm_line = '' if lm is None else '\nLM steps: {} accepted, {} rejected'.format(
+            int(np.sum(lm[:, 2] != 0.)), int(np.sum(lm[:, 2] == 0.)))
         if format == 'brief':
             return 'Iterations: {:3} | Cost: {:12e} --> {:12e}'.format(
-                len(self._cost_history), self._cost_history[0], self._cost_history[-1])
+                len(self._cost_history), self._cost_history[0], self._cost_history[-1]) + lm_line
         if format == 'full':
             header = '{:>5s} | {:>12s} --> {:>12s} | {:>10s}\n'.format(
                 'Iter', 'Initial cost', 'Final cost', 'Rel change')
             lines = [header, '-' * len(header) + '\n']
             for i, (ic, fc) in enumerate(zip(self._cost_history[:-1], self._cost_history[1:])):
                 lines.append('{:5} | {:12e} --> {:12e} | {:+10f}\n'.format(i, ic, fc, (fc - ic) / ic))
-            return ''.join(lines)
+            return ''.join(lines) + (lm_line[1:] + '\n' if lm_line else '')
         raise ValueError('Invalid summary format \'{}\'.'.format(format) +
                          'Valid formats are \'brief\' and \'full\'')
 
