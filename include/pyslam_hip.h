@@ -53,7 +53,7 @@ typedef struct ps_problem_desc {
     const int32_t* obs_point;
     const double*  obs_uvd;      /* (num_obs, 3)                                              */
     const int32_t* obs_grp;      /* row of obs_groups                                         */
-    int32_t num_cams;       const double* cams;        /* (num_cams, 5) cu cv fu fv b  (b = -1: RGB-D camera, third coordinate is z) */
+    int32_t num_cams;       const double* cams;        /* (num_cams, 5) cu cv fu fv b  (b >= 0: stereo; b = -1: RGB-D camera, third coordinate is z; b = -2: monocular (u, v), third coordinate 0 and third stiffness row / column 0; any other negative b is an error) */
     int32_t num_stiff3;     const double* stiff3;      /* (num_stiff3, 9) 3x3 row-major       */
     int32_t num_obs_groups; const double* obs_groups;  /* (n, 4) cam, stiff, loss id, loss k  */
 
@@ -389,6 +389,22 @@ int ps_covariance_pose_blocks(ps_problem* h, int64_t n, const int32_t* a, const 
    current Sigma_pp, a kind other than 0 / 1, an index out of range, landmarks on a problem whose poses are not SE(3). */
 int ps_covariance_cross_blocks(ps_problem* h, int64_t n, const int32_t* kind_a, const int32_t* a,
                                const int32_t* kind_b, const int32_t* b, double* out /* (n, 36) */);
+
+/* Multi-view triangulation of variable landmarks from their observations and the CURRENT poses (constant poses included);
+   Problem.triangulate_landmarks, pyslam_amd.triangulate_tables.  vids: n variable-landmark indices (vid, the caller's order),
+   or NULL for every variable landmark (n ignored; results in vid order).  Per landmark, in the fixed slot order of the
+   landmark-sorted tables (bit-identical from call to call):
+     1. linear start: with x_n = (u - cu) / fu, y_n = (v - cv) / fv and the pose (R | t), rows r1 r2 r3, every observation gives
+        (x_n r3 - r1) p = -(x_n t3 - t1) and (y_n r3 - r2) p = -(y_n t3 - t2); a stereo (z = fu b / d) or RGB-D (z = d) observation
+        also r3 p = z - t3; the 3 x 3 normal equations are solved by Cholesky;
+     2. refine_iters Gauss-Newton steps on the landmark's own robust reprojection cost (the iteration's evaluator: camera
+        types, stiffness, IRLS weights), poses held; a step that does not lower the cost is not taken and ends the iteration;
+     3. status 0 ok | 1 fewer than two observations and none bearing depth | 2 no depth and the largest angle between two
+        viewing rays below min_parallax_deg, or a 3 x 3 system that is not positive definite | 3 behind one of its cameras.
+   points_out (n, 3): the new point, or the old one where the status is not 0; status_out (n).  write_back != 0: points
+   with status 0 replace the handle's (as ps_set_params would).  One launch, one synchronisation. */
+int ps_triangulate(ps_problem* h, int64_t n, const int32_t* vids /* (n) or NULL */, int refine_iters, double min_parallax_deg,
+                   int write_back, double* points_out /* (n, 3) or NULL */, int32_t* status_out /* (n) or NULL */);
 
 /* Parity / debug taps (device -> host). */
 int ps_get_reduced_system(ps_problem* h, int32_t* row_ptr, int32_t* col_idx,

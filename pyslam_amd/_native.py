@@ -134,6 +134,7 @@ SIGNATURES = {
     'ps_covariance_marginals': (C.c_int, [H, c_f64p, c_f64p]),
     'ps_covariance_pose_blocks': (C.c_int, [H, C.c_int64, c_i32p, c_i32p, c_f64p]),
     'ps_covariance_cross_blocks': (C.c_int, [H, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p]),
+    'ps_triangulate': (C.c_int, [H, C.c_int64, c_i32p, C.c_int, C.c_double, C.c_int, c_f64p, c_i32p]),
     'ps_get_reduced_system': (C.c_int, [H, c_i32p, c_i32p, c_f64p, c_f64p]),
     'ps_get_landmark_factors': (C.c_int, [H, c_f64p, c_f64p]),
     'ps_debug_reproj_blocks': (C.c_int, [H, c_f64p, c_f64p, c_f64p]),

@@ -53,7 +53,7 @@ int ps_warm_up(void) {
         PS_TOUCH(k_pcg_spmv<6>); PS_TOUCH(k_pcg_spmv<3>); PS_TOUCH(k_ldi_init); PS_TOUCH(k_ldi_update); PS_TOUCH(k_ldi_gemm); PS_TOUCH(k_ldi_mirror);
         PS_TOUCH(k_ldi_ritz); PS_TOUCH(k_ldi_seed_prep); PS_TOUCH(k_ldi_fro_total); PS_TOUCH(k_ldi_pad_identity);
         PS_TOUCH(k_ldi_scaled_dense<6>); PS_TOUCH(k_ldi_sym_unscale<6>); PS_TOUCH(k_ldi_scaled_dense<3>); PS_TOUCH(k_ldi_sym_unscale<3>);
-        PS_TOUCH(k_shard_pack<6>); PS_TOUCH(k_shard_unpack<6>); PS_TOUCH(k_publish); PS_TOUCH(k_cov_rhs);
+        PS_TOUCH(k_shard_pack<6>); PS_TOUCH(k_shard_unpack<6>); PS_TOUCH(k_publish); PS_TOUCH(k_cov_rhs); PS_TOUCH(k_triangulate<false>);
         PS_TOUCH(k_scale_blocks<3>); PS_TOUCH(k_rows_setup<3>); PS_TOUCH(k_coarse_rowsums<3>); PS_TOUCH(k_coarse_matrix<3>);
         PS_TOUCH(k_coarse_chol<3, true>); PS_TOUCH(k_coarse_border<3>); PS_TOUCH(k_coarse_mreduce<3>); PS_TOUCH(k_coarse_xbuild<3>);
         PS_TOUCH(k_coarse_recover<3>); PS_TOUCH(k_cg_fused_lds<3, 8>); PS_TOUCH(k_cg_unscale<3>);
@@ -111,6 +111,7 @@ int ps_problem_destroy(ps_problem* h) {
     if (h->ldi_stream) hipStreamSynchronize(h->ldi_stream);
     cov_release(h);
     if (h->cov_xbuf) hipFree(h->cov_xbuf);
+    if (h->tri_buf) hipFree(h->tri_buf);
     for (void* p : h->allocs) hipFree(p);
     h->arena_release();            // arena block, its pinned mirror and the pinned result words go back to the process-wide pool
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
@@ -271,7 +272,9 @@ static int problem_create(const ps_problem_desc* d_in, const ps_host_rows_desc* 
             if (cam < 0 || cam >= d->num_cams || st < 0 || st >= d->num_stiff3) return fail("obs group index out of range");
             const double* c = d->cams + 5 * cam;
             o.cu = c[0]; o.cv = c[1]; o.fu = c[2]; o.fv = c[3];
-            o.cam_type = c[4] < 0.0 ? 1 : 0;            // cams row: baseline b >= 0 = stereo, b = -1 = RGB-D
+            // cams row: baseline b >= 0 = stereo, b = -1 = RGB-D, b = -2 = monocular (u, v); any other negative value is an error
+            if (c[4] < 0.0 && c[4] != -1.0 && c[4] != -2.0) return fail("cams row " + std::to_string(cam) + ": b must be >= 0 (stereo), -1 (RGB-D) or -2 (monocular)");
+            o.cam_type = c[4] == -2.0 ? 2 : (c[4] < 0.0 ? 1 : 0);
             o.b = o.cam_type ? 0.0 : c[4];
             for (int k = 0; k < 9; ++k) o.S[k] = with_s ? d->stiff3[9 * st + k] : (k % 4 == 0 ? 1.0 : 0.0);
             o.loss_id = (int)row[2]; o.loss_k = row[3];

@@ -29,6 +29,7 @@
 #include "ps_k_feat.h"
 #include "ps_sparse.h"
 #include "ps_k_covmarg.h"
+#include "ps_k_triang.h"
 
 namespace {
 
@@ -404,6 +405,8 @@ struct ps_problem {
     double* cov_buf = nullptr;
     double* cov_xbuf = nullptr;     // ps_covariance_cross_blocks' fixed pair buffer: allocated by its first call, freed by destroy
     long long cov_epoch = 0, cov_sigma_epoch = -1;
+    double* tri_buf = nullptr;      // ps_triangulate's result block (tri_cap doubles): grown by a call that needs more, freed by destroy
+    size_t tri_cap = 0;
     int ell_wf = 0, ell_wc = 0;     // two-class ELL widths of the CG matrix (0 = CSR)
     // scalars
     double *cost_partials = nullptr, *scalars = nullptr, *h_scalars = nullptr;
@@ -665,6 +668,7 @@ extern "C" {
 #include "ps_abi_problem.h"
 #include "ps_abi_solver.h"
 #include "ps_abi_cov.h"
+#include "ps_abi_triang.h"
 #include "ps_abi_small.h"
 #include "ps_abi_dense.h"
 #include "ps_abi_feat.h"

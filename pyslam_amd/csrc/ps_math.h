@@ -316,7 +316,10 @@ template <> struct PoseOps<3> {
 // followed by element-wise IRLS scaling (pyslam/problem.py:351-360).
 // ---------------------------------------------------------------------------
 // cam_type: 0 = stereo (u, v, d = fu b / z), 1 = RGB-D (u, v, z)  -- reference
-// pyslam/sensors/stereo_camera.py:100-134 and rgbd_camera.py:96-135
+// pyslam/sensors/stereo_camera.py:100-134 and rgbd_camera.py:96-135; 2 = monocular pinhole (u, v): the third row is carried
+// as zeros -- e2 = 0 exactly and j22 = 0, the stiffness has a zero third row and column (lowering.py), so r[2] = 0, rho(0) = 0
+// for every loss and the row adds nothing to the cost, to J~^T J~ or to J~^T r.  Its IRLS scale is pinned to 1: the L1 weight
+// at 0 is NaN (losses.py:30-33), and NaN * 0 would poison the row.
 struct ObsGroup { double cu, cv, fu, fv, b; double S[9]; int loss_id; int cam_type; double loss_k; };
 
 struct ReprojEval {
@@ -333,7 +336,7 @@ template <bool WITH_JP, bool WITH_JL>
 PS_DEV void reproj_eval_s(const Se3& T, const double* __restrict__ pw, const double* __restrict__ uvd,
                           const ObsGroup& g, const double* __restrict__ Sv, ReprojEval& o) {
     double pc[3], rr[3], iz;
-    const bool rgbd = g.cam_type == 1;
+    const bool rgbd = g.cam_type == 1, mono = g.cam_type == 2;
     {   // the chain the cost depends on: explicit fused multiply-adds, no contraction left to the compiler (see ps_loss_rho)
 #pragma clang fp contract(off)
 #pragma unroll
@@ -342,7 +345,7 @@ PS_DEV void reproj_eval_s(const Se3& T, const double* __restrict__ pw, const dou
         iz = 1.0 / pc[2];
         const double e0 = __builtin_fma(g.fu * pc[0], iz, g.cu - uvd[0]);
         const double e1 = __builtin_fma(g.fv * pc[1], iz, g.cv - uvd[1]);
-        const double e2 = rgbd ? pc[2] - uvd[2] : __builtin_fma(g.fu * g.b, iz, -uvd[2]);
+        const double e2 = mono ? 0.0 : (rgbd ? pc[2] - uvd[2] : __builtin_fma(g.fu * g.b, iz, -uvd[2]));
 #pragma unroll
         for (int i = 0; i < 3; ++i) rr[i] = __builtin_fma(Sv[3 * i + 2], e2, __builtin_fma(Sv[3 * i + 1], e1, Sv[3 * i] * e0));
         o.cost = 0.0;
@@ -354,14 +357,14 @@ PS_DEV void reproj_eval_s(const Se3& T, const double* __restrict__ pw, const dou
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const double ri = rr[i];
-        s[i] = ps_loss_sqrt_weight(g.loss_id, g.loss_k, ri);
+        s[i] = (i == 2 && mono) ? 1.0 : ps_loss_sqrt_weight(g.loss_id, g.loss_k, ri);
         o.r[i] = s[i] * ri;
     }
     if (!WITH_JP && !WITH_JL) return;
     const double iz2 = iz * iz;
     const double j00 = g.fu * iz, j02 = -g.fu * pc[0] * iz2;
     const double j11 = g.fv * iz, j12 = -g.fv * pc[1] * iz2;
-    const double j22 = rgbd ? 1.0 : -g.fu * g.b * iz2;
+    const double j22 = mono ? 0.0 : (rgbd ? 1.0 : -g.fu * g.b * iz2);
     double SJ[9];                       // diag(s) * S * Jc
 #pragma unroll
     for (int i = 0; i < 3; ++i) {

@@ -360,6 +360,21 @@ class DeviceProblem:
         nat.check(self._lib.ps_covariance_cross_blocks(self._h, arrs[0].shape[0], *[nat.i32p(x) for x in arrs], nat.f64p(out)))
         return out
 
+    # ---- multi-view triangulation (ps_triangulate) -----------------------
+    def triangulate(self, vids=None, refine_iters=5, min_parallax_deg=1.0, write_back=True):
+        """Variable landmarks `vids` (None: all, in vid order) from their observations and the current poses: linear start,
+        `refine_iters` Gauss-Newton steps on the landmark's own cost, status per landmark (include/pyslam_hip.h:
+        ps_triangulate).  -> (points (n, 3), status (n,) int32); with `write_back` the points with status 0 replace the
+        handle's."""
+        if vids is not None:
+            vids = np.ascontiguousarray(vids, dtype=np.int32).reshape(-1)
+        n = self.nv if vids is None else vids.shape[0]
+        pts, status = np.zeros((n, 3)), np.zeros(n, dtype=np.int32)
+        if n:
+            nat.check(self._lib.ps_triangulate(self._h, n, nat.i32p(vids) if vids is not None else None, int(refine_iters),
+                                               float(min_parallax_deg), int(bool(write_back)), nat.f64p(pts), nat.i32p(status)))
+        return pts, status
+
     # ---- data movement -------------------------------------------------
     def get_dx(self):
         """(dx_pose (nr, dof), dx_point (nv, 3)) in device order."""

@@ -15,6 +15,8 @@ Table layout (all fp64 / int32, C-contiguous):
 * ``pose_rid``   (P,)  index into the reduced (Schur) system, -1 = held constant
 * ``points``     (L, 3) landmarks;  ``point_vid`` (L,) variable index, -1 = constant
 * ``obs_*``      reprojection observations: pose idx, point idx, (u,v,d), group idx
+* ``cams``       (C, 5) [cu, cv, fu, fv, b]: b >= 0 stereo baseline, b = -1 RGB-D (third coordinate = depth), b = -2 monocular
+                 (third coordinate of its observations 0, third row and column of its stiffness 0)
 * ``obs_groups`` (G, 4) [camera idx, stiffness idx, loss id, loss k]
 * ``e_*``        binary pose-pose edges: i, j, T_obs^-1 (same packing as poses), group idx
 * ``u_*``        unary pose priors:      i,    T_obs^-1,                        group idx
@@ -373,6 +375,21 @@ def _load_fast_walk(rebuild=False):
     return mod
 
 
+def underdetermined_mono_points(cams, obs_groups, obs_grp, obs_point, point_vid):
+    """Indices of the variable points whose observations are all monocular (cams row b = -2) and number exactly one: their
+    3 x 3 block H_ll has rank 2.  (Points without any observation are left to the solver's own error, as before.)"""
+    cams = np.asarray(cams, dtype=F64).reshape(-1, 5)
+    if not cams.shape[0] or not np.any(cams[:, 4] == -2.0) or not np.size(obs_point):
+        return np.zeros(0, dtype=np.int64)
+    grp = np.asarray(obs_groups, dtype=F64).reshape(-1, 4)
+    mono = cams[grp[np.asarray(obs_grp, dtype=np.int64), 0].astype(np.int64), 4] == -2.0
+    L = len(point_vid)
+    pt = np.asarray(obs_point, dtype=np.int64)
+    n_all = np.bincount(pt, minlength=L)
+    n_mono = np.bincount(pt[mono], minlength=L)
+    return np.nonzero((np.asarray(point_vid) >= 0) & (n_all == 1) & (n_mono == 1))[0]
+
+
 def lower(param_dict, residual_blocks, block_param_keys, block_loss_functions,
           constant_param_keys, hybrid=False):
     """Build a LoweredProblem from the registries of a Problem.  `hybrid` (Options.hybrid_blocks): a block without a typed
@@ -455,10 +472,19 @@ def lower(param_dict, residual_blocks, block_param_keys, block_loss_functions,
         gkey = (id(cam), id(block.stiffness), id(loss))
         g = ogrp_cache.get(gkey)
         if g is None:
-            if np.size(block.stiffness) != 9:
-                raise NotLowerable("reprojection stiffness must be 3x3")
+            if getattr(cam, 'CAMERA_ID', None) == 2:
+                # monocular: the 2 x 2 stiffness in the top-left of a 3 x 3 whose third row and column are zero (the device
+                # carries the third residual row as zeros, csrc/ps_math.h: cam_type 2)
+                if np.size(block.stiffness) != 4:
+                    raise NotLowerable("the reprojection stiffness of a monocular camera must be 2x2")
+                S = np.zeros((3, 3))
+                S[:2, :2] = np.asarray(block.stiffness, dtype=F64).reshape(2, 2)
+            else:
+                if np.size(block.stiffness) != 9:
+                    raise NotLowerable("reprojection stiffness must be 3x3")
+                S = block.stiffness
             lid, lk = _loss_id_k(loss)
-            g = ogrp.add([cams.add(cam.intrinsics()), st3.add(block.stiffness), lid, lk])
+            g = ogrp.add([cams.add(cam.intrinsics()), st3.add(S), lid, lk])
             ogrp_cache[gkey] = g
         return g
 
@@ -481,8 +507,12 @@ def lower(param_dict, residual_blocks, block_param_keys, block_loss_functions,
                 raise KeyError(k)
         if kind in ('reproj', 'reproj_motion_only', 'reproj_motion_only_batch'):
             cam = block.camera
-            if getattr(cam, 'CAMERA_ID', None) not in (0, 1):
+            mono = getattr(cam, 'CAMERA_ID', None) == 2
+            if getattr(cam, 'CAMERA_ID', None) not in (0, 1, 2):
                 raise NotLowerable("camera {} has no device restatement".format(type(cam).__name__))
+            if mono and kind != 'reproj':
+                raise NotLowerable("motion-only reprojection blocks triangulate one observation: a monocular camera ({}) cannot"
+                                   .format(type(cam).__name__))
             if dof != 6 or keys[0] not in pose_ix:
                 raise NotLowerable("reprojection block needs an SE(3) pose first")
             g = obs_group(cam, block, loss)
@@ -490,7 +520,13 @@ def lower(param_dict, residual_blocks, block_param_keys, block_loss_functions,
                 if keys[1] not in point_ix:
                     raise NotLowerable("reprojection block needs a 3-vector landmark second")
                 o_pose[cnt], o_pt[cnt], o_g[cnt] = pose_ix[keys[0]], point_ix[keys[1]], g
-                o_uvd[cnt] = np.asarray(block.obs, dtype=F64).reshape(3)
+                if mono:
+                    if np.size(block.obs) != 2:
+                        raise NotLowerable("the observation of a monocular camera must be a 2-vector (u, v)")
+                    o_uvd[cnt, :2] = np.asarray(block.obs, dtype=F64).reshape(2)
+                    o_uvd[cnt, 2] = 0.
+                else:
+                    o_uvd[cnt] = np.asarray(block.obs, dtype=F64).reshape(3)
                 cnt += 1
             else:
                 # whole block at once (the per-frame Problem of pipelines/sparse.py:153-161 is ONE batch block of
@@ -582,6 +618,10 @@ def lower(param_dict, residual_blocks, block_param_keys, block_loss_functions,
     else:
         lp.obs_pose, lp.obs_point, lp.obs_grp, lp.obs_uvd = o_pose, o_pt, o_g, o_uvd
     lp.cams, lp.stiff3, lp.obs_groups = cams.table(5), st3.table(9), ogrp.table(4)
+    bad = underdetermined_mono_points(lp.cams, lp.obs_groups, lp.obs_grp, lp.obs_point, lp.point_vid)
+    if bad.size:
+        raise ValueError("landmark {!r} is variable and has a single observation, by a monocular camera: two numbers do not "
+                         "fix three (hold it constant, or add an observation)".format(point_keys[int(bad[0])]))
     lp.e_i, lp.e_j, lp.e_grp = e_i, e_j, e_g
     lp.e_Tobs_inv = np.array(e_T).reshape(-1, pw)
     lp.u_i, lp.u_grp = u_i, u_g

@@ -303,6 +303,33 @@ def solve_tables(lp, options=None, stream=None, device=None):
     return history, poses, points, stats
 
 
+def triangulate_tables(lp, refine_iters=5, min_parallax_deg=1.0, stream=None, device=None):
+    """Multi-view triangulation of every variable landmark of the tables ``lp`` on the device, from its observations and
+    ``lp``'s poses (constant ones included): a linear start, ``refine_iters`` Gauss-Newton steps on the landmark's own robust
+    reprojection cost with the poses held, a status per landmark (pyslam_amd/triangulation.py is the same
+    definition in numpy).  -> (points (L, 3): ``lp.points`` with the landmarks of status 0 replaced, status (L,) int32: 0 ok,
+    1 too few observations, 2 no parallax / not positive definite, 3 behind a camera, -1 a constant point, not touched).
+    ``device``: a DeviceProblem of the same tables kept from an earlier call (its parameters are reset to ``lp``'s)."""
+    from pyslam_amd.device import DeviceProblem
+    dev = device
+    if dev is None:
+        dev = DeviceProblem(lp, stream=stream)
+    else:
+        dev.set_params(lp.poses, lp.points)
+    try:
+        pts, st = dev.triangulate(None, refine_iters, min_parallax_deg, write_back=False)
+    finally:
+        if device is None:
+            dev.close()
+    points = np.array(lp.points, dtype=np.float64).reshape(-1, 3)
+    status = np.full(points.shape[0], -1, dtype=np.int32)
+    var = np.nonzero(np.asarray(lp.point_vid) >= 0)[0]
+    vid = np.asarray(lp.point_vid)[var]
+    points[var] = pts[vid]
+    status[var] = st[vid]
+    return points, status
+
+
 class Problem:
     def __init__(self, options=Options()):
         self.options = options
@@ -517,6 +544,44 @@ class Problem:
             if vid >= 0:
                 dx[self._update_partition_dict[key]] = xl[vid]
         return dx
+
+    # ------------------------------------------------------------------
+    # landmark initialisation from several views (no reference counterpart: its cameras triangulate one observation)
+    # ------------------------------------------------------------------
+    def triangulate_landmarks(self, keys=None, refine_iters=5, min_parallax_deg=1.0):
+        """Triangulate the landmarks `keys` (None: every non-constant landmark) on the device from their reprojection blocks
+        and the CURRENT poses (constant poses included) and write the new points into the problem's parameters: a linear
+        start from all views, `refine_iters` Gauss-Newton steps on the landmark's own robust cost with every pose held
+        (pyslam_amd.triangulate_tables).  -> dict key -> status: 0 ok, 1 fewer than two observations and none with depth,
+        2 largest angle between two viewing rays below `min_parallax_deg` and no depth, or a 3 x 3 system that is not
+        positive definite, 3 the result lies behind one of its cameras.  A landmark with a non-zero status keeps its
+        value.  Typed problems only (a block without a device kernel raises NotLowerable); a constant or unknown key raises
+        KeyError."""
+        dev = self._get_device()
+        if self._photometric_form() or not hasattr(dev, 'triangulate'):
+            raise ValueError('triangulate_landmarks: not offered on this route ({})'.format(type(dev).__name__))
+        lp = dev.lp
+        vid_of = {k: int(v) for k, v in zip(lp.point_keys, lp.point_vid)}
+        if keys is None:
+            keys = [k for k in lp.point_keys if vid_of[k] >= 0]
+        else:
+            keys = [keys] if isinstance(keys, str) else list(keys)
+            for k in keys:
+                if k not in vid_of:
+                    raise KeyError('{!r} is not a landmark of this problem'.format(k))
+                if vid_of[k] < 0:
+                    raise KeyError('{!r} is a constant parameter: it is not triangulated'.format(k))
+        pts, status = dev.triangulate([vid_of[k] for k in keys], refine_iters, min_parallax_deg, write_back=True)
+        out = {}
+        for k, p, s in zip(keys, pts, status):
+            out[k] = int(s)
+            if s == 0:
+                val = self.param_dict[k]
+                if isinstance(val, np.ndarray):
+                    val[...] = p
+                else:
+                    self.param_dict[k] = p.copy()
+        return out
 
     # ------------------------------------------------------------------
     # cost (reference problem.py:110-128)

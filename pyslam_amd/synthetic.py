@@ -132,6 +132,40 @@ def stereo_ba(num_kf=200, num_lm=50000, obs_per_lm=10, half_window=20, seed=0,
     return lp, {'poses': T_true, 'points': pts_true}
 
 
+def mono_ba(num_kf=200, num_lm=50000, obs_per_lm=10, half_window=20, seed=0, loss=None, pose_noise=0.01,
+            point_noise=0.05, stereo_fraction=0.0):
+    """Monocular BA: stereo_ba's scene (same seed, same keyframes, landmarks, observation lists and (u, v) noise) seen by a
+    pinhole camera that measures only (u, v) -- cams row b = -2, third coordinate of every observation 0, the 2 x 2
+    stiffness (unit pixel noise) in the top-left of a 3 x 3.  The FIRST TWO keyframes are held constant at their true
+    poses: monocular BA has seven gauge directions, the baseline between two held poses fixes the scale.
+    ``stereo_fraction`` > 0: that share of the observations (seeded) stays stereo, in a second (camera, stiffness) group:
+    both kinds of camera on the same landmarks.  Returns (LoweredProblem, truth dict) like stereo_ba."""
+    lp, truth = stereo_ba(num_kf=num_kf, num_lm=num_lm, obs_per_lm=obs_per_lm, half_window=half_window, seed=seed, loss=loss,
+                          pose_noise=pose_noise, point_noise=point_noise, const_first_pose=True)
+    if num_kf < 3:
+        raise ValueError('mono_ba: at least three keyframes (two are held constant)')
+    lp.poses[1] = pack_pose_matrices(truth['poses'][1:2])[0]
+    lp.pose_rid = np.maximum(np.arange(num_kf, dtype=np.int32) - 2, -1)
+    cam5 = lp.cams[0].copy()
+    mono_cam = cam5.copy()
+    mono_cam[4] = -2.
+    S2 = np.zeros((3, 3))
+    S2[:2, :2] = invsqrt(np.identity(2))
+    row = lp.obs_groups[0].copy()
+    if stereo_fraction > 0.:
+        stereo = np.random.default_rng([seed, 4]).random(lp.num_obs) < stereo_fraction
+        lp.cams = np.stack([mono_cam, cam5])
+        lp.stiff3 = np.stack([S2.ravel(), lp.stiff3[0]])
+        lp.obs_groups = np.array([[0., 0., row[2], row[3]], [1., 1., row[2], row[3]]])
+        lp.obs_grp = stereo.astype(np.int32)
+        lp.obs_uvd[~stereo, 2] = 0.
+    else:
+        lp.cams = mono_cam[None, :]
+        lp.stiff3 = S2.reshape(1, 9)
+        lp.obs_uvd[:, 2] = 0.
+    return lp.finalize(), truth
+
+
 # ---------------------------------------------------------------------------
 # C2: SE(3) pose graph;  C1-style: SE(2) pose graph
 # ---------------------------------------------------------------------------
@@ -278,7 +312,8 @@ def to_objects(lp, ns, options=None, points_first=True):
     lkeys = list(lp.point_keys) + ['_fixed_pt{}'.format(i)
                                    for i in range(lp.num_points - len(lp.point_keys))]
 
-    cams = [ns.StereoCamera(*row, 1280, 960) for row in lp.cams]
+    # (cams row b = -2: a monocular camera -- ns.MonoCamera, 2-vector observations, the 2 x 2 corner of the stiffness)
+    cams = [ns.MonoCamera(*row[:4], 1280, 960) if row[4] == -2. else ns.StereoCamera(*row, 1280, 960) for row in lp.cams]
     st3 = [row.reshape(3, 3) for row in lp.stiff3]
     std = [row.reshape(lp.dof, lp.dof) for row in lp.stiffd]
     og = [(cams[int(g[0])], st3[int(g[1])], make_loss(ns, g[2], g[3])) for g in lp.obs_groups]
@@ -294,8 +329,15 @@ def to_objects(lp, ns, options=None, points_first=True):
         else:
             block = ns.PoseToPoseResidual(Tinv.inv(), S)
         problem.add_residual_block(block, [pkeys[i], pkeys[j]], eg[g][1])
+    mono_stiff = {}
     for i, j, uvd, g in zip(lp.obs_pose, lp.obs_point, lp.obs_uvd, lp.obs_grp):
         cam, S, loss = og[g]
+        if getattr(cam, 'CAMERA_ID', None) == 2:
+            S2 = mono_stiff.get(id(S))
+            if S2 is None:
+                S2 = mono_stiff[id(S)] = S[:2, :2].copy()
+            problem.add_residual_block(ns.ReprojectionResidual(cam, uvd[:2].copy(), S2), [pkeys[i], lkeys[j]], loss)
+            continue
         problem.add_residual_block(ns.ReprojectionResidual(cam, uvd.copy(), S),
                                    [pkeys[i], lkeys[j]], loss)
 
