@@ -558,6 +558,27 @@ int ps_ransac_frame_to_frame(const double* pts_1, const double* pts_2, const dou
                              double thresh, double* T_all, int32_t* counts, int32_t* best_index,
                              int32_t* best_count, double* T_best, uint8_t* best_mask);
 
+/* Monocular two-view initialisation: essential-matrix RANSAC on 2-D - 2-D correspondences (pyslam_amd/pipelines/twoview.py;
+   the definition, the sign rule, the candidate order and the tie rules: pyslam_amd/csrc/ps_k_twoview.h, restated in numpy by
+   pyslam_amd/pipelines/epipolar.py).  Stateless; host pointers in, host pointers out.  obs_1, obs_2: (num_pts, 2) pixels;
+   cam5 = cu cv fu fv b (b is not read); sample_idx: (num_hyp, 8) point indices, drawn by the caller; thresh: squared Sampson
+   distance in pixels^2.  Two calls on the same input are bit-identical.
+   ps_twoview_hypotheses -- per sample the eight-point essential matrix E (row-major 3 x 3, x_2^T E x_1 = 0, singular values
+                            1 1 0, largest entry positive), its inlier count and its degenerate flag (a repeated index or a
+                            rank-deficient sample: E = 0, count 0, flag 1).
+   ps_twoview_score      -- inlier masks (num_hyp x num_pts bytes) and counts of given matrices.
+   ps_twoview_ransac     -- the whole chain with one synchronisation: hypotheses, the first one with the most inliers, its mask,
+                            the refit over its inliers (refit != 0; kept when its count is not lower), decomposition and cheirality
+                            vote.  T_21 (4 x 4, |t| = 1), E_out (9), mask (num_pts), parallax_deg (num_pts, 0 outside the inliers),
+                            info (8): best index, its count, final count, refit kept, the four candidates' cheirality counts. */
+int ps_twoview_hypotheses(const double* obs_1, const double* obs_2, int32_t num_pts, const int32_t* sample_idx, int32_t num_hyp,
+                          const double* cam5, double thresh, double* E_all, int32_t* counts, uint8_t* degenerate);
+int ps_twoview_score(const double* E, int32_t num_hyp, const double* obs_1, const double* obs_2, int32_t num_pts,
+                     const double* cam5, double thresh, uint8_t* masks, int32_t* counts);
+int ps_twoview_ransac(const double* obs_1, const double* obs_2, int32_t num_pts, const int32_t* sample_idx, int32_t num_hyp,
+                      const double* cam5, double thresh, int32_t refit, double* T_21, double* E_out, uint8_t* mask,
+                      int32_t* info, double* parallax_deg);
+
 /* Dense photometric alignment: one SE(3) pose, one residual per reference pixel --
    PhotometricResidualSE3 (pyslam/residuals/photometric_residual.py:38-161) inside Problem's Gauss-Newton
    iteration with element-wise IRLS (pyslam/problem.py:279-360), as the dense VO pipeline runs it per pyramid

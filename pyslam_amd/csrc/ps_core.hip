@@ -24,6 +24,7 @@
 #include "pyslam_hip.h"
 #include "ps_kernels.h"
 #include "ps_ransac.h"
+#include "ps_k_twoview.h"
 #include "ps_photo.h"
 #include "ps_k_dense.h"
 #include "ps_k_feat.h"
@@ -670,6 +671,7 @@ extern "C" {
 #include "ps_abi_cov.h"
 #include "ps_abi_triang.h"
 #include "ps_abi_small.h"
+#include "ps_abi_twoview.h"
 #include "ps_abi_dense.h"
 #include "ps_abi_feat.h"
 

@@ -603,3 +603,42 @@ def add_user_blocks(problem, lp, ns, kinds, poses, t_obs, stiffness, loss_rows):
         problem.add_residual_block(block, bkeys, make_loss(ns, lr[0], lr[1]))
         out.append(block)
     return out
+
+
+# ---------------------------------------------------------------------------
+# two monocular views of one scene: correspondences with outliers (pipelines/twoview.py)
+# ---------------------------------------------------------------------------
+TWO_VIEW_CAMERA = (320., 240., 500., 500., 640, 480)
+
+
+def two_view(num_pts=192, seed=11, outlier_fraction=0.3, pixel_noise=0.5, rotvec=(0.02, -0.05, 0.03), t=(0.5, -0.05, 0.1)):
+    """Two pinhole views of ``num_pts`` points uniform in [-3, 3] x [-2, 2] x [4, 12] m (frame of camera 1), camera
+    (cu, cv, fu, fv) = (320, 240, 500, 500) at 640 x 480, second pose p_2 = R p_1 + t with R = exp(rotvec).  Gaussian pixel noise
+    on both images; the first ``outlier_fraction * num_pts`` rows of obs_2 are replaced by uniform pixels.
+    -> (obs_1 (N, 2), obs_2 (N, 2), T_21 (4, 4) truth, outlier mask (N,) bool); the true points: two_view_points."""
+    pts, T = _two_view_scene(num_pts, seed, rotvec, t)
+    cu, cv, fu, fv, w, h = TWO_VIEW_CAMERA
+    rng = np.random.default_rng([seed, 1])
+    p2 = pts @ T[:3, :3].T + T[:3, 3]
+    obs_1 = np.stack([fu * pts[:, 0] / pts[:, 2] + cu, fv * pts[:, 1] / pts[:, 2] + cv], axis=1)
+    obs_2 = np.stack([fu * p2[:, 0] / p2[:, 2] + cu, fv * p2[:, 1] / p2[:, 2] + cv], axis=1)
+    obs_1 = obs_1 + pixel_noise * rng.standard_normal(obs_1.shape)
+    obs_2 = obs_2 + pixel_noise * rng.standard_normal(obs_2.shape)
+    n_out = int(outlier_fraction * num_pts)
+    outlier = np.arange(num_pts) < n_out
+    obs_2[:n_out] = rng.uniform([0., 0.], [w, h], size=(n_out, 2))
+    return obs_1, obs_2, T, outlier
+
+
+def _two_view_scene(num_pts, seed, rotvec, t):
+    rng = np.random.default_rng([seed, 0])
+    pts = np.stack([rng.uniform(-3., 3., num_pts), rng.uniform(-2., 2., num_pts), rng.uniform(4., 12., num_pts)], axis=1)
+    T = np.identity(4)
+    T[:3, :3] = SO3.exp(np.asarray(rotvec, dtype=np.float64)).as_matrix()
+    T[:3, 3] = t
+    return pts, T
+
+
+def two_view_points(num_pts=192, seed=11, rotvec=(0.02, -0.05, 0.03), t=(0.5, -0.05, 0.1)):
+    """The true points (N, 3) of two_view's scene, in the frame of camera 1."""
+    return _two_view_scene(num_pts, seed, rotvec, t)[0]

@@ -1,0 +1,200 @@
+"""Monocular two-view initialisation, host side: the numpy restatement (pyslam_amd/pipelines/epipolar.py) against closed forms,
+its tie and degeneracy rules, the C ABI of the new exports and the error paths of pyslam_amd/pipelines/twoview.py.  No device."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from pyslam_amd import synthetic
+from pyslam_amd.liegroups import SO3
+from pyslam_amd.pipelines import epipolar as ep
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CAM = np.array([320., 240., 500., 500., -2.])
+
+
+def samples_of(n, h, seed=5):
+    rs = np.random.RandomState(seed)
+    return np.stack([rs.choice(n, 8, replace=False) for _ in range(h)]).astype(np.int32)
+
+
+def rel_fro(a, b):
+    return np.linalg.norm(a - b) / np.linalg.norm(b)
+
+
+def rot_angle(Ra, Rb):
+    return np.linalg.norm(SO3.from_matrix(Ra @ Rb.T, normalize=True).log())
+
+
+def dir_angle(a, b):
+    a, b = a / np.linalg.norm(a), b / np.linalg.norm(b)
+    return np.linalg.norm(np.cross(a, b))          # (sine of the angle: exact near 0, unlike arccos)
+
+
+@pytest.fixture(scope='module')
+def exact():
+    obs_1, obs_2, T, outlier = synthetic.two_view(pixel_noise=0., outlier_fraction=0.)
+    return obs_1, obs_2, T, samples_of(192, 256)
+
+
+def test_the_scene_generator():
+    obs_1, obs_2, T, outlier = synthetic.two_view()
+    assert obs_1.shape == obs_2.shape == (192, 2) and T.shape == (4, 4) and outlier.sum() == 57 and outlier[:57].all()
+    again = synthetic.two_view()
+    assert np.array_equal(obs_1, again[0]) and np.array_equal(obs_2, again[1])
+    pts = synthetic.two_view_points()
+    assert pts[:, 0].min() >= -3. and pts[:, 0].max() <= 3. and pts[:, 2].min() >= 4. and pts[:, 2].max() <= 12.
+    assert np.allclose(T[:3, 3], [0.5, -0.05, 0.1]) and np.allclose(T[:3, :3] @ T[:3, :3].T, np.identity(3))
+    assert (obs_2[:57] >= 0.).all() and (obs_2[:57, 0] <= 640.).all() and (obs_2[:57, 1] <= 480.).all()
+
+
+def test_every_hypothesis_reproduces_the_true_essential_matrix(exact):
+    obs_1, obs_2, T, samples = exact
+    E_true = ep.essential_from_pose(T[:3, :3], T[:3, 3])
+    E, counts, degenerate, _ = ep.hypotheses(obs_1, obs_2, CAM, samples, 4.0)
+    assert not degenerate.any()
+    worst = max(rel_fro(E[h], E_true) for h in range(len(samples)))
+    print('noise-free scene: worst hypothesis against [t]x R / |t|: {:.2e} relative Frobenius'.format(worst))
+    assert worst <= 1e-9                                   # the issue's bound; measured 6.1e-12 (worst sample sigma_8 / sigma_1 = 2.6e-6)
+    assert (counts == 192).all()
+    s = np.linalg.svd(E[0], compute_uv=False)
+    assert np.allclose(s, [1., 1., 0.], atol=1e-12)
+    assert E[0].reshape(-1)[np.argmax(np.abs(E[0]))] > 0.
+
+
+def test_the_cheirality_vote_picks_the_true_pose(exact):
+    obs_1, obs_2, T, samples = exact
+    res = ep.ransac(obs_1, obs_2, CAM, samples[:16], 4.0)
+    assert res['count'] == 192 and res['cheirality_counts'][res['winner']] == 192
+    assert sorted(res['cheirality_counts'].tolist())[:3] == [0, 0, 0]
+    e_rot, e_dir = rot_angle(res['T_21'][:3, :3], T[:3, :3]), dir_angle(res['T_21'][:3, 3], T[:3, 3])
+    print('noise-free scene: rotation {:.2e} rad, translation direction {:.2e}'.format(e_rot, e_dir))
+    assert e_rot <= 1e-8 and e_dir <= 1e-8                 # E is held to 1e-9 above; the pose is a well-conditioned function of it
+    assert abs(np.linalg.norm(res['T_21'][:3, 3]) - 1.) <= 1e-14 and abs(np.linalg.det(res['T_21'][:3, :3]) - 1.) <= 1e-12
+    assert res['parallax_deg'].shape == (192,) and (res['parallax_deg'] > 1.).all()
+
+
+def test_sampson_distance_of_exact_correspondences(exact):
+    obs_1, obs_2, T, _ = exact
+    E_true = ep.essential_from_pose(T[:3, :3], T[:3, 3])
+    d = ep.sampson(E_true, ep.normalise(obs_1, CAM), ep.normalise(obs_2, CAM), CAM)
+    print('Sampson distance of exact correspondences: max {:.2e} px^2'.format(d.max()))
+    assert d.max() <= 1e-20
+    # one pixel off the epipolar line in image 2 is a squared distance of about half a pixel^2 shared between the two images
+    x1, x2 = ep.normalise(obs_1, CAM), ep.normalise(obs_2, CAM)
+    line = (E_true @ np.array([x1[0, 0], x1[0, 1], 1.]))[:2]
+    off = obs_2[:1] + line / np.linalg.norm(line)
+    d1 = ep.sampson(E_true, x1[:1], ep.normalise(off, CAM), CAM)[0]
+    assert 0.3 < d1 < 1.0
+    assert ep.sampson(np.zeros((3, 3)), x1, x2, CAM).min() == np.inf and not ep.score(np.zeros((3, 3)), x1, x2, CAM, 4.)[0].any()
+
+
+def test_degenerate_samples_and_the_first_maximum():
+    obs_1, obs_2, T, outlier = synthetic.two_view()
+    samples = samples_of(192, 8)
+    samples[2, 5] = samples[2, 1]                            # a repeated index
+    samples[6] = samples[4]                                  # the same hypothesis twice: equal counts
+    E, counts, degenerate, _ = ep.hypotheses(obs_1, obs_2, CAM, samples, 4.0)
+    assert degenerate.tolist() == [False, False, True] + [False] * 5
+    assert counts[2] == 0 and not E[2].any() and np.isfinite(E).all()
+    assert counts[4] == counts[6]
+    forced = samples[[2, 4, 6, 2]]
+    res = ep.ransac(obs_1, obs_2, CAM, forced, 4.0, refit_winner=False)
+    assert res['best'] == 1 and np.array_equal(res['E'], res['E_all'][1])
+    # collinear image points: a rank-deficient sample without a repeated index
+    x = np.stack([np.linspace(-0.3, 0.3, 8), np.zeros(8)], axis=1)
+    assert not ep.eight_point(x, x + [0.01, 0.], np.arange(8))[1]
+
+
+def test_the_candidate_order_and_its_ties(exact):
+    obs_1, obs_2, T, _ = exact
+    E = ep.essential_from_pose(T[:3, :3], T[:3, 3])
+    c = ep.candidates(E)
+    assert len(c) == 4
+    assert np.array_equal(c[0][0], c[1][0]) and np.array_equal(c[2][0], c[3][0]) and not np.allclose(c[0][0], c[2][0])
+    assert np.array_equal(c[0][1], -c[1][1]) and np.array_equal(c[0][1], c[2][1])
+    t = c[0][1]
+    assert t[np.argmax(np.abs(t))] > 0. and abs(np.linalg.norm(t) - 1.) < 1e-14
+    U, _, Vt = np.linalg.svd(E)
+    for R, _ in c:
+        assert abs(np.linalg.det(R) - 1.) < 1e-12
+    for R, tt in c:                                          # every candidate explains E up to sign
+        tx = np.array([[0., -tt[2], tt[1]], [tt[2], 0., -tt[0]], [-tt[1], tt[0], 0.]])
+        assert min(np.abs(tx @ R - E).max(), np.abs(tx @ R + E).max()) < 1e-12
+    # -E is another matrix with the same four poses: the two rotations change places, u_3 stays (which is why E carries a sign rule)
+    n = ep.candidates(-E)
+    assert np.allclose(n[0][0], c[2][0], atol=1e-12) and np.allclose(n[2][0], c[0][0], atol=1e-12)
+    assert all(np.allclose(a[1], b[1], atol=1e-12) for a, b in zip(n, c))
+    # no inliers: four counts of 0, the first candidate is taken
+    x1, x2 = ep.normalise(obs_1, CAM), ep.normalise(obs_2, CAM)
+    T0, counts, win, par = ep.cheirality(E, x1, x2, np.zeros(192, dtype=bool))
+    assert counts.tolist() == [0, 0, 0, 0] and win == 0 and np.array_equal(T0[:3, :3], c[0][0]) and np.array_equal(T0[:3, 3], c[0][1])
+    # the true pose is one of the four, and the vote finds it
+    T1, counts, win, _ = ep.cheirality(E, x1, x2, np.ones(192, dtype=bool))
+    assert counts[win] == 192 and rot_angle(T1[:3, :3], T[:3, :3]) < 1e-10
+
+
+def test_the_refit_is_kept_only_when_it_is_no_worse():
+    obs_1, obs_2, T, outlier = synthetic.two_view()
+    np.random.seed(5)
+    samples = np.stack([np.random.choice(192, 8, replace=False) for _ in range(400)])
+    raw = ep.ransac(obs_1, obs_2, CAM, samples, 4.0, refit_winner=False)
+    res = ep.ransac(obs_1, obs_2, CAM, samples, 4.0)
+    assert raw['best'] == res['best'] and res['raw_count'] == raw['count'] and res['count'] >= raw['count']
+    assert res['refit_kept'] and not raw['refit_kept']
+    assert (res['mask'] & ~outlier).sum() >= 0.8 * (~outlier).sum()
+
+
+def test_the_c_abi_of_the_new_exports():
+    from pyslam_amd import _native as nat
+    header = open(os.path.join(REPO, 'include', 'pyslam_hip.h')).read()
+    for name in ('ps_twoview_hypotheses', 'ps_twoview_ransac', 'ps_twoview_score'):
+        decl = re.search(r'\bint ' + name + r'\((.*?)\);', header, re.S).group(1)
+        assert name in nat.SIGNATURES and len(decl.split(',')) == len(nat.SIGNATURES[name][1]), name
+    src = open(os.path.join(REPO, 'pyslam_amd', 'csrc', 'ps_abi_twoview.h')).read()
+    for name in ('ps_twoview_hypotheses', 'ps_twoview_ransac', 'ps_twoview_score'):
+        defn = re.search(r'\nint ' + name + r'\((.*?)\) \{', src, re.S).group(1)
+        assert len(defn.split(',')) == len(nat.SIGNATURES[name][1]), name
+    core = open(os.path.join(REPO, 'pyslam_amd', 'csrc', 'ps_core.hip')).read()
+    assert '#include "ps_k_twoview.h"' in core and '#include "ps_abi_twoview.h"' in core
+    # the build hash covers every file of csrc/, the new headers included
+    import __graft_entry__ as g
+    assert {'ps_k_twoview.h', 'ps_abi_twoview.h'} <= set(os.listdir(os.path.dirname(g.SRC)))
+
+
+def test_errors_and_imports():
+    import pyslam.pipelines.twoview as shim
+    from pyslam_amd.pipelines import twoview
+    from pyslam_amd.sensors import MonoCamera
+    assert shim.EssentialRANSAC is twoview.EssentialRANSAC and shim.bootstrap is twoview.bootstrap
+    cam = MonoCamera(*synthetic.TWO_VIEW_CAMERA)
+    rs = twoview.EssentialRANSAC(cam)
+    assert (rs.ransac_iters, rs.ransac_thresh, rs.num_min_set_pts, rs.min_inliers, rs.refit) == (400, 4.0, 8, 16, True)
+    obs_1, obs_2, _, _ = synthetic.two_view()
+    rs.set_obs(obs_1[:7], obs_2[:7])
+    with pytest.raises(ValueError, match='at least 8 correspondences'):
+        rs.perform_ransac()
+    with pytest.raises(ValueError, match='same number of points'):
+        rs.set_obs(obs_1, obs_2[:100])
+    with pytest.raises(ValueError, match=r'shape \(N, 2\) or \(N, 3\)'):
+        rs.set_obs(obs_1.T, obs_2.T)
+    rs.set_obs(np.concatenate([obs_1, np.ones((192, 1))], axis=1), obs_2)       # a third column is ignored
+    assert rs.obs_1.shape == (192, 2) and np.array_equal(rs.obs_1, obs_1)
+    np.random.seed(1)
+    s = rs.draw_samples()
+    assert s.shape == (400, 8) and s.dtype == np.int32 and all(np.unique(r).size == 8 for r in s)
+    # too few inliers: the device's answer stands in here (the device path itself: tests/test_gpu_twoview.py)
+    from pyslam_amd import _native as nat
+    few = dict(T_21=np.identity(4), E=np.zeros((3, 3)), mask=np.arange(192) < 9, best=0, raw_count=9, count=9, refit_kept=False,
+               cheirality_counts=np.zeros(4, dtype=np.int32), parallax_deg=np.zeros(192))
+    rs._device_ransac = lambda idx: few
+    real = nat.require_gpu
+    nat.require_gpu = lambda: None
+    try:
+        with pytest.raises(ValueError, match='failed to find 16 inliers'):
+            rs.perform_ransac()
+    finally:
+        nat.require_gpu = real
+    lp = twoview.two_view_tables(cam, np.identity(4), obs_1[:5], obs_2[:5])
+    assert lp.num_poses == 2 and (lp.pose_rid < 0).all() and lp.num_var_points == 5 and lp.num_obs == 10 and lp.cams[0, 4] == -2.
