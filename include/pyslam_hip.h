@@ -237,7 +237,8 @@ int ps_gn_iteration(ps_problem* h, double lambda, double pcg_tol, int pcg_max_it
 /* The loop of Problem.solve (reference pyslam/problem.py:130-178) for a problem of ONE variable SE(3) pose observing
    constant landmarks -- config 5, built per frame by pipelines/sparse.py:153-161 -- in ONE launch and one
    synchronisation: the start cost, then iterations until `iterations > max_iters`, ||dx|| < min_update_norm, cost <
-   min_cost or the non-decreasing-step rules stop it (best parameters kept and restored as the reference does).
+   min_cost or the non-decreasing-step rules stop it (best parameters kept and restored as the reference does; the rule
+   is pyslam_amd/csrc/ps_stop_rule.h, run by the kernel).
    Options carry the reference's names; linesearch != 0: an iteration's cost is the cost after its (always full) step,
    else the cost of its linearisation point (problem.py:188-192).  cost_history receives the reference's
    _cost_history (at most max_iters + 2 entries), the pose is left updated and, if pose12_out is not NULL, also returned
@@ -270,8 +271,10 @@ const char* ps_build_sha(void);
    the non-decreasing-step rules stop it, the best parameters kept by ps_snapshot_params / ps_restore_params as the reference
    keeps best_params.  cost_history receives the reference's _cost_history (at most max_iters + 2 entries); pcg_iters,
    pcg_relres and iter_ms (host wall clock of every iteration call, ms) receive one entry per iteration, each may be NULL.
-   The same statements as pyslam_amd/problem.py: device_solve (which calls this when the device offers it), without the
-   interpreter between two iterations.  Returns 0 = solved, 1 = not offered for this handle (landmark-sharded: the caller
+   The same loop as pyslam_amd/problem.py: device_solve (which calls this when the device offers it), without the
+   interpreter between two iterations.  The stopping rule itself has ONE definition for every loop of the core, this one, ps_solve_lm
+   (its threshold tests), ps_motion_only_solve and ps_dense_track: pyslam_amd/csrc/ps_stop_rule.h, which reads ps_solve_options;
+   the Python loops use its counterpart, pyslam_amd/problem.py: StopRule.  Returns 0 = solved, 1 = not offered for this handle (landmark-sharded: the caller
    loops with ps_gn_iteration) or `cap` too small, <0 = error. */
 int ps_solve(ps_problem* h, const ps_solve_options* options, double pcg_tol, int pcg_max_iters, double* cost_history,
              int32_t cap, int32_t* n_history, int32_t* iterations, double* last_dx_norm, int32_t* pcg_iters,

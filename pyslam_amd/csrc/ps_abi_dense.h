@@ -233,8 +233,6 @@ int ps_dense_track(ps_dense* d, int32_t ref_slot, int32_t track_slot, int32_t nu
     HIP_OK(hipMemcpyAsync(d->pose, d->h_pose, 12 * sizeof(double), hipMemcpyHostToDevice, d->stream));
     HIP_OK(hipMemsetAsync(d->results, 0, (size_t)num_levels * per * sizeof(double), d->stream));
     HIP_OK(hipMemsetAsync(d->state, 0, sizeof(DenseSolveState), d->stream));
-    DenseSolveOpts o{opt->max_iters, opt->allow_nondecreasing_steps, opt->max_nondecreasing_steps, opt->linesearch,
-                     opt->min_update_norm, opt->min_cost, opt->min_cost_decrease};
     for (int k = 0; k < num_levels; ++k) {
         const int l = levels[k];
         const PsDenseLevel& L = d->lv[l];
@@ -252,17 +250,17 @@ int ps_dense_track(ps_dense* d, int32_t ref_slot, int32_t track_slot, int32_t nu
         const int rot = rot_only[k] != 0;
         hipLaunchKernelGGL(k_dense_pass, dim3(nparts), dim3(256), 0, d->stream, a, n_dev, (const double*)d->pose, 0, 1, d->partials,
                            (const DenseSolveState*)d->state);
-        hipLaunchKernelGGL(k_dense_finish, dim3(1), dim3(256), 0, d->stream, nparts, (const double*)d->partials, 0, rot, o, d->pose,
+        hipLaunchKernelGGL(k_dense_finish, dim3(1), dim3(256), 0, d->stream, nparts, (const double*)d->partials, 0, rot, *opt, d->pose,
                            d->state, out);
         for (int it = 0; it <= opt->max_iters; ++it) {       // the loop stops once the iteration count exceeds max_iters
             hipLaunchKernelGGL(k_dense_pass, dim3(nparts), dim3(256), 0, d->stream, a, n_dev, (const double*)d->pose, 1, 0,
                                d->partials, (const DenseSolveState*)d->state);
-            hipLaunchKernelGGL(k_dense_finish, dim3(1), dim3(256), 0, d->stream, nparts, (const double*)d->partials, 1, rot, o,
+            hipLaunchKernelGGL(k_dense_finish, dim3(1), dim3(256), 0, d->stream, nparts, (const double*)d->partials, 1, rot, *opt,
                                d->pose, d->state, out);
             if (opt->linesearch) {
                 hipLaunchKernelGGL(k_dense_pass, dim3(nparts), dim3(256), 0, d->stream, a, n_dev, (const double*)d->pose, 0, 0,
                                    d->partials, (const DenseSolveState*)d->state);
-                hipLaunchKernelGGL(k_dense_finish, dim3(1), dim3(256), 0, d->stream, nparts, (const double*)d->partials, 2, rot, o,
+                hipLaunchKernelGGL(k_dense_finish, dim3(1), dim3(256), 0, d->stream, nparts, (const double*)d->partials, 2, rot, *opt,
                                    d->pose, d->state, out);
             }
         }

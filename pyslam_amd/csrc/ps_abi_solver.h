@@ -558,7 +558,8 @@ int ps_gn_iteration(ps_problem* h, double lambda, double pcg_tol, int pcg_max_it
 }
 
 // The loop of Problem.solve (reference pyslam/problem.py:130-178), driven from here: no interpreter between two iterations,
-// the start cost's pass rides in front of the first iteration.  Statement for statement pyslam_amd/problem.py: device_solve.
+// the start cost's pass rides in front of the first iteration.  The stopping rule is ps_stop_rule.h's, as it is for
+// pyslam_amd/problem.py: device_solve (StopRule), the loop this one is held against bit for bit.
 int ps_solve(ps_problem* h, const ps_solve_options* o, double pcg_tol, int pcg_max_iters, double* cost_history, int32_t cap,
              int32_t* n_history, int32_t* iterations, double* last_dx_norm, int32_t* pcg_iters, double* pcg_relres, double* iter_ms) {
     if (!h || !o || !cost_history || !n_history) return fail("null argument");
@@ -566,14 +567,15 @@ int ps_solve(ps_problem* h, const ps_solve_options* o, double pcg_tol, int pcg_m
     if (h->hybrid) return 1;                                  // the stopping rules need the caller's blocks' cost (the caller loops)
     if (o->max_iters < 0 || (long)o->max_iters + 2 > cap) return 1;
     if (ps_reset_solver_state(h)) return -1;
-    int n = 0, it = 0, nd = 0;
-    double cost = 0.0, dxn = 0.0, last_ratio = 1.0;
+    ps_stop_state stop;
+    ps_stop_begin(&stop, 0.0);                                // (the start cost arrives with the first iteration)
+    int n = 0;
+    double dxn = 0.0, last_ratio = 1.0;
     bool done = false;
     while (!done) {
-        ++it;
+        const int it = stop.iters + 1;
         // iterations the stopping rules still allow after this one if its step is non-decreasing (option "solve_horizon")
-        h->solve_horizon = !o->allow_nondecreasing_steps ? 0
-                         : std::max(0, std::min(o->max_nondecreasing_steps - (nd + 1), o->max_iters + 1 - it));
+        h->solve_horizon = ps_stop_horizon(o, &stop);
         // Will there be another iteration?  Surely (short of ||dx|| / min_cost stopping it) if even a non-decreasing step leaves
         // the solve running; without allow_nondecreasing_steps, likely while the steps still cut the cost in half.  Then the next
         // linearisation is enqueued behind this iteration's tail (wait_published).  Not while the lagged dense inverse may seed: its
@@ -586,24 +588,20 @@ int ps_solve(ps_problem* h, const ps_solve_options* o, double pcg_tol, int pcg_m
         const int rc_it = gn_iteration_impl(h, o->lm_lambda, pcg_tol, pcg_max_iters, o->linesearch, &c, &dxn, &its, &rel, it == 1 ? &c0 : nullptr);
         h->spec_next = false; h->expect_next = 0;
         if (rc_it) return -1;
-        if (it == 1) { cost = c0; cost_history[n++] = c0; h->prev_cost = c0; }
-        const double prev = cost;
-        cost = c;
-        last_ratio = prev > 0.0 ? cost / prev : 1.0;
+        if (it == 1) { ps_stop_begin(&stop, c0); cost_history[n++] = c0; h->prev_cost = c0; }
+        last_ratio = stop.cost > 0.0 ? c / stop.cost : 1.0;
         if (pcg_iters) pcg_iters[it - 1] = its;
         if (pcg_relres) pcg_relres[it - 1] = rel;
         if (iter_ms) iter_ms[it - 1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        cost_history[n++] = cost;
-        done = it > o->max_iters || dxn < o->min_update_norm || cost < o->min_cost;
-        if (o->allow_nondecreasing_steps) {
-            if (nd == 0 && ps_snapshot_params(h)) return -1;
-            if (cost >= o->min_cost_decrease * prev) ++nd; else nd = 0;
-            if (nd >= o->max_nondecreasing_steps) { done = true; if (restore_params_by_exchange(h)) return -1; }
-        } else done = done || cost >= o->min_cost_decrease * prev;
+        cost_history[n++] = c;
+        const int f = ps_stop_step(o, &stop, c, dxn);
+        if ((f & PS_STOP_KEEP_BEST) && ps_snapshot_params(h)) return -1;
+        if ((f & PS_STOP_RESTORE_BEST) && restore_params_by_exchange(h)) return -1;
+        done = f & PS_STOP_DONE;
     }
     h->solve_horizon = -1;
     *n_history = n;
-    if (iterations) *iterations = it;
+    if (iterations) *iterations = stop.iters;
     if (last_dx_norm) *last_dx_norm = dxn;
     return 0;
 }
@@ -639,9 +637,11 @@ int ps_lm_iteration(ps_problem* h, double lambda, double pcg_tol, int pcg_max_it
                              pcg_relres_out, nullptr);
 }
 
-// The adaptive loop of Problem.solve (Options.lm_adaptive), driven from here as ps_solve drives the default one.  Statement for
-// statement pyslam_amd/problem.py: _lm_loop.  A rejected step costs one exchange of the parameter tables with the snapshot taken
-// in front of the iteration (no copy back) and a fresh linearisation at the restored point under the raised damping.
+// The adaptive loop of Problem.solve (Options.lm_adaptive), driven from here as ps_solve drives the default one; pyslam_amd/
+// problem.py: _lm_loop is the same loop on ps_lm_iteration.  Of the stopping rule it shares the three threshold tests
+// (ps_stop_rule.h: ps_stop_base); its own two conditions are below.  A rejected step costs one exchange of the parameter tables
+// with the snapshot taken in front of the iteration (no copy back) and a fresh linearisation at the restored point under the
+// raised damping.
 int ps_solve_lm(ps_problem* h, const ps_lm_options* o, double pcg_tol, int pcg_max_iters, double* cost_history, int32_t cap,
                 int32_t* n_history, int32_t* iterations, double* last_dx_norm, int32_t* pcg_iters, double* pcg_relres, double* iter_ms,
                 double* lm_rows) {
@@ -683,7 +683,8 @@ int ps_solve_lm(ps_problem* h, const ps_lm_options* o, double pcg_tol, int pcg_m
         if (pcg_relres) pcg_relres[it - 1] = rel;
         if (iter_ms) iter_ms[it - 1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         cost_history[n++] = cost;
-        done = it > o->max_iters || dxn < o->min_update_norm || cost < o->min_cost;
+        static_assert(offsetof(ps_lm_options, lambda0) == sizeof(ps_solve_options), "ps_lm_options begins with ps_solve_options' fields");
+        done = ps_stop_base(reinterpret_cast<const ps_solve_options*>(o), it, cost, dxn);
         if (accepted) done = done || cost >= o->min_cost_decrease * prev;
         else done = done || raw > o->lambda_max;
     }
@@ -709,21 +710,16 @@ int ps_motion_only_solve(ps_problem* h, const ps_solve_options* o, double* cost_
         HIP_OK(hipMemsetAsync(h->status, 0, ST_NWORDS * sizeof(int32_t), h->stream));
         h->status_clean = true;
     }
-    MoSolveOptions mo{};
-    mo.max_iters = o->max_iters; mo.allow_nondecreasing_steps = o->allow_nondecreasing_steps;
-    mo.max_nondecreasing_steps = o->max_nondecreasing_steps; mo.linesearch = o->linesearch;
-    mo.min_update_norm = o->min_update_norm; mo.min_cost = o->min_cost; mo.min_cost_decrease = o->min_cost_decrease;
-    mo.lambda = o->lm_lambda;
     const ObsWide wp{h->sidx_p, h->stiff_tab};
     const long long seq_now = ++h->seq;
     StageTimer total(h, PS_ST_TOTAL, 2);
     if (h->wide_obs)
         hipLaunchKernelGGL(k_motion_only_solve<true>, dim3(1), dim3(PS_MO_THREADS), 0, h->stream, h->pitems, h->pitem_ptr, h->pobs,
-                           h->points, h->ogroups, h->poses, mo, h->x, h->status, h->scalars, h->h_mo_hist_dev, PS_MO_HIST_WORDS,
+                           h->points, h->ogroups, h->poses, *o, h->x, h->status, h->scalars, h->h_mo_hist_dev, PS_MO_HIST_WORDS,
                            h->h_status_dev, h->h_scalars_dev, h->h_seq_dev, seq_now, wp);
     else
         hipLaunchKernelGGL(k_motion_only_solve<false>, dim3(1), dim3(PS_MO_THREADS), 0, h->stream, h->pitems, h->pitem_ptr, h->pobs,
-                           h->points, h->ogroups, h->poses, mo, h->x, h->status, h->scalars, h->h_mo_hist_dev, PS_MO_HIST_WORDS,
+                           h->points, h->ogroups, h->poses, *o, h->x, h->status, h->scalars, h->h_mo_hist_dev, PS_MO_HIST_WORDS,
                            h->h_status_dev, h->h_scalars_dev, h->h_seq_dev, seq_now, wp);
     total.stop();
     if (wait_published(h)) return -1;

@@ -1,6 +1,7 @@
 // ps_k_tail.h -- one-launch motion-only iteration, covariance right-hand side, back-substitution, updates, costs, final reductions, dense normal equations.
 // Part of ps_kernels.h (included from there, in this order; not a stand-alone header).
 #pragma once
+#include "ps_stop_rule.h"
 
 // ---------------------------------------------------------------------------
 // Motion-only problems (no variable landmark, no pose factor: the reduced system is block diagonal --
@@ -184,16 +185,12 @@ __global__ __launch_bounds__(PS_MO_THREADS) void k_motion_only_iteration(
 // cost after a step and the cost at the next linearisation point are the same sum, evaluated once.
 // ---------------------------------------------------------------------------
 #define PS_MO_SOLVE_OBS 4                     // observations per thread: 4 x 512 = the 2 048 of the one-launch limit
-struct MoSolveOptions {          // Options of the reference (problem.py:14-40) that the loop reads
-    int max_iters, allow_nondecreasing_steps, max_nondecreasing_steps, linesearch;
-    double min_update_norm, min_cost, min_cost_decrease, lambda;
-};
 
 template <bool WIDE>
 __global__ __launch_bounds__(PS_MO_THREADS) void k_motion_only_solve(
     const PItem* __restrict__ items, const int32_t* __restrict__ pitem_ptr,
     const LObs* __restrict__ pobs, const double* __restrict__ points, const ObsGroup* __restrict__ groups,
-    double* __restrict__ poses, MoSolveOptions opt, double* __restrict__ xout /* 6: the last step */,
+    double* __restrict__ poses, ps_solve_options opt, double* __restrict__ xout /* 6: the last step */,
     int32_t* __restrict__ status, double* __restrict__ scalars,
     double* __restrict__ hist /* pinned host: [0] = entries, [1] = iterations, [2] = last |dx|, [3..14] final pose, [15..] cost history */, int hist_cap,
     int32_t* __restrict__ hst, double* __restrict__ hsc, long long* __restrict__ hseq, long long seq, ObsWide wide)
@@ -218,9 +215,18 @@ __global__ __launch_bounds__(PS_MO_THREADS) void k_motion_only_solve(
         obs[q] = pobs[i < end ? i : (end > start ? end - 1 : 0)];
         pwr[q][0] = points[3 * (size_t)obs[q].point]; pwr[q][1] = points[3 * (size_t)obs[q].point + 1]; pwr[q][2] = points[3 * (size_t)obs[q].point + 2];
     }
-    // thread 0's loop state (Problem.solve's local variables)
-    double cost = 0.0, prev_cost = 0.0, last_dx = 100.0;
-    int nhist = 0, iters = 0, nondecreasing = 0;
+    // thread 0's loop state (Problem.solve's local variables; the stopping rule's own are in `stop`: ps_stop_rule.h)
+    ps_stop_state stop = {0, 0, 0.0};
+    double last_dx = 100.0;
+    int nhist = 0;
+    // a finished iteration: its cost joins the history, the rule decides, best parameters are kept in / restored from sBest
+    auto judge = [&](double c) {
+        hist[15 + nhist++] = c;
+        const int f = ps_stop_step(&opt, &stop, c, last_dx);
+        if (f & PS_STOP_KEEP_BEST) se3_store(sBest, T);
+        if (f & PS_STOP_RESTORE_BEST) T = se3_load(sBest);
+        return f & PS_STOP_DONE;
+    };
     for (;;) {
         {
             // ---- the 33 sums + the cost at T (k_motion_only_iteration's first phase, same order)
@@ -266,42 +272,24 @@ __global__ __launch_bounds__(PS_MO_THREADS) void k_motion_only_solve(
             int done = 0;
             const double c_here = tot[PS_NPOSE_ACC];     // cost at the current T
             if (nhist == 0) {                            // the start: Problem.solve's eval_cost
-                cost = c_here;
-                hist[15 + nhist++] = cost;
+                ps_stop_begin(&stop, c_here);
+                hist[15 + nhist++] = c_here;
             } else if (opt.linesearch) {                 // the step just taken is judged by the cost it led to
-                cost = c_here;
-                hist[15 + nhist++] = cost;
-                done = iters > opt.max_iters || last_dx < opt.min_update_norm || cost < opt.min_cost;
-                if (opt.allow_nondecreasing_steps) {
-                    if (nondecreasing == 0) se3_store(sBest, T);
-                    nondecreasing = (cost >= opt.min_cost_decrease * prev_cost) ? nondecreasing + 1 : 0;
-                    if (nondecreasing >= opt.max_nondecreasing_steps) { done = 1; T = se3_load(sBest); }
-                } else done = done || cost >= opt.min_cost_decrease * prev_cost;
+                done = judge(c_here);
             }
-            double sq = 0.0;
             if (!done) {
                 // H = J^T J (+ lambda diag) = L L^T ;  x = H^-1 g   (the function k_motion_only_iteration calls)
                 double x[6];
-                const bool ok = mo_solve6(tot, opt.lambda, x);
+                const bool ok = mo_solve6(tot, opt.lm_lambda, x);
                 if (!ok) { atomicAdd(&status[ST_DIAG_FAIL], 1); done = 2; }
                 else {
+                    double sq = 0.0;
                     for (int k = 0; k < 6; ++k) { xout[k] = x[k]; sq += x[k] * x[k]; }
-                    prev_cost = cost;
-                    ++iters;
                     last_dx = sqrt(sq);
                     T = se3_mul(se3_exp(x), T);
-                    if (!opt.linesearch) {               // the step is judged by the cost of its linearisation point
-                        hist[15 + nhist++] = c_here;
-                        cost = c_here;
-                        done = iters > opt.max_iters || last_dx < opt.min_update_norm || cost < opt.min_cost;
-                        if (opt.allow_nondecreasing_steps) {
-                            if (nondecreasing == 0) se3_store(sBest, T);
-                            // (prev_cost: the cost recorded one iteration earlier -- at the first iteration the start cost,
-                            //  i.e. this very number: the reference counts that as a non-decreasing step, and so does this)
-                            nondecreasing = (cost >= opt.min_cost_decrease * prev_cost) ? nondecreasing + 1 : 0;
-                            if (nondecreasing >= opt.max_nondecreasing_steps) { done = 1; T = se3_load(sBest); }
-                        } else done = done || cost >= opt.min_cost_decrease * prev_cost;
-                    }
+                    // without a line search the step is judged by the cost of its linearisation point (at the first iteration
+                    // the start cost once more: a non-decreasing step, ps_stop_rule.h)
+                    if (!opt.linesearch) done = judge(c_here);
                 }
             }
             if (nhist >= hist_cap - 16 && !done) done = 3;             // (the caller sized hist for max_iters + 2 entries)
@@ -315,8 +303,8 @@ __global__ __launch_bounds__(PS_MO_THREADS) void k_motion_only_solve(
     if (t == 0) {
         se3_store(poses + 12 * (size_t)pose, T);
         se3_store(hist + 3, T);
-        hist[0] = (double)nhist; hist[1] = (double)iters; hist[2] = last_dx;
-        scalars[opt.linesearch ? SC_COST : SC_LINCOST] = cost;
+        hist[0] = (double)nhist; hist[1] = (double)stop.iters; hist[2] = last_dx;
+        scalars[opt.linesearch ? SC_COST : SC_LINCOST] = stop.cost;
         scalars[SC_DXP2] = last_dx * last_dx; scalars[SC_DXL2] = 0.0;
         scalars[SC_RR0] = 1.0; scalars[SC_RRFINAL] = 0.0;
         status[ST_PCG_DONE] = 1; status[ST_PCG_ITERS] = 0;

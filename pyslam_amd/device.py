@@ -15,6 +15,17 @@ from pyslam_amd import _native as nat
 COVARIANCE_MARGINALS_LIMIT = 12288
 
 
+def _solve_options(o, opt, linesearch=None):
+    """The fields of ps_solve_options in `o` (nat.SolveOptions, or nat.LmOptions, which begins with them) from an Options.
+    `linesearch`: what the caller decided, instead of Options.linesearch_max_iters > 0.  -> o"""
+    o.max_iters, o.allow_nondecreasing_steps = int(opt.max_iters), int(bool(opt.allow_nondecreasing_steps))
+    o.max_nondecreasing_steps = int(opt.max_nondecreasing_steps)
+    o.linesearch = int(bool(opt.linesearch_max_iters > 0 if linesearch is None else linesearch))
+    o.min_update_norm, o.min_cost = float(opt.min_update_norm), float(opt.min_cost)
+    o.min_cost_decrease, o.lm_lambda = float(opt.min_cost_decrease), float(getattr(opt, 'lm_lambda', 0.))
+    return o
+
+
 class DeviceProblem:
     def __init__(self, lp, stream=None, extra_pairs=None):
         lib = nat.require_gpu()
@@ -144,11 +155,7 @@ class DeviceProblem:
         """Problem.solve's whole loop in one launch (ps_motion_only_solve) for a one-pose motion-only problem.
         -> (cost history, iterations, last ||dx||, final pose row) or None when the problem is not of that kind (iterate
         instead)."""
-        o = nat.SolveOptions()
-        o.max_iters, o.allow_nondecreasing_steps = int(opt.max_iters), int(bool(opt.allow_nondecreasing_steps))
-        o.max_nondecreasing_steps, o.linesearch = int(opt.max_nondecreasing_steps), int(bool(linesearch))
-        o.min_update_norm, o.min_cost = float(opt.min_update_norm), float(opt.min_cost)
-        o.min_cost_decrease, o.lm_lambda = float(opt.min_cost_decrease), float(getattr(opt, 'lm_lambda', 0.))
+        o = _solve_options(nat.SolveOptions(), opt, linesearch)
         cap = o.max_iters + 2
         if cap < 2 or cap > 238 or self.host is not None:
             return None
@@ -164,11 +171,7 @@ class DeviceProblem:
     def solve_loop(self, opt):
         """Problem.solve's loop in one C call (ps_solve).  -> (cost history, [(pcg iterations, relative residual)], [ms per
         iteration call]) or None when the core does not offer it for this handle (the caller loops itself)."""
-        o = nat.SolveOptions()
-        o.max_iters, o.allow_nondecreasing_steps = int(opt.max_iters), int(bool(opt.allow_nondecreasing_steps))
-        o.max_nondecreasing_steps, o.linesearch = int(opt.max_nondecreasing_steps), int(opt.linesearch_max_iters > 0)
-        o.min_update_norm, o.min_cost = float(opt.min_update_norm), float(opt.min_cost)
-        o.min_cost_decrease, o.lm_lambda = float(opt.min_cost_decrease), float(getattr(opt, 'lm_lambda', 0.))
+        o = _solve_options(nat.SolveOptions(), opt)
         cap = o.max_iters + 2
         if cap < 2 or cap > 100000 or self.host is not None:
             return None
@@ -205,11 +208,7 @@ class DeviceProblem:
         """The adaptive LM loop of Problem.solve in one C call (ps_solve_lm).  -> (cost history, [(pcg iterations, relative
         residual)], [ms per iteration call], lm rows (n, 4)) or None when the core does not offer it for this handle."""
         from pyslam_amd.problem import lm_options
-        o = nat.LmOptions()
-        o.max_iters, o.linesearch = int(opt.max_iters), int(opt.linesearch_max_iters > 0)
-        o.allow_nondecreasing_steps, o.max_nondecreasing_steps = 0, 0
-        o.min_update_norm, o.min_cost, o.min_cost_decrease = float(opt.min_update_norm), float(opt.min_cost), float(opt.min_cost_decrease)
-        o.lm_lambda = 0.
+        o = _solve_options(nat.LmOptions(), opt)      # (the non-decreasing-step fields and lm_lambda: ps_solve_lm ignores them)
         o.lambda0, o.lambda_min, o.lambda_max = lm_options(opt)
         cap = o.max_iters + 2
         if cap < 2 or cap > 100000 or self.host is not None:
@@ -744,13 +743,7 @@ class DenseTracker:
         from pyslam_amd.lowering import _loss_id_k
         lv = np.ascontiguousarray(levels, dtype=np.int32)
         ro = np.ascontiguousarray([1 if r else 0 for r in rot_only], dtype=np.int32)
-        o = nat.SolveOptions()
-        o.max_iters = int(options.max_iters)
-        o.allow_nondecreasing_steps = int(bool(options.allow_nondecreasing_steps))
-        o.max_nondecreasing_steps = int(options.max_nondecreasing_steps)
-        o.linesearch = int(options.linesearch_max_iters > 0)
-        o.min_update_norm, o.min_cost = float(options.min_update_norm), float(options.min_cost)
-        o.min_cost_decrease, o.lm_lambda = float(options.min_cost_decrease), float(getattr(options, 'lm_lambda', 0.))
+        o = _solve_options(nat.SolveOptions(), options)
         lid, lk = _loss_id_k(loss)
         cap = o.max_iters + 2
         pin = np.ascontiguousarray(pose12, dtype=np.float64).reshape(12)

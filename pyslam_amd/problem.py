@@ -110,15 +110,52 @@ def check_lm_route(opt, what=None):
 
 
 def solve_horizon(opt, iteration, nondecreasing_steps_taken):
-    """Iterations the stopping rules of Problem.solve (reference pyslam/problem.py:159-178) still allow AFTER iteration
-    number `iteration` (1-based) if its step turns out non-decreasing (cost >= min_cost_decrease * previous cost): none
-    without allow_nondecreasing_steps, else what max_nondecreasing_steps and max_iters leave.  The device core does not
-    start side work that needs several more iterations to pay back when fewer are to come (ps_set_option "solve_horizon")."""
+    """Iterations the stopping rule of Problem.solve still allows AFTER iteration number `iteration` (1-based) if its step
+    turns out non-decreasing: none without allow_nondecreasing_steps, else what max_nondecreasing_steps and max_iters leave.
+    The device core does not start side work that needs several more iterations to pay back when fewer are to come
+    (ps_set_option "solve_horizon").  csrc/ps_stop_rule.h: ps_stop_horizon."""
     if not opt.allow_nondecreasing_steps:
         return 0
     left_nd = opt.max_nondecreasing_steps - (nondecreasing_steps_taken + 1)
     left_it = opt.max_iters + 1 - iteration       # the loop stops once optimization_iters > max_iters
     return max(0, min(left_nd, left_it))
+
+
+class StopRule:
+    """THE stopping rule of Problem.solve (reference pyslam/problem.py:159-178) for every Python loop here; the contract of
+    csrc/ps_stop_rule.h (which says the rule in words), held against that header by tests/test_stop_rule_host.py.
+    `cost` is the last entry of the cost history, `iters` the iterations judged, `nd` the consecutive non-decreasing steps."""
+    DONE, KEEP_BEST, RESTORE_BEST = 1, 2, 4
+
+    def __init__(self, opt, start_cost):
+        self.opt, self.iters, self.nd, self.cost = opt, 0, 0, start_cost
+
+    @staticmethod
+    def base(opt, iters, cost, dx_norm):
+        """The three threshold tests (all the adaptive LM loop shares with the default one)."""
+        return bool(iters > opt.max_iters or dx_norm < opt.min_update_norm or cost < opt.min_cost)
+
+    def step(self, cost, dx_norm):
+        """One finished iteration -> flags.  KEEP_BEST: store the current (post-step) parameters as best, now; RESTORE_BEST
+        (implies DONE): make best the current parameters; both: store first, then restore."""
+        opt = self.opt
+        nondecreasing = cost >= opt.min_cost_decrease * self.cost      # (the tie counts as non-decreasing)
+        self.iters += 1
+        self.cost = cost
+        flags = self.DONE if self.base(opt, self.iters, cost, dx_norm) else 0
+        if opt.allow_nondecreasing_steps:
+            if self.nd == 0:                                            # (before this step moves the count)
+                flags |= self.KEEP_BEST
+            self.nd = self.nd + 1 if nondecreasing else 0
+            if self.nd >= opt.max_nondecreasing_steps:
+                flags |= self.DONE | self.RESTORE_BEST
+        elif nondecreasing:
+            flags |= self.DONE
+        return flags
+
+    def horizon(self):
+        """solve_horizon for the iteration about to start."""
+        return solve_horizon(self.opt, self.iters + 1, self.nd)
 
 
 def device_solve(dev, opt, use_core_loop=True, call_ms=None):
@@ -177,21 +214,18 @@ def _device_solve_loop(dev, opt, use_core_loop, call_ms):
 
 
 def _reference_loop(dev, opt, expect, horizon, cost, lam, pcg_tol, pcg_max, linesearch, call_ms):
-    """The statements of reference pyslam/problem.py:141-178 on device calls."""
+    """The loop of reference pyslam/problem.py:141-178 on whole-iteration calls of `dev` (gn_iteration, snapshot, restore)."""
     history, stats = [cost], []
-    optimization_iters = 0
-    nondecreasing_steps_taken = 0
-    done_optimization = False
+    rule = StopRule(opt, cost)
     last_ratio = 1.
-    while not done_optimization:
-        optimization_iters += 1
-        prev_cost = cost
+    flags = 0
+    while not flags & StopRule.DONE:
+        it = rule.iters + 1
         if horizon is not None:
-            horizon(solve_horizon(opt, optimization_iters, nondecreasing_steps_taken))
-        if expect is not None:            # the rule ps_solve applies (csrc/ps_abi_solver.h): will another iteration follow?
-            expect(optimization_iters <= opt.max_iters and
-                   (solve_horizon(opt, optimization_iters, nondecreasing_steps_taken) >= 1 if opt.allow_nondecreasing_steps
-                    else (optimization_iters >= 2 and last_ratio < 0.5)))
+            horizon(rule.horizon())
+        if expect is not None:            # as ps_solve (csrc/ps_abi_solver.h): will another iteration follow?
+            expect(it <= opt.max_iters and
+                   (rule.horizon() >= 1 if opt.allow_nondecreasing_steps else (it >= 2 and last_ratio < 0.5)))
         # one device call: linearise, solve, update, post-step cost
         t0 = time.perf_counter()
         cost, dx_norm, its, rel = dev.gn_iteration(lam, pcg_tol, pcg_max, linesearch)
@@ -199,24 +233,34 @@ def _reference_loop(dev, opt, expect, horizon, cost, lam, pcg_tol, pcg_max, line
             call_ms.append((time.perf_counter() - t0) * 1e3)
         stats.append((its, rel))
         history.append(cost)
-        last_ratio = cost / prev_cost if prev_cost > 0. else 1.
-
-        done_optimization = optimization_iters > opt.max_iters or \
-            dx_norm < opt.min_update_norm or cost < opt.min_cost
-
-        if opt.allow_nondecreasing_steps:
-            if nondecreasing_steps_taken == 0:
-                dev.snapshot()
-            if cost >= opt.min_cost_decrease * prev_cost:
-                nondecreasing_steps_taken += 1
-            else:
-                nondecreasing_steps_taken = 0
-            if nondecreasing_steps_taken >= opt.max_nondecreasing_steps:
-                done_optimization = True
-                dev.restore()
-        else:
-            done_optimization = done_optimization or cost >= opt.min_cost_decrease * prev_cost
+        last_ratio = cost / rule.cost if rule.cost > 0. else 1.
+        flags = rule.step(cost, dx_norm)
+        if flags & StopRule.KEEP_BEST:
+            dev.snapshot()
+        if flags & StopRule.RESTORE_BEST:
+            dev.restore()
     return history, stats
+
+
+class _HostIterations:
+    """The generic host path of Problem.solve (a block without a typed kernel) as _reference_loop's `dev`: an iteration is
+    solve_one_iter + the update, best parameters are a deep copy of param_dict (reference pyslam/problem.py:141-178)."""
+
+    def __init__(self, problem):
+        self.problem, self.best = problem, None
+
+    def gn_iteration(self, *_):
+        p = self.problem
+        dx, cost = p.solve_one_iter()
+        for k, r in p._update_partition_dict.items():
+            p._perturb_by_key(k, dx[r])
+        return cost, np.linalg.norm(dx), 0, 0.
+
+    def snapshot(self):
+        self.best = copy.deepcopy(self.problem.param_dict)
+
+    def restore(self):
+        self.problem.param_dict.update(self.best)
 
 
 def _lm_solve_loop(dev, opt, use_core_loop, call_ms):
@@ -241,7 +285,8 @@ def _lm_solve_loop(dev, opt, use_core_loop, call_ms):
 
 
 def _lm_loop(dev, opt, cost, call_ms):
-    """Nielsen's damping rule around whole iterations (csrc/ps_abi_solver.h: ps_solve_lm is this, statement for statement)."""
+    """Nielsen's damping rule around whole iterations (csrc/ps_abi_solver.h: ps_solve_lm is the same loop in the core).  Of
+    the stopping rule it shares StopRule.base; its own two conditions are below."""
     lam, lam_min, lam_max = lm_options(opt)
     nu = 2.
     pcg_tol, pcg_max = (getattr(opt, 'pcg_tol', None) or 0.), getattr(opt, 'pcg_max_iters', 2000)
@@ -270,7 +315,7 @@ def _lm_loop(dev, opt, cost, call_ms):
         lam = min(max(lam, lam_min), lam_max)
         rows.append((used, rho, 1. if accepted else 0., md))
         history.append(cost)
-        done = iters > opt.max_iters or dx_norm < opt.min_update_norm or cost < opt.min_cost
+        done = StopRule.base(opt, iters, cost, dx_norm)
         if accepted:
             done = done or cost >= opt.min_cost_decrease * prev_cost
         else:
@@ -642,40 +687,7 @@ class Problem:
             self._write_back(dev)
             return self.param_dict
 
-        cost = self._eval_cost_host()
-        dx_norm = 100.
-        optimization_iters = 0
-        nondecreasing_steps_taken = 0
-        self._cost_history = [cost]
-        best_params = None
-        done_optimization = False
-
-        while not done_optimization:
-            optimization_iters += 1
-            prev_cost = cost
-
-            dx, cost = self.solve_one_iter()
-            dx_norm = np.linalg.norm(dx)
-            for k, r in self._update_partition_dict.items():
-                self._perturb_by_key(k, dx[r])
-            self._cost_history.append(cost)
-
-            done_optimization = optimization_iters > opt.max_iters or \
-                dx_norm < opt.min_update_norm or cost < opt.min_cost
-
-            if opt.allow_nondecreasing_steps:
-                if nondecreasing_steps_taken == 0:
-                    best_params = copy.deepcopy(self.param_dict)
-                if cost >= opt.min_cost_decrease * prev_cost:
-                    nondecreasing_steps_taken += 1
-                else:
-                    nondecreasing_steps_taken = 0
-                if nondecreasing_steps_taken >= opt.max_nondecreasing_steps:
-                    done_optimization = True
-                    self.param_dict.update(best_params)
-            else:
-                done_optimization = done_optimization or cost >= opt.min_cost_decrease * prev_cost
-
+        self._cost_history, _ = _reference_loop(_HostIterations(self), opt, None, None, self._eval_cost_host(), 0., 0., 0, True, None)
         return self.param_dict
 
     def solve_one_iter(self):

@@ -346,12 +346,17 @@ def test_coarse_to_fine_solve_matches_the_host_restatement(vga, loss, linesearch
 
 
 # ---------------------------------------------------------------- 5. stopping-rule edges
-@pytest.mark.parametrize('case', ['max_iters0', 'max_iters1', 'max_iters2', 'min_cost', 'min_update_norm', 'nd1', 'nd2'])
+@pytest.mark.parametrize('case', ['max_iters0', 'max_iters1', 'max_iters2', 'min_cost', 'min_update_norm', 'nd1', 'nd2',
+                                  'pipeline_nd1', 'pipeline_max_iters0'])
 def test_stopping_rule_edges(vga, case, record_property):
     host = vga['host']['u8']
     R0, t0 = _xi_pose(XI0)
     kw = {}
-    if case.startswith('max_iters'):
+    if case == 'pipeline_nd1':    # the pipeline's options: best parameters kept and restored in the same (first) iteration
+        kw = dict(max_nondecreasing_steps=1)
+    elif case == 'pipeline_max_iters0':       # ... and the iteration limit ends it while the count of bad steps is running
+        kw = dict(max_iters=0)
+    elif case.startswith('max_iters'):
         kw = dict(max_iters=int(case[-1]), allow_nondecreasing_steps=False, min_cost_decrease=1.5)
     elif case == 'min_cost':
         c0 = float(po.normal_equations_ld(host[1]['tb'], host[1]['im_track'], VAR, VAR, R0, t0, 3, 10.)['cost'])
@@ -365,7 +370,7 @@ def test_stopping_rule_edges(vga, case, record_property):
         kw = dict(max_nondecreasing_steps=2, min_cost_decrease=0.95, linesearch_max_iters=10)
     opt = _options(**kw)
     want, pose, its, hist, worst, perr = _compare_solve(vga['t'], host, [1], [0], opt, 3, 10., R0, t0)
-    if case.startswith('max_iters'):
+    if case.startswith('max_iters') or case == 'pipeline_max_iters0':
         assert its == [opt.max_iters + 1]
     elif case in ('min_cost', 'min_update_norm'):
         assert its == [1]

@@ -43,11 +43,14 @@ OPTION_SETS = [
     dict(PIPELINE, max_nondecreasing_steps=2, min_cost_decrease=0.9),         # best parameters restored early
     dict(PIPELINE, min_update_norm=1e-3),                                     # the step norm ends it
     dict(PIPELINE, min_cost=1e6),                                             # the cost threshold ends it at once
+    dict(PIPELINE, max_nondecreasing_steps=1),                                # best kept and restored in the same iteration
+    dict(PIPELINE, max_iters=0),                                              # one iteration, whatever it does
 ]
+# every set but the last two at three sizes; those two at the smallest (one workgroup with a partly filled tail)
+SOLVES = [(k, n, seed) for n, seed in [(256, 3), (2048, 4), (40, 5)] for k in range(8)] + [(8, 40, 5), (9, 40, 5)]
 
 
-@pytest.mark.parametrize('num_pts,seed', [(256, 3), (2048, 4), (40, 5)])
-@pytest.mark.parametrize('k', range(len(OPTION_SETS)))
+@pytest.mark.parametrize('k,num_pts,seed', SOLVES)
 def test_one_launch_solve_equals_the_iteration_by_iteration_loop(num_pts, seed, k):
     """Same decisions, same numbers: cost history from entry 1 on and the final pose are bit-identical (entry 0, the start
     cost, comes from the cost kernel in the host-driven loop and from the iteration kernel's own sum here: equal to

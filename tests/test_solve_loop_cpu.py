@@ -1,9 +1,12 @@
 """device_solve (pyslam_amd/problem.py) -- the Python statement of Problem.solve's loop (reference pyslam/problem.py:130-178) -- on a
 scripted device: the stopping rules, the best-parameter bookkeeping and what the loop tells the core about its own future
-(set_solve_horizon, set_expect_next: the rules ps_solve applies in C, csrc/ps_abi_solver.h).  No GPU."""
+(set_solve_horizon, set_expect_next: the rules ps_solve applies in C, csrc/ps_abi_solver.h); the generic host path of
+Problem.solve on the same cases.  No GPU."""
+import numpy as np
 import pytest
 
-from pyslam_amd.problem import Options, device_solve, solve_horizon
+from pyslam_amd.lowering import NotLowerable
+from pyslam_amd.problem import Options, Problem, device_solve, solve_horizon
 
 
 class ScriptedDevice:
@@ -91,6 +94,40 @@ def test_python_loop_follows_the_reference_rules_and_announces_its_next_call(kw,
         if opt.allow_nondecreasing_steps:
             nd = nd + 1 if hist[it] >= opt.min_cost_decrease * hist[it - 1] else 0
     assert len(calls) == 3 * (len(hist) - 1) + 1 and calls[-1] == ('expect', False)
+
+
+class ScriptedHostProblem(Problem):
+    """A Problem without a typed kernel whose iterations return a prescribed cost sequence and a step of 1 on its one
+    parameter: after k updates the parameter reads k."""
+
+    def __init__(self, opt, costs):
+        super().__init__(opt)
+        self.costs, self.k = list(costs), 0
+        self.param_dict['x'] = np.zeros(1)
+
+    def _get_device(self, param_dict=None):
+        raise NotLowerable('scripted')
+
+    def _eval_cost_host(self, param_dict=None):
+        return self.costs[0]
+
+    def solve_one_iter(self):
+        self.k += 1
+        self._update_partition_dict = self._get_update_partition_dict()
+        return np.ones(1), self.costs[self.k]
+
+
+@pytest.mark.parametrize('kw,costs', CASES)
+def test_generic_host_path_follows_the_reference_rules(kw, costs):
+    opt = Options()
+    for k, v in kw.items():
+        setattr(opt, k, v)
+    problem = ScriptedHostProblem(opt, costs)
+    params = problem.solve()
+    want, best_at = reference_loop(costs, opt)
+    assert problem._cost_history == want and problem.k == len(want) - 1
+    # the parameters left behind: best_params where the reference restores them, else those of the last iteration
+    assert params is problem.param_dict and params['x'][0] == (best_at if best_at is not None else len(want) - 1)
 
 
 def test_solve_horizon_table():
