@@ -38,14 +38,21 @@ def project(pts, cam5):
         return np.stack([fu * pts[:, 0] * iz + cu, fv * pts[:, 1] * iz + cv, third], axis=1)
 
 
+def reprojection_errors(T_stacked, pts_1, obs_2, cam5):
+    """Squared (u, v, d) reprojection errors (H, N) of every transform over every point: what ransac_cost holds against the
+    threshold (non-finite where a point, an observation or a transform is)."""
+    out = np.zeros((len(T_stacked), len(pts_1)))
+    with np.errstate(all='ignore'):
+        for h, T in enumerate(T_stacked):
+            pred = project(T[:3, :3].dot(pts_1.T).T + T[:3, 3], cam5)
+            out[h] = ((pred - obs_2) ** 2).sum(axis=1)
+    return out
+
+
 def ransac_cost(T_stacked, pts_1, obs_2, cam5, thresh):
     """Boolean (H, N) inlier masks, reference ransac.py:153-165."""
-    out = np.zeros((len(T_stacked), len(pts_1)), dtype=bool)
-    for h, T in enumerate(T_stacked):
-        pred = project(T[:3, :3].dot(pts_1.T).T + T[:3, 3], cam5)
-        with np.errstate(invalid='ignore'):
-            out[h] = ((pred - obs_2) ** 2).sum(axis=1) < thresh
-    return out
+    with np.errstate(invalid='ignore'):
+        return reprojection_errors(T_stacked, pts_1, obs_2, cam5) < thresh
 
 
 def perform_ransac(pts_1, pts_2, obs_2, rand_idx, cam5, thresh):

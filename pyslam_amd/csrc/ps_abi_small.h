@@ -13,6 +13,7 @@ int ps_ransac_transforms(const double* pts_1, const double* pts_2, int32_t batch
     HIP_OK(hipMemcpy(b.p, pts_2, nb, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_ransac_transforms, dim3(cdiv(batch, 64)), dim3(64), 0, 0, batch, n, a.as<double>(), b.as<double>(),
                        t.as<double>());
+    HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpy(T_out, t.p, (size_t)batch * 16 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -33,6 +34,7 @@ int ps_ransac_cost(const double* T, int32_t num_hyp, const double* pts_1, const 
     hipLaunchKernelGGL(k_ransac_hypotheses, dim3(num_hyp), dim3(256), 0, 0, num_pts, 0, (const int32_t*)nullptr,
                        dp.as<double>(), (const double*)nullptr, dobs.as<double>(), dcam.as<double>(), thresh,
                        dT.as<double>(), dcnt.as<int32_t>(), dmask.as<uint8_t>());
+    HIP_OK(hipGetLastError());
     if (masks) HIP_OK(hipMemcpy(masks, dmask.p, (size_t)num_hyp * num_pts, hipMemcpyDeviceToHost));
     if (counts) HIP_OK(hipMemcpy(counts, dcnt.p, (size_t)num_hyp * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIP_OK(hipDeviceSynchronize());
@@ -62,8 +64,10 @@ int ps_ransac_frame_to_frame(const double* pts_1, const double* pts_2, const dou
     hipLaunchKernelGGL(k_ransac_hypotheses, dim3(num_hyp), dim3(256), 0, 0, num_pts, set_size, didx.as<int32_t>(),
                        dp1.as<double>(), dp2.as<double>(), dobs.as<double>(), dcam.as<double>(), thresh,
                        dT.as<double>(), dcnt.as<int32_t>(), dmask.as<uint8_t>());
+    HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(256), 0, 0, num_hyp, num_pts, dcnt.as<int32_t>(), dT.as<double>(),
                        dmask.as<uint8_t>(), dbest.as<int32_t>(), dTb.as<double>(), dbm.as<uint8_t>());
+    HIP_OK(hipGetLastError());
     int32_t bi[2];
     HIP_OK(hipMemcpy(bi, dbest.p, sizeof(bi), hipMemcpyDeviceToHost));
     if (best_index) *best_index = bi[0];

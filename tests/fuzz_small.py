@@ -1,5 +1,6 @@
 """Randomised sweeps of the two small device paths behind SURVEY 8f ranks 3 and 4 against their oracles:
-  * frame-to-frame RANSAC: random two-frame scenes, outlier fractions, point counts and sample draws;
+  * frame-to-frame RANSAC: random two-frame scenes, outlier fractions, point counts and sample draws (counts and winner exactly the
+    oracle's outside the 1e-6 margin of the threshold; the shapes and edges one by one: tests/test_gpu_ransac_edges.py);
   * dense photometric alignment: random image sizes, cameras (stereo / RGB-D), poses, stiffnesses, gradient thresholds
     and losses -- normal equations and one Gauss-Newton step (both parameter forms).
 usage: python tests/fuzz_small.py [cases] [seed0]"""
@@ -35,12 +36,18 @@ def ransac_case(rng, case):
     T_o, counts_o, best_o, mask_o = ro.perform_ransac(r.pts_1, r.pts_2, r.obs_2, idx, cam5, float(r.ransac_thresh))
     well = ro.sample_conditioning(r.pts_1, r.pts_2, idx) > 1e-3          # 3-point sets that determine the rotation
     e_T = np.abs(T_all[well] - T_o[well]).max() if well.any() else 0.
-    # a count may differ by a point sitting on the threshold to rounding; the winner must be the oracle's when unique
-    dc = np.abs(counts[well].astype(int) - counts_o[well].astype(int)).max() if well.any() else 0
-    ok = e_T < 1e-8 and dc <= 1
-    if ok and well.all() and (np.ptp(np.sort(counts_o)[-2:]) > 1 if H > 1 else True):
-        ok = best == best_o and abs(count - counts_o[best_o]) <= 1
-    return ok, 'ransac N %d H %d: |T - T_oracle| %.1e, count diff %d' % (N, H, e_T, dc)
+    # the margin rule (tests/test_gpu_twoview.py): a pair whose oracle squared error lies within 1e-6 relative of the threshold may
+    # fall on either side; outside it the counts are the oracle's, and so is the winner whenever the oracle's maximum is unique
+    thresh = float(r.ransac_thresh)
+    err = ro.reprojection_errors(T_o, r.pts_1, r.obs_2, cam5)
+    near, inl = np.abs(err - thresh) <= 1e-6 * thresh, err < thresh
+    lo, hi = (inl & ~near).sum(axis=1), (inl | near).sum(axis=1)
+    dc = int(((counts < lo) | (counts > hi))[well].sum())
+    ok = e_T < 1e-8 and dc == 0
+    top = int(np.argmax(lo))
+    if ok and well.all() and (lo[top] > np.delete(hi, top).max() if H > 1 else True):
+        ok = best == top and lo[top] <= count <= hi[top]
+    return ok, 'ransac N %d H %d: |T - T_oracle| %.1e, counts off the oracle\'s %d, pairs in the margin %d' % (N, H, e_T, dc, near.sum())
 
 
 def photo_case(rng, case):

@@ -198,3 +198,48 @@ def test_errors_and_imports():
         nat.require_gpu = real
     lp = twoview.two_view_tables(cam, np.identity(4), obs_1[:5], obs_2[:5])
     assert lp.num_poses == 2 and (lp.pose_rid < 0).all() and lp.num_var_points == 5 and lp.num_obs == 10 and lp.cams[0, 4] == -2.
+
+
+# ---- the conditions tests/test_gpu_ransac_edges.py relies on, for every committed seed and shape (tests/ransac_scenes.py) ----------
+
+def test_edge_scenes_have_nothing_in_the_margin():
+    import ransac_scenes as rs
+    assert [(n, h) for n, h, _, _ in rs.TV_SWEEP] == [(67, 255), (67, 257), (67, 513), (9, 64), (256, 64)]
+    for n, h, seed, sseed in rs.TV_SWEEP:
+        obs_1, obs_2 = rs.tv_scene(n, seed)
+        samples = rs.tv_samples(n, h, sseed)
+        assert samples.shape == (h, 8) and obs_1.shape == (n, 2)
+        for refit in (True, False):
+            ref, near, worst = rs.tv_oracle(obs_1, obs_2, samples, refit)
+            print('N = {}, H = {}, refit {}: pairs in the margin {}, worst sigma_8 / sigma_1 {:.2e}, winner {} with {}'.format(
+                n, h, refit, near, worst, ref['best'], ref['count']))
+            assert near == 0 and not ref['degenerate'].any() and ref['raw_count'] > 0
+            assert worst > 1e-9                                # three decades off the degeneracy rule (1e-12): no flag hangs on rounding
+
+
+def test_edge_scenes_tie_tables_and_non_finite_rows():
+    import ransac_scenes as rs
+    n, h, seed, sseed = rs.TV_TIES
+    obs_1, obs_2 = rs.tv_scene(n, seed)
+    samples = rs.tv_samples(n, h, sseed)
+    ref, near, worst = rs.tv_oracle(obs_1, obs_2, samples)
+    w, l = rs.winner_and_loser(ref)
+    assert near == 0 and rs.unique_winner(ref['counts']) and not ref['degenerate'][w] and not ref['degenerate'][l]
+    assert ref['counts'][l] < ref['counts'][w] // 2
+    alone, near_alone, _ = rs.tv_oracle(obs_1, obs_2, samples[w:w + 1])
+    assert near_alone == 0 and alone['raw_count'] == ref['counts'][w] >= 8
+    for hh, positions in rs.TIE_POSITIONS:
+        tied = ep.ransac(obs_1, obs_2, CAM, rs.tie_table(samples, w, l, hh, positions), 4.0)
+        assert tied['best'] == min(positions) and np.array_equal(tied['E'], alone['E']) and np.array_equal(tied['mask'], alone['mask'])
+    # non-finite observations: the restatement flags their rows, never counts them, and stays finite
+    obs_1, obs_2, planted = rs.tv_nonfinite_scene()
+    idx, rows = rs.tv_nonfinite_samples(planted)
+    assert not np.isfinite(obs_1[planted[0]]).any() and np.isinf(obs_2[planted[1]]).all() and np.isnan(obs_2[planted[2], 1])
+    ref, near, worst = rs.tv_oracle(obs_1, obs_2, idx)
+    assert near == 0 and worst > 1e-9 and np.where(ref['degenerate'])[0].tolist() == rows
+    assert not ref['counts'][rows].any() and ref['best'] not in rows and rs.unique_winner(ref['counts'])
+    assert not (ref['dist'][:, planted] < 4.0).any() and not ref['mask'][planted].any()
+    for key in ('T_21', 'E', 'E_all', 'parallax_deg'):
+        assert np.isfinite(ref[key]).all(), key
+    only, _, _ = rs.tv_oracle(obs_1, obs_2, idx[rows])
+    assert only['degenerate'].all() and only['best'] == 0 and only['count'] == 0 and np.isfinite(only['T_21']).all()
