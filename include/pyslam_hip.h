@@ -488,12 +488,20 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
                               launch per solve (csrc/ps_k_xcg_persist.h): matrix in registers / LDS, w, partials and records exchanged
                               in-launch; 0: one launch per iteration (k_xcg_fused1).  Time-outs as "cg_persist"
      "pose_xcd"           [1] the pose pass's work items in eight contiguous ranges, one per XCD (0: item = workgroup); speed only
+     "lin_zero_list"      [1] a linearisation zeroes only what it accumulates into -- the diagonal blocks of S, blocks a factor or a host
+                              row adds into, pattern blocks no Schur pair writes, g, the cost and status words -- from trailing
+                              workgroups of the pose pass; every other block is stored by the pair kernel.  Live on a handle with the
+                              untiled pipelined pair kernel ("schur_pipeline"), SE(3) poses and no landmark shard (ps_get_option tells);
+                              every other handle, and 0, keep the fill over all of [S | g | cost | status].  Speed only
      "lm_packed" [1], "band_part" [1], "band_part_chunk" [0 auto], "sync_refactor" [1], "hold_across_steps" [1]: round-5 kernels and
                               schedules against their predecessors (DESIGN.md sections 0 and 3)
      "cg_force_restart"   [0] tests: end the first pass of a synchronous reduced solve at 1e-4 and restart from the true residual
      "cg_lds", "profile_every", "big_chol", "cg_margin", "pcg_chunk", "cg_split_min_rows", "cg_explicit_min_rows": implementation switches (see ps_set_option in csrc/ps_abi_solver.h)
      "cg_ablate", "schur_ablate", "lm_ablate": timing experiments only (results are wrong under ablation) */
 int ps_set_option(ps_problem* h, const char* name, double value);
+/* What an option comes to on this handle.  "lin_zero_list": 1 if linearisations zero by the list, 0 if they keep the fill;
+   "lin_zero_launches" / "lin_fills": linearisations so far that did the one / the other. */
+int ps_get_option(ps_problem* h, const char* name, double* value);
 
 /* hipEvent stage timers on the handle's stream (the reference has no tracing). */
 int ps_set_profiling(ps_problem* h, int enabled);

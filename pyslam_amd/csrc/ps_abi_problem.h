@@ -825,6 +825,24 @@ static int problem_create(const ps_problem_desc* d_in, const ps_host_rows_desc* 
         h->nes = (int)eslots.size();
         if (h->upload(&h->eslots, eslots) || h->upload(&h->eptr, eptr) || h->upload(&h->eslot_diag, ediag) ||
             h->upload(&h->eitems, eitems) || h->upload(&h->gptr, gptr) || h->upload(&h->gitems, gitems)) return -1;
+        // ---- the slots of S a linearisation accumulates into (option "lin_zero_list"), from the structure alone: an
+        // off-diagonal slot that exactly ONE pair item of the untiled list writes is stored with `=` (k_schur_pairs_db); a
+        // diagonal slot, a slot a factor or a host row adds into, a slot no pair item writes (an extra pattern block, a block
+        // that exists through a factor only) and a slot with more than one writer are accumulated and must start at zero
+        if (D == 6 && ntiles == 1 && nnzb > 0) {
+            std::vector<uint8_t> writers((size_t)nnzb, 0);     // pair items that write the slot, saturating at 2
+            for (const PairItem& it : pitm) {
+                if (it.slot >= 0 && writers[it.slot] < 2) ++writers[it.slot];
+                if (it.slotT >= 0 && it.slotT != it.slot && writers[it.slotT] < 2) ++writers[it.slotT];
+            }
+            for (int32_t s : eslots) if (s >= 0) writers[s] = 2;
+            for (int r = 0; r < nr; ++r) writers[diag_slot[r]] = 2;
+            std::vector<int32_t> zl;
+            for (int b = 0; b < nnzb; ++b) if (writers[b] != 1) zl.push_back(b);
+            h->nzero_slots = (int)zl.size();
+            if (!zl.empty() && h->upload(&h->zero_slots, zl)) return -1;
+        }
+        h->has_extra_pairs = d->num_extra_pairs > 0;
     }
 
     lap("factor lists");
@@ -924,6 +942,7 @@ static int problem_create(const ps_problem_desc* d_in, const ps_host_rows_desc* 
         !ps_pool().take(ps_pool().side_streams, &h->ldi_stream))
         HIP_OK(hipStreamCreateWithFlags(&h->ldi_stream, hipStreamNonBlocking));
     lap("scalars + final sync");
+    relook_launch_gates(h);
     guard.ok = true;
     *out = h;
     return 0;

@@ -57,6 +57,7 @@ static int ensure_shard_pack(ps_problem* h) {
     h->nup = (long)up.size();
     h->pack_count = h->nup * DD + (long)nr * h->D + 2 + 1;
     if (h->upload(&h->up_slot, up) || h->upload(&h->upT_slot, upT) || h->alloc(&h->shard_pack, (size_t)h->pack_count)) return -1;
+    relook_launch_gates(h);                                  // (a landmark shard from here on: it keeps the fill over all of S)
     return 0;
 }
 
@@ -311,6 +312,7 @@ int ps_set_collective(ps_problem* h, void* nccl_all_reduce_fn, void* nccl_comm) 
     if (h->hybrid && nccl_comm) return fail("a hybrid handle (host rows) is not landmark-sharded");
     h->nccl_allreduce = (ps_problem::allreduce_fn)nccl_all_reduce_fn;
     h->nccl_comm = nccl_comm;
+    relook_launch_gates(h);
     return 0;
 }
 
@@ -963,7 +965,20 @@ int ps_set_option(ps_problem* h, const char* name, double value) {
     else if (n == "cg_split_min_rows") { h->cg_split_min_rows = (int)value; h->coarse_built = false; }
     else if (n == "cg_explicit_min_rows") { h->cg_explicit_min_rows = (int)value; h->coarse_built = false; }
     else if (n == "pcg_chunk") { if (value < 1 || value > 4096) return fail("pcg_chunk out of range"); h->pcg_chunk = (int)value; }
+    else if (n == "lin_zero_list") h->lin_zero_list = value != 0.0;
     else return fail("unknown option: " + n);
+    relook_launch_gates(h);
+    return 0;
+}
+
+// what an option comes to on THIS handle (the launch gates: 1 = the handle is eligible and the option is on)
+int ps_get_option(ps_problem* h, const char* name, double* value) {
+    if (!h || !name || !value) return fail("null argument");
+    const std::string n(name);
+    if (n == "lin_zero_list") *value = h->lin_zero_gate ? 1.0 : 0.0;
+    else if (n == "lin_fills") *value = (double)h->lin_fills;
+    else if (n == "lin_zero_launches") *value = (double)h->lin_zero_launches;
+    else return fail("ps_get_option: no read-back for option: " + n);
     return 0;
 }
 

@@ -227,6 +227,16 @@ struct ps_problem {
     double* red = nullptr;          // [S (nnzb*D*D) | g (nr*D) | cost]
     long red_count = 0;
     double *S = nullptr, *g = nullptr, *red_cost = nullptr;
+    // option "lin_zero_list": the slots of S that a linearisation ACCUMULATES into (diagonal blocks, blocks a factor or a host
+    // row adds into, blocks of the pattern no pair item writes); every other slot is stored with `=` by exactly one pair item
+    // of the untiled pair kernel and needs no zero in front.  Trailing workgroups of the pose pass zero these, g, the cost
+    // words and the status words in place of the fill over all of [S | g | cost | status] (ps_host_cg.h: linearize)
+    int32_t* zero_slots = nullptr;
+    int nzero_slots = 0;
+    bool has_extra_pairs = false;   // created with extra pattern blocks: a landmark shard (pyslam_amd/distributed.py)
+    int lin_zero_list = 1;          // the option as set
+    bool lin_zero_gate = false;     // ... and whether this handle is eligible (relook_launch_gates)
+    long lin_fills = 0, lin_zero_launches = 0;   // linearisations that ran the fill / that zeroed by the list
     std::vector<int32_t> h_row_ptr, h_col_idx;
     std::vector<int32_t> h_vid_of_slot;   // landmarks are stored in locality order; external order is vid
     // pcg
@@ -654,6 +664,15 @@ inline void cov_release(ps_problem* h) {
     hipFree(h->cov_buf);
     h->cov_buf = nullptr;
     h->cov_sigma_epoch = -1;
+}
+
+// which launches a linearisation issues is decided when an option (or the handle's role: a collective, a shard buffer)
+// changes, not per call.  "lin_zero_list": only where the split of S into stored and accumulated slots holds -- the untiled
+// pipelined pair kernel writes every block it owns with `=` -- and the handle is no landmark shard (a shard's system is
+// packed, exchanged and summed over slots its own pairs never touch: it keeps the fill over everything)
+inline void relook_launch_gates(ps_problem* h) {
+    const bool shard = (h->nccl_allreduce && h->nccl_comm) || h->seg_allgather || h->shard_pack || h->has_extra_pairs;
+    h->lin_zero_gate = h->lin_zero_list && h->zero_slots && !h->Spart && h->schur_pipeline && h->npitems > 0 && h->D == 6 && !shard;
 }
 
 #include "ps_host_cg.h"

@@ -1037,8 +1037,20 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
         HIP_OK(hipStreamWaitEvent(h->stream, h->ev_ldi_sread, 0));
         h->ldi_sread_pending = false;
     }
-    HIP_OK(hipMemsetAsync(h->red, 0, h->red_count * sizeof(double) + ST_NWORDS * sizeof(int32_t), h->stream));   // [S | g | cost | status]
-    if (h->nv > 0 && !lm_done) {
+    // option "lin_zero_list" (relook_launch_gates): no fill over all of S -- the pair kernel stores every block it owns; what is
+    // accumulated into is zeroed by trailing workgroups of the pose pass.  The status words go with them unless a landmark pass
+    // runs between here and the pose pass: it raises ST_LM_FAIL, so then they are cleared in front of it as before.  (A pass that
+    // ran ahead in the previous tail reports through the pinned words -- lin_lmfail_tag --, its status word is cleared either way.)
+    const bool zero_by_list = h->lin_zero_gate;
+    const bool lm_here = h->nv > 0 && !lm_done;
+    if (!zero_by_list) {
+        HIP_OK(hipMemsetAsync(h->red, 0, h->red_count * sizeof(double) + ST_NWORDS * sizeof(int32_t), h->stream));   // [S | g | cost | status]
+        ++h->lin_fills;
+    } else {
+        if (lm_here) HIP_OK(hipMemsetAsync(h->status, 0, ST_NWORDS * sizeof(int32_t), h->stream));
+        ++h->lin_zero_launches;
+    }
+    if (lm_here) {
         StageTimer t(h, PS_ST_LANDMARK);
         const ObsWide wl{h->sidx_l, h->stiff_tab};
 #define PS_LM_LAUNCH(W) hipLaunchKernelGGL(k_landmark_pass<W>, dim3(cdiv(h->nv, 256 / PS_LM_GROUP)), dim3(256), 0, h->stream, h->nv, h->lm_ptr, \
@@ -1060,12 +1072,19 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
         // (option "pose_xcd", default on: the pose-ordered items in eight contiguous ranges, one per XCD -- ps_k_linearize.h)
         const int per_xcd = h->pose_xcd ? cdiv(h->npitems, 8) : 0;
         const int nblk = per_xcd ? 8 * per_xcd : h->npitems;
+        // (lin_zero_list: + the workgroups that zero the accumulated blocks of S and [g | cost (| status)], 256 doubles each)
+        static_assert(ST_NWORDS % 2 == 0, "the status words are cleared as doubles");
+        const int ntail = zero_by_list ? h->nr * 6 + 2 + (lm_here ? 0 : ST_NWORDS / 2) : 0;
+        const int nzs = zero_by_list ? h->nzero_slots : 0;
+        const int nzblk = zero_by_list ? cdiv((long)nzs * 36 + ntail, 256) : 0;
         if (h->wide_obs)
-            hipLaunchKernelGGL(k_pose_pass<true>, dim3(nblk), dim3(256), 0, h->stream, h->pitems, h->pobs,
-                               h->poses, h->points, h->ogroups, h->Cinv, h->cvec, h->ppartial, lambda != 0.0 ? 1 : 0, wp, h->npitems, per_xcd);
+            hipLaunchKernelGGL(k_pose_pass<true>, dim3(nblk + nzblk), dim3(256), 0, h->stream, h->pitems, h->pobs,
+                               h->poses, h->points, h->ogroups, h->Cinv, h->cvec, h->ppartial, lambda != 0.0 ? 1 : 0, wp, h->npitems, per_xcd,
+                               nblk, (const int32_t*)h->zero_slots, nzs, h->S, h->g, ntail);
         else
-            hipLaunchKernelGGL(k_pose_pass<false>, dim3(nblk), dim3(256), 0, h->stream, h->pitems, h->pobs,
-                               h->poses, h->points, h->ogroups, h->Cinv, h->cvec, h->ppartial, lambda != 0.0 ? 1 : 0, wp, h->npitems, per_xcd);
+            hipLaunchKernelGGL(k_pose_pass<false>, dim3(nblk + nzblk), dim3(256), 0, h->stream, h->pitems, h->pobs,
+                               h->poses, h->points, h->ogroups, h->Cinv, h->cvec, h->ppartial, lambda != 0.0 ? 1 : 0, wp, h->npitems, per_xcd,
+                               nblk, (const int32_t*)h->zero_slots, nzs, h->S, h->g, ntail);
         // tiled Schur: the combine launch also finalizes the poses (unless a task writes a diagonal block)
         fin_in_combine = h->Spart && h->npair_items > 0 && !h->has_diag_tasks && h->D == 6;
         // untiled Schur with the pipelined pair kernel: its trailing workgroups finalize the poses

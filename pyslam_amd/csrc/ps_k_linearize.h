@@ -237,12 +237,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PS_POSE_WAV
     const double* __restrict__ poses, const double* __restrict__ points,
     const ObsGroup* __restrict__ groups, const double* __restrict__ Cinv,
     const double* __restrict__ cvec, double* __restrict__ partial, int want_diag /* lambda != 0: the six damping sums too */,
-    ObsWide wide, int nitems, int per_xcd /* > 0: XCD-major order of the items (round 6), 0: item = workgroup */)
+    ObsWide wide, int nitems, int per_xcd /* > 0: XCD-major order of the items (round 6), 0: item = workgroup */,
+    // option "lin_zero_list": workgroups from zero_first on do no pose work; they zero what the kernels BEHIND this launch
+    // accumulate into -- the listed blocks of S and the ntail doubles at ztail ([g | cost | status]) -- in place of a fill over
+    // the whole reduced system in front of the linearisation.  Nothing in this launch reads S or g.
+    int zero_first, const int32_t* __restrict__ zero_slots, int nzero_slots, double* __restrict__ S, double* __restrict__ ztail, int ntail)
 {
     __shared__ double red[4][PS_NPOSE_ACC];
 #if PS_POSE_TRANSPOSE
     __shared__ double tr[4][64 * 17];
 #endif
+    if ((int)blockIdx.x >= zero_first) {
+        const int e = ((int)blockIdx.x - zero_first) * 256 + (int)threadIdx.x, ns = 36 * nzero_slots;
+        if (e < ns) { const int k = e / 36; S[(size_t)zero_slots[k] * 36 + (e - 36 * k)] = 0.0; }
+        else if (e - ns < ntail) ztail[e - ns] = 0.0;
+        return;
+    }
     // Round 6: workgroup b runs on XCD b % 8 (observed dispatch rule; affects speed only).  The items are in pose order and a pose's
     // observations gather points / C^-1 / c of the landmarks it sees -- with item = workgroup every XCD walked ALL poses and pulled
     // the whole landmark table through its own L2 (C3: 60 MB of fabric traffic for 16 MB of records, round-5 verdict weak #4).  With

@@ -480,6 +480,12 @@ class DeviceProblem:
     def set_option(self, name, value):
         nat.check(self._lib.ps_set_option(self._h, name.encode(), float(value)))
 
+    def get_option(self, name):
+        """What an option comes to on this handle (ps_get_option: the launch gates and their counters)."""
+        v = C.c_double()
+        nat.check(self._lib.ps_get_option(self._h, name.encode(), C.byref(v)))
+        return v.value
+
     # ---- tracing -------------------------------------------------------
     def set_profiling(self, level=2):
         """0 off; 1 = hipEvents around the whole iteration and the Schur kernel only (cheap);
