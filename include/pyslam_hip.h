@@ -427,77 +427,92 @@ int ps_debug_factor_blocks(ps_problem* h, double* r, double* j1, double* j2);
    structure build against the host builder bit for bit (tests/test_gpu_create.py); no reference counterpart. */
 int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* count);
 
-/* Tuning knobs (defaults in brackets):
-     "pcg_variant"        [1] fused single-launch-per-iteration CG on the block-Jacobi scaled system; 0 = classic two-launch PCG
-     "coarse_groups"      [-1 auto] hat-function intervals of the two-level preconditioner, 0 = off
-     "coarse_basis"       [1] coarse unknowns are body-frame twists (P_iq = w L_i^T Ad(T_i)); 0 = hats in scaled coordinates
-     "coarse_lag"         [1] whole-iteration calls build the two-level system with the previous iteration's coarse factor
-     "direct_max_unknowns"[90] reduced systems up to this size are solved by a dense Cholesky instead of CG (0 = never)
-     "fused_motion_only"  [1] problems without variable landmarks / pose factors: one launch per iteration
-     "cg_explicit"        [1] long sparse chains: apply the two-level preconditioner (k_xcg_*) instead of folding it in
-     "coarse_lag_x"       [1] ... and with the previous iteration's basis and X = P L_c^-T too: three set-up launches (k_rows_setup)
-     "coarse_refresh_every" [1] explicit two-level PCG: only every k-th lagged set-up takes the newest coarse inverse and starts the
+/* Tuning knobs.  [default; accepted values]: "0 / 1" is stored as value != 0; a range is refused outside it and truncated to
+   an integer inside it; "any" is truncated and never refused.  One table holds every name with its parse rule, bounds, refusal
+   and what a change invalidates on the handle: csrc/ps_options.h (checked on the CPU by tests/test_options_host.py).  Every
+   name but "expect_next" and "solve_horizon" drops what was computed ahead for the next call.
+     "pcg_variant"        [1; 0 or 1 exactly] fused single-launch-per-iteration CG on the block-Jacobi scaled system; 0 = classic two-launch PCG
+     "coarse_groups"      [-1 auto; -1 <= value < 1024] hat-function intervals of the two-level preconditioner, 0 = off; above 63 only for the explicit
+                              two-level PCG.  The coarse level is planned again by the next solve
+     "coarse_basis"       [1; 0 / 1] coarse unknowns are body-frame twists (P_iq = w L_i^T Ad(T_i)); 0 = hats in scaled coordinates
+     "coarse_lag"         [1; 0 / 1] whole-iteration calls build the two-level system with the previous iteration's coarse factor
+     "direct_max_unknowns"[90; 0 .. 90] reduced systems up to this size are solved by a dense Cholesky instead of CG (0 = never)
+     "direct_fused"       [1; 0 / 1] ... in one launch (k_direct_solve); 0: three
+     "fused_motion_only"  [1; 0 / 1] problems without variable landmarks / pose factors: one launch per iteration
+     "cg_explicit"        [1; 0 / 1] long sparse chains: apply the two-level preconditioner (k_xcg_*) instead of folding it in
+     "coarse_lag_x"       [1; 0 / 1] ... and with the previous iteration's basis and X = P L_c^-T too: three set-up launches (k_rows_setup)
+     "coarse_refresh_every" [1; 1 .. 16] explicit two-level PCG: only every k-th lagged set-up takes the newest coarse inverse and starts the
                               next side-stream factorisation (landmark-sharded runs whose iteration is shorter than that factorisation)
-     "coarse_auto_hold"   [1] explicit two-level PCG: while the solve has settled (last iteration changed the cost by < 1e-4
+     "coarse_auto_hold"   [1; 0 / 1] explicit two-level PCG: while the solve has settled (last iteration changed the cost by < 1e-4
                               relative) keep the lagged coarse inverse, for at most 3 set-ups in a row (no assembly, no factorisation);
                               and for as long as the caller linearises at the point (same start cost, same lambda) the inverse in use
                               was formed from.  A call whose lambda is more than a factor of four from the newest inverse's (or zero against non-zero)
                               factors its own A_c (no lag).
-     "coarse_adaptive_hold" [1] explicit two-level PCG: keep the lagged coarse inverse (no assembly, no side-stream factorisation) while the
+     "coarse_adaptive_hold" [1; 0 / 1] explicit two-level PCG: keep the lagged coarse inverse (no assembly, no side-stream factorisation) while the
                               last solve with it took at most 3 iterations more than the first one did (at most 8 set-ups in a row)
-     "xcg_restrict_fused" [1] explicit two-level PCG: three launches per iteration (restriction in the SpMV epilogue, t by recurrence)
+     "xcg_restrict_fused" [1; 0 / 1] explicit two-level PCG: three launches per iteration (restriction in the SpMV epilogue, t by recurrence)
                               instead of four
-     "lagged_inverse"     [1] reduced systems of 91 .. "ldi_max_unknowns" [2048; up to 3328: pays from ~7 iterations per solve on] unknowns (folded CG, one GPU, whole-iteration calls):
+     "lagged_inverse"     [1; 0 / 1] reduced systems of "direct_max_unknowns" + 1 .. "ldi_max_unknowns" [2048; 0 .. 3328: pays from ~7 iterations per solve on] unknowns (folded CG, one GPU, whole-iteration calls):
                               precondition the CG with a dense fp32 inverse of the PREVIOUS iteration's S, kept current on the side
                               stream by one Newton-Schulz step per iteration (two fp32 MFMA GEMMs) and seeded from the two-level
                               operator of the last standard solve; tried while the last step changed the cost by at most
-                              "ldi_cost_tol" [0.05] relative, given up (standard solver + re-seed) after "ldi_cap" [12] iterations.
+                              "ldi_cost_tol" [0.05; any double >= 0] relative, given up (standard solver + re-seed) after "ldi_cap" [12; 1 .. 64] iterations.
                               It only preconditions: the solution is the current system's at pcg_tol either way.
-     "ldi_direct"         [-1] ... seeded by a DIRECT fp64 factorisation of S on a stream of its own instead of Newton-Schulz
-                              (-1: pose graphs from the start, any problem after a rejected Newton-Schulz seed; 0 never; 1 always);
+     "ldi_direct"         [-1; any] ... seeded by a DIRECT fp64 factorisation of S on a stream of its own instead of Newton-Schulz
+                              (below 0: pose graphs from the start, any problem after a rejected Newton-Schulz seed; 0 never; above 0 always);
                               usable a fixed 2 / 4 / 6 calls later (n <= 400 / 800 / 1 536)
-     "ldi_seed_lag" [1], "ldi_seed_steps" [3], "ldi_refresh_its" [7]: schedule of the Newton-Schulz seed / refresh
-     "xcg_fused"          [1] explicit two-level PCG: ONE launch per iteration (single-reduction recurrences; the restriction, the coarse
+     "ldi_seed_lag" [1; 1 .. 16], "ldi_seed_steps" [3; 1 .. 40], "ldi_refresh_its" [7; 0 .. 64]: schedule of the Newton-Schulz seed / refresh
+     "xcg_fused"          [1; 0, 1 or 2 exactly] explicit two-level PCG: ONE launch per iteration (single-reduction recurrences; the restriction, the coarse
                               product for the nodes a workgroup needs, the prolongation and the SpMV in one kernel, the row's matrix
                               blocks requested before the scalar phase) up to 2 048 poses and 2 048 coarse unknowns, TWO beyond (scalars,
                               t and y = A_c^-1 t once, in k_xcg_f2_coarse); 2: always two; 0: three launches per iteration.
                               A breakdown of the recurrences repeats the solve in the three-launch form
-     "band_chol"          [1] explicit two-level PCG: banded factorisation + band substitutions for the coarse inverse when A_c
+     "band_chol"          [1; 0 / 1] explicit two-level PCG: banded factorisation + band substitutions for the coarse inverse when A_c
                               has at most 7 block off-diagonals (chain-like problems); 0: always the dense factorisation
-     "solve_horizon"      [-1 unknown] how many more whole-iteration calls the caller's stopping rule allows if the step about to be
+     "solve_horizon"      [-1 unknown; below 0 is -1, else truncated, at most 1e6] how many more whole-iteration calls the caller's stopping rule allows if the step about to be
                               taken turns out non-decreasing (reference problem.py:163-178); side work that pays back only over
                               several later calls (the lagged inverse's seed) is not started with fewer than three to come
-     "expect_next"        [0] the caller will ask for another whole iteration after the coming one unless a stopping rule on ||dx|| or
+     "expect_next"        [0; 0 / 1, always 0 on a hybrid handle] the caller will ask for another whole iteration after the coming one unless a stopping rule on ||dx|| or
                               the cost fires (ps_solve sets it for its own loop): with "fuse_cost" the coming call's tail runs the NEXT
                               iteration's landmark pass in place of its cost pass -- every observation evaluated once per iteration;
                               the next call's linearisation takes the pass over if the parameters have not moved since.  Does not
                               invalidate what was computed ahead (every other option does)
-     "fuse_cost"          [1] the cost of all blocks summed by the packed landmark pass itself (tails that expect a successor, the start
+     "fuse_cost"          [1; any] the cost of all blocks summed by the packed landmark pass itself (tails that expect a successor, the start
                               cost of ps_solve, ps_eval_cost) or by a cost-only pass in the same structure: the same number bit for bit;
                               2: in the tails only; 0: the grid-stride cost pass of rounds 1-4 everywhere (another summation order).
                               Needs every observation on a variable landmark with at most 16 observations, else 0 is what runs
-     "cg_persist"         [1] the folded two-level CG in ONE launch (csrc/ps_k_cg_persist.h) where the augmented system fits (<= 2 048
-                              unknowns, <= 1 024 tasks); 0: one launch per CG iteration.  "cg_persist_spin" [200000]: passes over the
+     "cg_persist"         [1; 0 / 1] the folded two-level CG in ONE launch (csrc/ps_k_cg_persist.h) where the augmented system fits (<= 2 048
+                              unknowns, <= 1 024 tasks); 0: one launch per CG iteration.  "cg_persist_spin" [200000; 0 .. 1e7]: passes over the
                               in-launch exchange before a workgroup gives up -- or one second, whichever comes first -- (then the solve is
                               repeated launch by launch and the form is not used on the handle any more:
                               ps_problem_info.cg_persist_failures).  The form is only used when its whole grid can be resident on the
                               compute units the handle's stream may use (device count, stream CU mask, occupancy of the kernel:
                               ps_problem_info.persist_cus / persist_cus_needed) and while one-launch solves of other handles of the
                               process leave them free (cg_persist_refused)
-     "xcg_persist"        [1] the explicit two-level PCG of bundle adjustments (long rows, one workgroup per compute unit of the stream: up to 2 048 poses on a whole MI355X) in ONE
+     "xcg_persist"        [1; 0 / 1] the explicit two-level PCG of bundle adjustments (long rows, one workgroup per compute unit of the stream: up to 2 048 poses on a whole MI355X) in ONE
                               launch per solve (csrc/ps_k_xcg_persist.h): matrix in registers / LDS, w, partials and records exchanged
                               in-launch; 0: one launch per iteration (k_xcg_fused1).  Time-outs as "cg_persist"
-     "pose_xcd"           [1] the pose pass's work items in eight contiguous ranges, one per XCD (0: item = workgroup); speed only
-     "lin_zero_list"      [1] a linearisation zeroes only what it accumulates into -- the diagonal blocks of S, blocks a factor or a host
+     "pose_xcd"           [1; 0 / 1] the pose pass's work items in eight contiguous ranges, one per XCD (0: item = workgroup); speed only
+     "lin_zero_list"      [1; 0 / 1] a linearisation zeroes only what it accumulates into -- the diagonal blocks of S, blocks a factor or a host
                               row adds into, pattern blocks no Schur pair writes, g, the cost and status words -- from trailing
                               workgroups of the pose pass; every other block is stored by the pair kernel.  Live on a handle with the
                               untiled pipelined pair kernel ("schur_pipeline"), SE(3) poses and no landmark shard (ps_get_option tells);
                               every other handle, and 0, keep the fill over all of [S | g | cost | status].  Speed only
-     "lm_packed" [1], "band_part" [1], "band_part_chunk" [0 auto], "sync_refactor" [1], "hold_across_steps" [1]: round-5 kernels and
-                              schedules against their predecessors (DESIGN.md sections 0 and 3)
-     "cg_force_restart"   [0] tests: end the first pass of a synchronous reduced solve at 1e-4 and restart from the true residual
-     "cg_lds", "profile_every", "big_chol", "cg_margin", "pcg_chunk", "cg_split_min_rows", "cg_explicit_min_rows": implementation switches (see ps_set_option in csrc/ps_abi_solver.h)
-     "cg_ablate", "schur_ablate", "lm_ablate": timing experiments only (results are wrong under ablation) */
+     "schur_pipeline"     [1; 0 / 1] the Schur pair kernel with two chunks per wave in flight (k_schur_pairs_db); 0: k_schur_pairs
+     "lm_packed" [1; 0 / 1], "band_part" [1; 0 / 1], "band_part_chunk" [0 auto; 0 .. 4096 nodes], "sync_refactor" [1; 0 / 1],
+     "hold_across_steps" [1; 0 / 1]: round-5 kernels and schedules against their predecessors (DESIGN.md sections 0 and 3)
+     "cg_force_restart"   [0; 0 / 1] tests: end the first pass of a synchronous reduced solve at 1e-4 and restart from the true residual
+     "cg_lds"             [1; 0 / 1] small systems: the fused CG with the whole vector through LDS (k_cg_fused_lds)
+     "big_chol"           [1; 0 / 1] coarse matrices of more than 90 unknowns: the blocked factorisation over many workgroups; 0: one workgroup
+     "profile_every"      [1; >= 1] profiling level 1 times the Schur kernel of every n-th linearisation only
+     "cg_margin"          [4; 0 .. 64] CG launches enqueued beyond the previous solve's iteration count
+     "pcg_chunk"          [8; 1 .. 4096] launch-per-iteration solves: launches between two host polls of the 'done' flag
+     "cg_split_min_rows"  [1024; any] more reduced poses than this: the coarse rows in a kernel of their own (split mode; the threshold
+                              below is never above this one), and
+     "cg_explicit_min_rows" [-1; any] ... the explicit two-level PCG instead of the folded one (-1: 400 poses for pose-graph rows, 540 for
+                              bundle-adjustment rows, 250 where the lagged inverse cannot apply).  Either has the coarse level planned again
+     "cg_ablate", "schur_ablate", "lm_ablate" [0; any]: timing experiments of the measurement build only (results are wrong under
+                              ablation); the product build accepts 0 and refuses every other value */
 int ps_set_option(ps_problem* h, const char* name, double value);
 /* What an option comes to on this handle.  "lin_zero_list": 1 if linearisations zero by the list, 0 if they keep the fill;
    "lin_zero_launches" / "lin_fills": linearisations so far that did the one / the other. */

@@ -115,7 +115,7 @@ int ps_problem_destroy(ps_problem* h) {
     for (void* p : h->allocs) hipFree(p);
     h->arena_release();            // arena block, its pinned mirror and the pinned result words go back to the process-wide pool
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
-    if (h->ev_ldi) { hipEventDestroy(h->ev_ldi); hipEventDestroy(h->ev_ldi_sread); hipEventDestroy(h->ev_ldi_ritz); }
+    if (h->ev_ldi) { hipEventDestroy(h->ev_ldi); hipEventDestroy(h->ev_ldi_sread); }
     if (h->ldi_stream && !ps_pool().give(ps_pool().side_streams, h->ldi_stream)) hipStreamDestroy(h->ldi_stream);
     if (h->side) { hipStreamSynchronize(h->side); if (!h->side_poolable || !ps_pool().give(ps_pool().side_streams, h->side)) hipStreamDestroy(h->side); hipEventDestroy(h->ev_ac); hipEventDestroy(h->ev_chol); hipEventDestroy(h->ev_acdone); }
     if (h->own_stream && h->stream && !ps_pool().give(ps_pool().streams, h->stream)) hipStreamDestroy(h->stream);
@@ -187,6 +187,8 @@ static int problem_create(const ps_problem_desc* d_in, const ps_host_rows_desc* 
     lap("device-resident tables");
 
     ps_problem* h = new ps_problem();
+    if (ps_env("PS_DIRECT_3LAUNCH")) h->direct_fused = 0;   // (measurement build: two option defaults from the environment)
+    if (ps_env("PS_LDI_SEED_LAG")) h->ldi_seed_lag = atoi(ps_env("PS_LDI_SEED_LAG"));
     struct Guard { ps_problem* h; bool ok = false; ~Guard() { if (!ok) ps_problem_destroy(h); } } guard{h};
     if (stream) h->stream = (hipStream_t)stream;
     else {
@@ -719,7 +721,7 @@ static int problem_create(const ps_problem_desc* d_in, const ps_host_rows_desc* 
     h->red_count = (long)nnzb * DD + (long)nr * D + 2;
     if (h->alloc(&h->red, (size_t)h->red_count + ST_NWORDS / 2)) return -1;       // + the status words: one memset clears both
     h->status = reinterpret_cast<int32_t*>(h->red + h->red_count);
-    h->S = h->red; h->g = h->red + (size_t)nnzb * DD; h->red_cost = h->g + (size_t)nr * D;
+    h->S = h->red; h->g = h->red + (size_t)nnzb * DD;
 
     lap("block pattern");
     // one work item (task) per (tile, block) that has pairs

@@ -267,7 +267,7 @@ int ps_set_segment_exchange(ps_problem* h, void* nccl_all_gather_fn, int32_t wor
                                vo(src_off, src_off + (n_dst ? src_ptr[n_dst] : 0));
     if (h->upload(&h->seg_mine, vm) || h->upload(&h->seg_dst, vd) || h->upload(&h->seg_src_ptr, vp) || h->upload(&h->seg_src_off, vo) ||
         h->alloc(&h->seg_in, (size_t)maxlen) || h->alloc(&h->seg_all, (size_t)maxlen * world)) return -1;
-    h->seg_world = world; h->seg_rank = rank; h->seg_maxlen = maxlen; h->seg_nmine = n_mine; h->seg_ndst = n_dst;
+    h->seg_world = world; h->seg_maxlen = maxlen; h->seg_nmine = n_mine; h->seg_ndst = n_dst;
     h->seg_allgather = (ps_problem::allgather_fn)nccl_all_gather_fn;
     return 0;
 }
@@ -899,74 +899,26 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
 // the folded / explicit crossover depends on whether the lagged dense inverse can apply (ps_host_cg.h: build_coarse): an
 // option that changes that answer has the coarse level rebuilt by the next solve
 static void relook_path(ps_problem* h) {
-    const long n = (long)h->nr * h->D;
-    const bool possible = h->ldi_enable && n <= h->ldi_max_n && n <= PS_LDI_MAXN && n > h->direct_max;
+    const bool possible = ps_ldi_possible(*h, (long)h->nr * h->D);
     if (h->coarse_built && possible != h->xmin_auto_ldi && h->cg_explicit_min_rows < 0) h->coarse_built = false;
 }
 
+// every name but the two early ones: csrc/ps_options.h (parse rule, bounds, refusal, effects per name)
 int ps_set_option(ps_problem* h, const char* name, double value) {
     if (!h || !name) return fail("null argument");
-    const std::string n(name);
     // what a caller's own loop says about its next call leaves what was computed ahead in place
-    if (n == "expect_next") { h->expect_next = value != 0 && !h->hybrid; return 0; }      // (hybrid: see ps_problem_create_hybrid)
-    if (n == "solve_horizon") { h->solve_horizon = value < 0 ? -1 : (int)std::min(value, 1e6); return 0; }
+    if (!std::strcmp(name, "expect_next")) { h->expect_next = value != 0 && !h->hybrid; return 0; }      // (hybrid: see ps_problem_create_hybrid)
+    if (!std::strcmp(name, "solve_horizon")) { h->solve_horizon = value < 0 ? -1 : (int)std::min(value, 1e6); return 0; }
     h->prelin_valid = h->prelm_valid = false;
-    if (n == "pcg_variant") { if (value != 0 && value != 1) return fail("pcg_variant must be 0 or 1"); h->pcg_variant = (int)value; }
-    else if (n == "coarse_groups") {
-        if (value < -1 || value >= PS_XCG_MAXNODES) return fail("coarse_groups out of range (-1 auto, 0 off, else number of hat intervals; above 63 only for the explicit two-level PCG, at most 1023)");
-        h->coarse_req = (int)value; h->coarse_built = false;
-    }
-#ifdef PS_MEASURE
-    else if (n == "cg_ablate") h->cg_ablate = (int)value;
-    else if (n == "schur_ablate") h->schur_ablate = (int)value;
-    else if (n == "lm_ablate") h->lm_ablate = (int)value;
-#else
-    else if (n == "cg_ablate" || n == "schur_ablate" || n == "lm_ablate") {
-        if (value != 0.0) return fail(n + ": timing experiments exist in the measurement build only (__graft_entry__.build_measure(), PYSLAM_AMD_MEASURE=1)");
-    }
-#endif
-    else if (n == "schur_pipeline") h->schur_pipeline = value != 0.0;
-    else if (n == "coarse_lag") h->coarse_lag = value != 0.0;
-    else if (n == "cg_force_restart") h->cg_force_restart = value != 0.0;
-    else if (n == "xcg_restrict_fused") h->xcg_rt = value != 0;
-    else if (n == "band_chol") { h->band_chol = value != 0; h->lci_next = -1; }
-    else if (n == "lm_packed") h->lm_packed = value != 0;
-    else if (n == "pose_xcd") h->pose_xcd = value != 0;
-    else if (n == "fuse_cost") h->fuse_cost = (int)value;       // 0 off, 1 on, 2 = in the tails only (not the start cost / ps_eval_cost)
-    else if (n == "sync_refactor") h->sync_refactor = value != 0;
-    else if (n == "hold_across_steps") h->hold_across_steps = value != 0;
-    else if (n == "band_part") { h->band_part = value != 0; h->lci_next = -1; }
-    else if (n == "band_part_chunk") { if (value < 0 || value > 4096) return fail("band_part_chunk must be 0 (automatic) .. 4096 nodes"); h->band_part_m = (int)value; h->lci_next = -1; }
-    else if (n == "coarse_auto_hold") h->xcg_auto_hold = value != 0;
-    else if (n == "coarse_adaptive_hold") h->xcg_adaptive_hold = value != 0;
-    else if (n == "xcg_fused") { if (value != 0 && value != 1 && value != 2) return fail("xcg_fused must be 0, 1 or 2"); h->xcg_fused = (int)value; }
-    else if (n == "lagged_inverse") { h->ldi_enable = value != 0; if (!h->ldi_enable) { h->ldi_cur = -1; if (h->ldi_state != 1) h->ldi_state = 0; } relook_path(h); }
-    else if (n == "ldi_max_unknowns") { if (value < 0 || value > PS_LDI_MAXN) return fail("ldi_max_unknowns out of range (0 .. 3328)"); h->ldi_max_n = (int)value; relook_path(h); }
-    else if (n == "ldi_cap") { if (value < 1 || value > 64) return fail("ldi_cap out of range (1 .. 64)"); h->ldi_cap = (int)value; }
-    else if (n == "ldi_cost_tol") { if (!(value >= 0)) return fail("ldi_cost_tol must be >= 0"); h->ldi_cost_tol = value; }
-    else if (n == "ldi_refresh_its") { if (value < 0 || value > 64) return fail("ldi_refresh_its out of range (0 .. 64)"); h->ldi_refresh_its = (int)value; }
-    else if (n == "ldi_direct") { h->ldi_direct_ok = value != 0.0; h->ldi_direct = value > 0.0; }
-    else if (n == "direct_fused") h->direct_fused = value != 0.0;
-    else if (n == "ldi_seed_lag") { if (value < 1 || value > 16) return fail("ldi_seed_lag out of range (1 .. 16)"); h->ldi_seed_lag = (int)value; }
-    else if (n == "ldi_seed_steps") { if (value < 1 || value > 40) return fail("ldi_seed_steps out of range (1 .. 40)"); h->ldi_seed_steps = (int)value; }
-    else if (n == "coarse_refresh_every") { if (value < 1 || value > 16) return fail("coarse_refresh_every must be 1..16"); h->xcg_refresh_every = (int)value; }
-    else if (n == "coarse_lag_x") { h->lagx = value != 0.0; h->lci_next = -1; h->side_todo = false; }
-    else if (n == "cg_lds") h->cg_lds = value != 0.0;
-    else if (n == "cg_persist") h->cg_persist = value != 0.0;
-    else if (n == "xcg_persist") h->xcg_persist = value != 0.0;
-    else if (n == "cg_persist_spin") { if (value < 0 || value > 1e7) return fail("cg_persist_spin out of range"); h->cp_spin = (unsigned)value; }
-    else if (n == "cg_explicit") { h->explicit_ok = value != 0.0; h->coarse_built = false; }
-    else if (n == "big_chol") h->big_chol = value != 0.0;
-    else if (n == "fused_motion_only") h->mo_fused = value != 0.0;
-    else if (n == "direct_max_unknowns") { if (value < 0 || value > 90) return fail("direct_max_unknowns must be 0..90"); h->direct_max = (int)value; }
-    else if (n == "coarse_basis") { h->coarse_basis = value != 0.0; h->lci_next = -1; h->side_todo = false; }
-    else if (n == "profile_every") { if (value < 1) return fail("profile_every must be >= 1"); h->prof_every = (int)value; }
-    else if (n == "cg_margin") { if (value < 0 || value > 64) return fail("cg_margin out of range"); h->cg_margin = (int)value; }
-    else if (n == "cg_split_min_rows") { h->cg_split_min_rows = (int)value; h->coarse_built = false; }
-    else if (n == "cg_explicit_min_rows") { h->cg_explicit_min_rows = (int)value; h->coarse_built = false; }
-    else if (n == "pcg_chunk") { if (value < 1 || value > 4096) return fail("pcg_chunk out of range"); h->pcg_chunk = (int)value; }
-    else if (n == "lin_zero_list") h->lin_zero_list = value != 0.0;
-    else return fail("unknown option: " + n);
+    const char* refusal = nullptr;
+    const int fx = ps_option_apply(*h, name, value, &refusal);
+    if (fx == PS_OPT_UNKNOWN) return fail(std::string("unknown option: ") + name);
+    if (fx == PS_OPT_REFUSED) return fail(refusal);
+    if (fx & PS_FX_COARSE_REBUILD) h->coarse_built = false;
+    if (fx & PS_FX_DROP_FACTOR) h->lci_next = -1;
+    if (fx & PS_FX_DROP_SIDE) h->side_todo = false;
+    if ((fx & PS_FX_LDI_OFF) && !h->ldi_enable) { h->ldi_cur = -1; if (h->ldi_state != 1) h->ldi_state = 0; }
+    if (fx & PS_FX_RELOOK_PATH) relook_path(h);
     relook_launch_gates(h);
     return 0;
 }
@@ -984,7 +936,7 @@ int ps_get_option(ps_problem* h, const char* name, double* value) {
 
 // Forget everything the solver carries from one whole-iteration call to the next, as if the handle had just been
 // created: the lagged coarse factor / inverse and their tags, the lagged dense inverse of S (seeds in flight are waited
-// for, then dropped), held coarse inverses, the launch-count predictions, the cost history.  Tables, parameters, options
+// for, then dropped), held coarse inverses, the launch-count predictions (PsCarried), the cost history (PsCostHistory).  Tables, parameters, options
 // and the structures built at create time stay.  The first ps_gn_iteration after this runs the exact (un-lagged) set-up,
 // exactly like the first iteration of a fresh handle.  What a caller that starts a NEW solve on a live handle calls
 // (Problem.solve; bench.py's cold solves).
@@ -992,8 +944,7 @@ int ps_reset_solver_state(ps_problem* h) {
     if (!h) return fail("null argument");
     h->prelin_valid = h->prelm_valid = false;
     if (!h->solver_touched) {                               // nothing linearised since creation / the last reset: only the history
-        h->last_cost = h->prev_cost = h->snap_cost = -1.0;
-        h->solve_horizon = -1;
+        static_cast<PsCostHistory&>(*h) = PsCostHistory{};
         return 0;
     }
     h->solver_touched = false;
@@ -1001,26 +952,10 @@ int ps_reset_solver_state(ps_problem* h) {
     if (h->side) HIP_OK(hipStreamSynchronize(h->side));
     if (h->ldi_stream) HIP_OK(hipStreamSynchronize(h->ldi_stream));
     drain_timers(h);
-    // lagged coarse level (folded and explicit forms)
-    h->lci_next = -1; h->lci_cur = 0;
-    h->side_todo = false; h->side_ready = false; h->side_pending = false; h->acdone_pending = false;
-    h->xcg_side_todo = false; h->xcg_lag_count = 0; h->xcg_held = 0;
-    h->xcg_its_ref = 0; h->xcg_good_held = 0; h->xcg_ref_pending = false;
-    h->xcg_tag[0] = h->xcg_tag[1] = -1.0; h->xcg_tag_lambda[0] = h->xcg_tag_lambda[1] = 0.0;
-    h->xcg_setup_cost = -1.0; h->xcg_setup_lambda = 0.0;
-    h->mc_active = false; h->last_setup_lagx = false; h->xf_skip = 0;
+    static_cast<PsCarried&>(*h) = PsCarried{};
+    static_cast<PsCostHistory&>(*h) = PsCostHistory{};
     if (h->lag_status) HIP_OK(hipMemsetAsync(h->lag_status, 0, ST_NWORDS * sizeof(int32_t), h->stream));
-    // lagged dense inverse
-    h->ldi_state = 0; h->ldi_cur = -1; h->ldi_next = -1; h->ldi_iter = 0; h->ldi_ready_at = 0;
-    h->ldi_side_todo = false; h->ldi_update_ok = false; h->ldi_sread_pending = false; h->ldi_refreshed = false;
-    h->ldi_last_its = h->ldi_prev_its = 0; h->ldi_rejects = 0; h->ldi_no_seed_before = 0;
-    h->ldi_tag = h->ldi_next_tag = h->ldi_call_start_cost = -1.0; h->ldi_prev_start_cost = -2.0;
-    h->ldi_moved = false; h->ldi_last_rms = 0.0;
     if (h->ldi_ready && !(h->ldi_direct_ok && h->N == 0 && h->F > 0)) h->ldi_direct = false;   // (a rejected seed had switched the direct seed on)
-    // predictions and history
-    h->last_pcg_iters = 0; h->prev_pcg_iters = -1;
-    h->last_cost = h->prev_cost = h->snap_cost = -1.0;
-    h->solve_horizon = -1;
     h->cov_ready = false;
     return 0;
 }

@@ -156,8 +156,62 @@ PersistLedger& ps_persist_ledger() { static PersistLedger* p = new PersistLedger
 }  // namespace
 
 #include "ps_host_bandpart.h"
+#include "ps_options.h"
 
-struct ps_problem {
+// ---- the handle by role -------------------------------------------------------------------------------------------------
+// ps_problem derives from three plain structs so that the struct itself says what a member is: a user option (PsOptions,
+// ps_options.h), what one whole-iteration call hands to the next (PsCostHistory, PsCarried: ps_reset_solver_state assigns
+// fresh ones), and everything else -- tables and structures built at create time or by build_coarse, counters, timers, plumbing
+// ("The handle": why a reset leaves each of those alone).
+
+// costs the whole-iteration calls returned, and what the caller's stopping rule still allows: reset even on a handle that has
+// not linearised anything since the last reset
+struct PsCostHistory {
+    double last_cost = -1.0, prev_cost = -1.0;   // costs returned by the last two ps_gn_iteration calls (-1: none / parameters replaced since)
+    double snap_cost = -1.0;        // last_cost at the time of ps_snapshot_params
+    // option "solve_horizon" (the one option outside PsOptions): how many MORE whole-iteration calls the caller's stopping rule allows if the step about to be
+    // taken does not decrease the cost enough (reference problem.py:163-178: max_nondecreasing_steps - taken - 1, or 0 without
+    // allow_nondecreasing_steps); -1 = unknown (a caller that drives ps_gn_iteration itself).  Side work that only pays back
+    // over several later calls -- the seed of the lagged dense inverse -- is not started when the solve is about to stop.
+    int solve_horizon = -1;
+};
+
+// what the solver carries from one whole-iteration call to the next.  A member that is added here is reset with the rest; the
+// initialisers ARE the reset values
+struct PsCarried {
+    // lagged coarse level (folded and explicit forms)
+    int lci_cur = 0;                // buffer the current augmented system was built with
+    int lci_next = -1;              // buffer holding (or receiving, see side_pending) the newest factor; -1: none
+    bool side_todo = false;         // the next X (from SB / the basis in buffer side_buf) is still to be formed on the side stream
+    bool side_ready = false;        // the host has synchronised with the solver stream since the side stream's inputs were enqueued
+    bool side_pending = false;      // a side-stream factorisation is in flight: wait for ev_chol before reuse
+    bool acdone_pending = false;    // explicit PCG: the side stream may still be assembling A_c from SB / the basis (wait before they are overwritten)
+    bool xcg_side_todo = false;     // explicit PCG: lagged setup whose side-stream half is not enqueued yet
+    long xcg_lag_count = 0;         // lagged set-ups since the last refresh ("coarse_refresh_every")
+    int xcg_held = 0;               // set-ups in a row that kept the inverse ("coarse_auto_hold")
+    int xcg_its_ref = 0, xcg_good_held = 0;   // CG iterations of the first solve with the inverse in use / set-ups it has been kept for
+    bool xcg_ref_pending = false;
+    double xcg_tag[2] = {-1.0, -1.0}, xcg_setup_cost = -1.0;   // start cost of the call whose A_c each inverse buffer was formed from
+    double xcg_tag_lambda[2] = {0.0, 0.0}, xcg_setup_lambda = 0.0;
+    bool mc_active = false;         // the current system was built with a lagged factor in split mode
+    bool last_setup_lagx = false;   // the current folded system was built with the lagged X~ (three-launch set-up)
+    int xf_skip = 0;                // upcoming set-ups that must not use the one-launch form (a fallback after its breakdown)
+    // lagged dense inverse
+    int ldi_state = 0;              // 0 none, 1 seed in flight, 2 valid (ldi_cur), 3 valid + update in flight
+    int ldi_cur = -1, ldi_next = -1;
+    long ldi_iter = 0, ldi_ready_at = 0;
+    bool ldi_side_todo = false, ldi_update_ok = false, ldi_sread_pending = false;
+    int ldi_last_its = 0, ldi_prev_its = 0;
+    int ldi_rejects = 0; long ldi_no_seed_before = 0;
+    double ldi_tag = -1.0, ldi_next_tag = -1.0, ldi_call_start_cost = -1.0;   // cost at the point the inverse in use / in flight was built at
+    double ldi_prev_start_cost = -2.0;   // cost the previous standard-path call started from
+    bool ldi_moved = false;         // this call left the lagged inverse behind (cost jump): the standard solve's launch-count prediction is stale
+    // launch-count predictions
+    int last_pcg_iters = 0;
+    int prev_pcg_iters = -1;        // iteration count of the solve before the last one
+};
+
+struct ps_problem : PsOptions, PsCostHistory, PsCarried {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     int D = 6, PW = 12;
@@ -226,7 +280,7 @@ struct ps_problem {
     int32_t *row_ptr = nullptr, *col_idx = nullptr, *diag_slot = nullptr;
     double* red = nullptr;          // [S (nnzb*D*D) | g (nr*D) | cost]
     long red_count = 0;
-    double *S = nullptr, *g = nullptr, *red_cost = nullptr;
+    double *S = nullptr, *g = nullptr;
     // option "lin_zero_list": the slots of S that a linearisation ACCUMULATES into (diagonal blocks, blocks a factor or a host
     // row adds into, blocks of the pattern no pair item writes); every other slot is stored with `=` by exactly one pair item
     // of the untiled pair kernel and needs no zero in front.  Trailing workgroups of the pose pass zero these, g, the cost
@@ -234,40 +288,32 @@ struct ps_problem {
     int32_t* zero_slots = nullptr;
     int nzero_slots = 0;
     bool has_extra_pairs = false;   // created with extra pattern blocks: a landmark shard (pyslam_amd/distributed.py)
-    int lin_zero_list = 1;          // the option as set
-    bool lin_zero_gate = false;     // ... and whether this handle is eligible (relook_launch_gates)
+    bool lin_zero_gate = false;     // the option is on and this handle is eligible (relook_launch_gates)
     long lin_fills = 0, lin_zero_launches = 0;   // linearisations that ran the fill / that zeroed by the list
     std::vector<int32_t> h_row_ptr, h_col_idx;
     std::vector<int32_t> h_vid_of_slot;   // landmarks are stored in locality order; external order is vid
     // pcg
     double *x = nullptr, *r = nullptr, *z = nullptr, *p0 = nullptr, *p1 = nullptr, *q = nullptr, *Minv = nullptr;
     double *rz_part = nullptr, *rr_part = nullptr, *pq_part = nullptr, *hist = nullptr;
-    int npartA = 0, npartB = 0, hist_cap = 0, last_pcg_iters = 0;
+    int npartA = 0, npartB = 0, hist_cap = 0;
     // fused CG (one launch per iteration) on the block-Jacobi-scaled system
-    int pcg_variant = 1;            // 1 = fused single-reduction CG, 0 = classic two-launch PCG
-    int pcg_chunk = 8;              // launches between host polls of the 'done' flag
     double *Linv = nullptr, *cg_r[2] = {}, *cg_w[2] = {}, *cg_s[2] = {}, *cg_gd[2] = {}, *cg_xh = nullptr;
     int32_t* brow_of = nullptr;
     double* cg_p = nullptr;
     double* Saug = nullptr;         // scaled (and, with a coarse level, augmented) matrix the CG runs on
     int32_t* ident_slot = nullptr;
     // two-level preconditioner (coarse level), built lazily by build_coarse()
-    int coarse_req = -1;            // requested number of groups: -1 = auto, 0 = off
     int G = 0, ncb = 0, nc = 0, nr_aug = 0, nnzb_aug = 0;
     size_t cg_cap = 0, saug_cap = 0; // CG vectors / matrix are allocated for this many block rows / blocks
     int32_t *pnode = nullptr, *slo = nullptr, *shi = nullptr, *run_lo = nullptr, *run_hi = nullptr,
             *arow_ptr = nullptr, *acol_idx = nullptr, *aug_slot = nullptr, *fine_nnz = nullptr;
     double *pw0 = nullptr, *pw1 = nullptr, *SZ = nullptr, *Ac = nullptr, *tvec = nullptr, *chol_scratch = nullptr;
     // coarse basis P_iq = w(i,q) B_i: B_i = L_i^T Ad(T_i) (coarse_basis 1, rigid-motion aware) or I (0)
-    int coarse_basis = 1;
     double *Bmat = nullptr, *bgv = nullptr, *SB = nullptr, *BSZ = nullptr;   // Bmat: the basis the CURRENT system was built with
     // lagged three-launch setup (k_rows_setup): basis blocks and X = P L_c^-T double-buffered with the coarse factor
     double *Bmat2[2] = {}, *X2[2] = {}, *Mpart = nullptr;
     bool lagx_ok = false;           // the problem's shape allows it (folded, not split, nc <= 96, rows <= PS_RS_MAXROW blocks)
-    int lagx = 1;                   // option "coarse_lag_x"
-    bool side_todo = false;         // the next X (from SB / the basis in buffer side_buf) is still to be formed on the side stream
-    int side_buf = 0;
-    bool side_ready = false;        // the host has synchronised with the solver stream since the side stream's inputs were enqueued
+    int side_buf = 0;               // (PsCarried::side_todo: the buffer the next X is formed from)
     double host_wait_ns = 0.0, host_call_ns = 0.0;   // PS_HOST_TIMING
     long host_waits = 0, host_calls = 0;
     size_t rows_lds = 0;
@@ -279,11 +325,6 @@ struct ps_problem {
     // coarse factor L_c^-1 (and transpose), double-buffered: with "coarse_lag" the factorisation of THIS
     // iteration's A_c runs on a side stream while the CG iterates with the previous iteration's factor
     double *Lci2[2] = {}, *LciT2[2] = {};
-    int lci_cur = 0;                // buffer the current augmented system was built with
-    int lci_next = -1;              // buffer holding (or receiving, see side_pending) the newest factor; -1: none
-    bool xcg_side_todo = false;     // explicit PCG: lagged setup whose side-stream half is not enqueued yet
-    bool side_pending = false;      // a side-stream factorisation is in flight: wait for ev_chol before reuse
-    int coarse_lag = 1;
     hipStream_t side = nullptr;
     int side_cus = 0;               // > 0: the side stream is confined to this many compute units (CU mask)
     hipEvent_t ev_ac = nullptr, ev_chol = nullptr, ev_acdone = nullptr;
@@ -291,72 +332,44 @@ struct ps_problem {
     // compared bit for bit with what the side stream assembled: [entries of A_c that differ, of BSZ, comparisons]
     unsigned long long* chk_sums = nullptr; int chk_nsum = 0;      // PS_XCG_INV_SUM: bit checksums (pinned) of [inverse consumed | A_c the side job factored | inverse it produced] per set-up
     double *chk_Ac = nullptr, *chk_BSZ = nullptr, *chk_Ac_side = nullptr; int32_t* chk_cnt = nullptr; size_t chk_bsz_n = 0;
-    bool acdone_pending = false;    // explicit PCG: the side stream may still be assembling A_c from SB / the basis (wait before they are overwritten)
     int32_t* lag_status = nullptr;  // ST_DIAG_FAIL of the side-stream factorisation
     double* Mc = nullptr;           // split mode: dense coarse-coarse block M of the lagged system
-    bool mc_active = false;         // the current system was built with a lagged factor in split mode
     bool coarse_built = false;
     bool coarse_clamped = false;    // the automatic coarse level was cut back to 255 nodes: its matrix is not banded
-    int cg_ablate = 0, schur_ablate = 0, lm_ablate = 0;
-    int schur_pipeline = 1;         // k_schur_pairs_db (two chunks per wave in flight) instead of k_schur_pairs; option "schur_pipeline"
     int max_pose_obs = 0;           // most observations on one variable pose
-    int mo_fused = 1;               // motion-only problems: one launch per iteration (k_motion_only_iteration)
     double* mo_partials = nullptr;
     bool status_clean = true;       // no failure flag can be pending in the device status words
-    int direct_fused = ps_env("PS_DIRECT_3LAUNCH") ? 0 : 1;   // option "direct_fused": the direct solve in one launch (k_direct_solve)
-    int direct_max = 90;            // reduced systems up to this many unknowns are solved directly (0: never)
     double *dA = nullptr, *dLi = nullptr, *dLiT = nullptr;
-    int big_chol = 1;               // nc > 90: multi-workgroup blocked factorisation (0: one workgroup out of L2)
     // explicit two-level PCG (long sparse chains)
-    int explicit_ok = 1;
     bool cg_explicit = false;
-    int xcg_refresh_every = 1;      // option "coarse_refresh_every": lagged set-ups between two refreshes of the coarse inverse
-    long xcg_lag_count = 0;
-    // "coarse_auto_hold": keep the lagged coarse inverse (no assembly, no side-stream factorisation) while the solve has
-    // settled -- the last whole-iteration call changed the cost by less than 1e-4 relative -- for at most 3 set-ups in a row
-    int xcg_auto_hold = 1, xcg_held = 0;
-    int xcg_adaptive_hold = 1;      // option "coarse_adaptive_hold": keep the lagged inverse while it still does its job (xcg_setup)
-    int xcg_its_ref = 0, xcg_good_held = 0;   // CG iterations of the first solve with the inverse in use / set-ups it has been kept for
-    bool xcg_ref_pending = false;
-    double xcg_tag[2] = {-1.0, -1.0}, xcg_setup_cost = -1.0, xcg_tag_lambda[2] = {0.0, 0.0}, xcg_setup_lambda = 0.0, lin_lambda = 0.0;   // start cost of the call whose A_c each inverse buffer was formed from
-    double last_cost = -1.0, prev_cost = -1.0;   // costs returned by the last two ps_gn_iteration calls (-1: none / parameters replaced since)
+    double lin_lambda = 0.0;        // damping of the last linearisation
     double *xstate = nullptr, *xy = nullptr, *xp2 = nullptr;
     // ... banded coarse matrix (ps_k_band.h): block off-diagonals of A_c (-1: not banded enough), band factor by rows / columns
     int ac_bw = -1;
-    int band_chol = 1;              // option "band_chol"
-    int band_part = 1;              // option "band_part": the banded coarse matrix by the PARTITIONED factorisation (ps_k_bandpart.h) where it applies
-    int hold_across_steps = 1;      // option "hold_across_steps": BA rows keep a coarse inverse that still converges as fast, also behind a big step
-    int sync_refactor = 1;          // option "sync_refactor": pose graphs factor the CURRENT coarse matrix on the solver stream behind a step that halved the cost
-    int band_part_m = 0;            // option "band_part_chunk": interior nodes per chunk (0: automatic, ~ sqrt(B ncb) - B)
     std::unique_ptr<BandPart> bpart;
     double *Lrow = nullptr, *Lcol = nullptr, *rdiag = nullptr;
     // ... three-launch form (restriction folded into the SpMV epilogue + a recurrence for t)
-    int xcg_rt = 1;                 // option "xcg_restrict_fused"
     bool xcg_rt_ok = false;         // every SpMV workgroup touches at most PS_XCG_NSLOT coarse nodes
     int xcg_rt_rows = PS_XCG_ROWS_RT;
     int32_t *xcg_wg_out = nullptr, *xcg_nptr = nullptr;
     double *tq_part = nullptr, *tvec2 = nullptr;
     // ... one-launch form (k_xcg_fused1)
-    int xcg_fused = 1;              // option "xcg_fused": 0 = three launches per iteration, 1 = one (two when the coarse level is too wide), 2 = two
     bool xf_ok = false, xf_active = false;
     bool xf_one_ok = false, xf_two = false;   // the one-launch form fits (nc <= 2 048, even) / this solve runs the two-launch form
-    int xf_skip = 0;                // upcoming set-ups that must not use the one-launch form (a fallback after its breakdown)
     int32_t *xf_cptr = nullptr, *xf_cols = nullptr, *xf_nlo = nullptr, *xf_nhi = nullptr, *xf_rec = nullptr;
     uint16_t* xf_lidx = nullptr;
     double *xf_tq[2] = {}, *xf_ts[2] = {}, *xf_t[2] = {};
     int xf_rmax = 1, xf_nwg = 0, xf_pf = 2;
     size_t xf_nrec = 0;
     long xf_solves = 0, xf_fallbacks = 0;
-    int cg_lds = 1;                 // small systems: k_cg_fused_lds (whole vector through LDS)
     // the folded CG in ONE launch (ps_k_cg_persist.h): option "cg_persist"; task table built with the coarse level
-    int cg_persist = 1;
     bool cp_ok = false;             // the augmented system fits the kernel's layout
     bool cp_recovered = false;      // the launch just enqueued recovers x itself when it converges
     int cp_ntasks = 0, cg_max_launches = 0;
     void* cp_tasks = nullptr;       // CpTask[cp_ntasks]
     int32_t* cp_row_task0 = nullptr;
     unsigned long long* cp_exch = nullptr;
-    unsigned cp_salt = 0, cp_spin = 200000;   // option "cg_persist_spin": passes over the exchange before a workgroup gives up
+    unsigned cp_salt = 0;
     long cp_launches = 0, cp_failures = 0;
     // co-residency (ps_stream_cus / PersistLedger above): what build_coarse found, what a solve in flight holds
     int persist_dev = 0, persist_cus = 0;       // device of the handle; compute units its stream may use (0: unknown -> no one-launch form)
@@ -381,31 +394,21 @@ struct ps_problem {
         persist_held = need; return true;
     }
     // the explicit two-level PCG's one-launch-per-iteration form as one launch per solve (ps_k_xcg_persist.h): option "xcg_persist"
-    int xcg_persist = 1;
     bool xp_ok = false;             // every workgroup resident at once, at most PS_XP_RB records per node
     int32_t* xf_cnt = nullptr;      // live records per coarse node
     unsigned long long* xp_exch = nullptr;
     size_t xp_words = 0;
     unsigned xp_salt = 0;
-    long xp_launches = 0;
     bool xp_defer = false;          // xcg_setup left launch -1 to the one launch that runs them all
     long long* cp_dbg = nullptr;    // measurement build, PS_CP_CLOCKS: phase clocks of the kernel's first workgroup
     long long* xp_dbg = nullptr;    // measurement build, PS_XP_CLOCKS: phase clocks of three workgroups of k_xcg_persist
-    long xp_dbg_launches = 0;
-    int prof_every = 1;             // profiling level 1: time the Schur kernel of every n-th linearisation only
-    long prof_tick = 0;
-    int prev_pcg_iters = -1;        // iteration count of the solve before the last one (launch-count prediction)
+    long prof_tick = 0;             // linearisations so far ("profile_every" times every n-th)
     int cg_fallbacks = 0;           // solves repeated with the classic PCG after a breakdown of the pipelined CG
-    int cg_force_restart = 0;       // option (tests): end the first pass of a synchronous solve at 1e-4 and restart from the true residual
-    bool ldi_moved = false;         // this call left the lagged inverse behind (cost jump): the standard solve's launch-count prediction is stale
-    int cg_margin = 4;              // CG launches enqueued beyond the previous solve's iteration count
     bool cg_two_level_reduce = false, cg_short_rows = false;
     double* cg_tot = nullptr;
     // split mode (large systems): coarse rows are owned by k_cg_reduce_split
     bool cg_split = false;
-    int cg_split_min_rows = 1024;
     bool xmin_auto_ldi = false;     // build_coarse chose the folded / explicit crossover assuming the lagged inverse applies (re-decided when that changes)
-    int cg_explicit_min_rows = -1;  // explicit two-level PCG beyond this many reduced poses (-1: 400 for pose-graph rows, 540 for BA rows)
     double *cg_U = nullptr, *cg_cgd[2] = {}, *cg_ab = nullptr;
     int cg_launched = 0;            // CG launches enqueued since the last setup
     long cg_kernel_launches = 0;    // kernels enqueued for CG / PCG iterations since creation (ps_problem_info)
@@ -431,7 +434,7 @@ struct ps_problem {
     long long setup_seq = 0;
     int32_t* arrivals = nullptr;
     double *h_mo_hist = nullptr, *h_mo_hist_dev = nullptr;   // pinned: k_motion_only_solve's [entries, iterations, |dx|, cost history ...]
-    int ncost_obs = 0, ncost_fac = 0, nsq = 0;
+    int ncost_obs = 0, ncost_fac = 0;
     // native RCCL: function pointer + communicator handed over by the binding (ps_set_collective)
     typedef int (*allreduce_fn)(const void*, void*, size_t, int, int, void*, hipStream_t);
     allreduce_fn nccl_allreduce = nullptr;
@@ -440,7 +443,7 @@ struct ps_problem {
     // system], then every destination element summed over its contributors in RANK order (the same on every rank)
     typedef int (*allgather_fn)(const void*, void*, size_t, int, void*, hipStream_t);
     allgather_fn seg_allgather = nullptr;
-    int seg_world = 0, seg_rank = 0;
+    int seg_world = 0;
     long seg_maxlen = 0, seg_nmine = 0, seg_ndst = 0;
     int32_t *seg_mine = nullptr, *seg_dst = nullptr, *seg_src_off = nullptr, *seg_src_ptr = nullptr;   // (the plan in 32 bits on the device: 12 B per element less to read)
     double *seg_in = nullptr, *seg_all = nullptr;
@@ -460,55 +463,22 @@ struct ps_problem {
     // (lmw_nwaves + 1 entries; 0 waves: the 16-lane kernels -- a track longer than 16 observations, or an unobserved landmark)
     int32_t* lmw_first = nullptr;
     int lmw_nwaves = 0;
-    int lm_packed = 1;              // option "lm_packed"
-    int pose_xcd = 1;               // option "pose_xcd": the pose pass's items in eight contiguous ranges, one per XCD (round 6)
     // lagged dense inverse of the reduced system as the CG preconditioner (ps_k_ldi.h / ps_host_ldi.h)
-    int ldi_enable = 1;             // option "lagged_inverse"
-    int ldi_max_n = 2048;           // option "ldi_max_unknowns": reduced systems up to this many unknowns
-    int ldi_cap = 12;               // option "ldi_cap": PCG iterations before a solve gives the inverse up
-    int ldi_seed_steps = 3;         // Newton-Schulz steps of a seed
-    double ldi_cost_tol = 0.05;     // option "ldi_cost_tol": try the inverse while the last step changed the cost by at most this (relative)
     bool ldi_ready = false;         // buffers allocated
     int ldi_n = 0, ldi_np = 0, ldi_kp = 0;
     float *ldi_S32 = nullptr, *ldi_X32 = nullptr, *ldi_R32 = nullptr, *ldi_T32 = nullptr, *ldi_Xt = nullptr, *ldi_XtT = nullptr;
     float* ldi_Xu[2] = {};          // unscaled inverse, double-buffered against the side stream
     double *ldi_x64 = nullptr, *ldi_Linv = nullptr, *ldi_r[2] = {}, *ldi_part = nullptr, *ldi_fro_part = nullptr;
     double *h_ldi_fro = nullptr, *h_ldi_fro_dev = nullptr;   // ||R||_F^2 of the side stream's last Newton-Schulz step (pinned)
-    int ldi_state = 0;              // 0 none, 1 seed in flight, 2 valid (ldi_cur), 3 valid + update in flight
-    int ldi_cur = -1, ldi_next = -1;
-    long ldi_iter = 0, ldi_ready_at = 0;
-    double ldi_fro_limit = 0.1, ldi_last_rms = 0.0;
-    bool ldi_side_todo = false, ldi_update_ok = false, ldi_sread_pending = false, ldi_ritz_ok = false;
-    double ldi_ritz_lo = 0.0, ldi_ritz_hi = 0.0;
-    int ldi_last_its = 0, ldi_prev_its = 0;
-    int ldi_refresh_its = 7;        // option "ldi_refresh_its": solves slower than this switch the per-iteration refresh on
-    bool ldi_refreshed = false;     // the inverse in use has had a Newton-Schulz step since its seed
+    double ldi_fro_limit = 0.1;     // ||R||_F bound the seed / refresh in flight is accepted under
     int2* ldi_krange = nullptr;
-    // calls between a seed's start and its first use (fixed schedule).  1: the call after the seed waits for it where the solve
-    // begins (~0.1 ms of the seed's GEMMs are then still ahead at C3, hidden behind this call's linearisation for most of it) and
-    // takes 6 iterations instead of 18-25 -- eight-call solves 3-7 % shorter at every size from 138 to 2 034 unknowns than with 2
-    int ldi_seed_lag = ps_env("PS_LDI_SEED_LAG") ? atoi(ps_env("PS_LDI_SEED_LAG")) : 1;
-    int ldi_rejects = 0; long ldi_no_seed_before = 0;
-    // direct seed (ps_host_ldi.h: ldi_direct_enqueue): on for pose graphs from the start, for any problem after a rejected
-    // Newton-Schulz seed; option "ldi_direct" (-1 auto, 0 never, 1 always)
-    bool ldi_direct = false, ldi_direct_ok = true;
     bool side_poolable = false;            // `side` is an ordinary non-blocking stream (no CU mask, no priority)
     hipStream_t ldi_stream = nullptr;      // the direct seed's own stream: ~100 launches that must not sit in front of the coarse operator on `side`
     double *ldi_A64 = nullptr, *ldi_Li = nullptr, *ldi_LiT = nullptr, *ldi_Tinv = nullptr; int32_t* ldi_stat = nullptr;
     float* ldi_coef = nullptr;      // device: seed scale c and the two Ritz values (k_ldi_ritz)
-    double ldi_tag = -1.0, ldi_next_tag = -1.0, ldi_call_start_cost = -1.0;   // cost at the point the inverse in use / in flight was built at
-    hipEvent_t ev_ldi_ritz = nullptr;
-    double ldi_prev_start_cost = -2.0;   // cost the previous standard-path call started from
     long ldi_solves = 0, ldi_fallbacks = 0, ldi_seeds = 0;
-    bool last_setup_lagx = false;   // the current folded system was built with the lagged X~ (three-launch set-up)
     hipEvent_t ev_ldi = nullptr, ev_ldi_sread = nullptr;
-    double snap_cost = -1.0;        // last_cost at the time of ps_snapshot_params
     bool snap_valid = false;        // a snapshot has been taken and not consumed (ps_solve's final restore exchanges the tables)
-    // option "solve_horizon": how many MORE whole-iteration calls the caller's stopping rule allows if the step about to be
-    // taken does not decrease the cost enough (reference problem.py:163-178: max_nondecreasing_steps - taken - 1, or 0 without
-    // allow_nondecreasing_steps); -1 = unknown (a caller that drives ps_gn_iteration itself).  Side work that only pays back
-    // over several later calls -- the seed of the lagged dense inverse -- is not started when the solve is about to stop.
-    int solve_horizon = -1;
     // speculative next linearisation (ps_solve): the call's tail stamps h_early when its reduced solve has converged; the host,
     // waiting for the end of the iteration, then enqueues the linearisation of the NEXT iteration behind the tail, and the next
     // ps_gn_iteration finds it done (prelin_valid) -- the GPU does not idle while the host ends one call and starts the next
@@ -522,7 +492,6 @@ struct ps_problem {
     // parameters have not moved since -- linearize() then skips its landmark pass.  A landmark block that was not positive
     // definite there stamps h_lmfail[tag & 1] with the tag (two pinned words: consecutive passes cannot overwrite one another's
     // report before it is read); the call whose linearisation consumed the pass reports it (lmfail_check).
-    int expect_next = 0, fuse_cost = 1;
     bool prelm_pending = false, prelm_valid = false;
     double prelm_lambda = 0.0;
     long long prelm_tag = 0, prelm_seq = 0, lmfail_check = 0, lin_lmfail_tag = 0;
@@ -532,7 +501,6 @@ struct ps_problem {
     bool solver_touched = false;    // something has been linearised since creation / the last ps_reset_solver_state
     // profiling
     int profiling = 0;              // 0 off, 1 = iteration total + Schur kernel only, 2 = every stage
-    hipEvent_t ev[2 * PS_NUM_STAGES] = {};
     std::vector<std::pair<int, int>> pending;   // (stage, event slot) recorded, not yet read
     double stage_ms[PS_NUM_STAGES] = {};
     int64_t stage_n[PS_NUM_STAGES] = {};

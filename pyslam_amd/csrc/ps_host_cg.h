@@ -270,7 +270,7 @@ int build_coarse(ps_problem* h) {
     // switched off -- the one- / two-launch explicit PCG of round 3 wins from ~250 poses on (tools/path_threshold_probe.py,
     // settled ms folded / explicit: BA 250 keyframes 0.435 / 0.412, 360: 0.53 / 0.45, 480: 0.71 / 0.51, 539: 0.80 / 0.53;
     // SE(3) graphs 250 poses 0.64 / 0.60, 350: 0.82 / 0.72; at 200 keyframes / poses the folded form still leads, 0.31 / 0.40).
-    const bool ldi_possible = h->ldi_enable && (long)nr * D <= h->ldi_max_n && (long)nr * D <= PS_LDI_MAXN && nr * D > h->direct_max;
+    const bool ldi_possible = ps_ldi_possible(*h, (long)nr * D);
     const int xmin_auto = ldi_possible ? (sparse_rows ? 400 : 540) : 250;
     h->xmin_auto_ldi = ldi_possible;
     const int xmin = std::min(h->cg_split_min_rows, h->cg_explicit_min_rows >= 0 ? h->cg_explicit_min_rows : xmin_auto);

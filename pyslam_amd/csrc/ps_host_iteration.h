@@ -273,7 +273,7 @@ void xcg_launch(ps_problem* h, double tol, int count) {
                 per_cu_ < 1 || cdiv(h->xf_nwg, per_cu_) > h->persist_capacity()) { launched = false; break; }                                 \
             hipLaunchKernelGGL((k_xcg_persist<D, PF, PL, NE>), dim3(h->xf_nwg), dim3(64 * PS_XF_ROWS), lds, h->stream, nr, h->arow_ptr,        \
                                h->ell_wf, h->Saug, a, h->xf_cnt, nl, tol * tol, h->hist, h->hist_cap, h->status, h->scalars, h->xstate,        \
-                               h->xp_exch, h->xp_salt, h->cp_spin, h->xp_dbg); ++h->xp_dbg_launches; } while (0)
+                               h->xp_exch, h->xp_salt, h->cp_spin, h->xp_dbg); } while (0)
         // (LDS: the static arrays + t + the records + PL blocks per lane of the matrix: as many as fit 160 KB)
         const size_t per_pl = (size_t)64 * PS_XF_ROWS * (D * sizeof(double) + sizeof(int32_t));
         const size_t fixed = 11700 + 1024;                   // (the kernel's static arrays, -Rpass-analysis=kernel-resource-usage)
@@ -293,7 +293,7 @@ void xcg_launch(ps_problem* h, double tol, int count) {
             return;
         }
 #undef PS_XP_LAUNCH
-        h->cg_launched = h->cg_max_launches; h->cg_kernel_launches += 1; ++h->xp_launches; ++h->cp_launches;
+        h->cg_launched = h->cg_max_launches; h->cg_kernel_launches += 1; ++h->cp_launches;
         return;
     }
     if (h->xf_active) {                                     // ONE launch per iteration (launch index n = k + 1 picks the buffers)

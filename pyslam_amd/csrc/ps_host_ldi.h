@@ -13,9 +13,8 @@
 namespace {
 
 bool ldi_eligible(const ps_problem* h) {
-    const long n = (long)h->nr * h->D;
-    return h->ldi_enable && !h->hybrid && h->pcg_variant == 1 && !h->cg_explicit && !h->cg_split && h->G > 0 && n > h->direct_max &&
-           n <= h->ldi_max_n && n <= PS_LDI_MAXN && !(h->nccl_allreduce && h->nccl_comm);
+    return ps_ldi_possible(*h, (long)h->nr * h->D) && !h->hybrid && h->pcg_variant == 1 && !h->cg_explicit && !h->cg_split && h->G > 0 &&
+           !(h->nccl_allreduce && h->nccl_comm);
 }
 
 int ldi_ensure(ps_problem* h) {
@@ -61,7 +60,6 @@ int ldi_ensure(ps_problem* h) {
     if (!h->ev_ldi) {
         HIP_OK(hipEventCreateWithFlags(&h->ev_ldi, PS_XSTREAM_EVENT_FLAGS));
         HIP_OK(hipEventCreateWithFlags(&h->ev_ldi_sread, PS_XSTREAM_EVENT_FLAGS));
-        HIP_OK(hipEventCreateWithFlags(&h->ev_ldi_ritz, PS_XSTREAM_EVENT_FLAGS));
     }
     const size_t lds = (size_t)np * sizeof(double);
     if (ensure_dynamic_lds((const void*)k_ldi_init, (size_t)(lds))) return -1;
@@ -145,7 +143,6 @@ int ldi_direct_enqueue(ps_problem* h, int state, int lag) {
     hipLaunchKernelGGL(k_ldi_direct_done, dim3(1), dim3(64), 0, st, h->ldi_stat, h->h_ldi_fro_dev);
     HIP_OK(hipEventRecord(h->ev_ldi, st));
     h->ldi_state = state; h->ldi_next = wb; h->ldi_ready_at = h->ldi_iter + lag; h->ldi_fro_limit = 0.1;
-    h->ldi_refreshed = state == 3;
     h->ldi_next_tag = h->ldi_call_start_cost;
     if (state == 1) ++h->ldi_seeds;
     return 0;
@@ -202,7 +199,6 @@ int ldi_seed_enqueue(ps_problem* h, int its, double cost_now) {
     }
     HIP_OK(hipEventRecord(h->ev_ldi, st));
     h->ldi_state = 1; h->ldi_next = wb; h->ldi_ready_at = h->ldi_iter + h->ldi_seed_lag; h->ldi_fro_limit = 0.1;
-    h->ldi_refreshed = false;
     h->ldi_next_tag = h->ldi_call_start_cost;               // the cost at the point whose S this inverse is built from
     ++h->ldi_seeds;
     return 0;
@@ -223,7 +219,6 @@ int ldi_update_kick(ps_problem* h) {
     ldi_ns_step<D>(h, st, h->ldi_Xu[wb], true);
     HIP_OK(hipEventRecord(h->ev_ldi, st));
     h->ldi_state = 3; h->ldi_next = wb; h->ldi_ready_at = h->ldi_iter + 1; h->ldi_fro_limit = 0.3;
-    h->ldi_refreshed = true;
     h->ldi_next_tag = h->ldi_call_start_cost;
     return 0;
 }
@@ -244,7 +239,6 @@ bool ldi_decide(ps_problem* h) {
         if (hipEventSynchronize(h->ev_ldi) != hipSuccess) { h->ldi_state = 0; h->ldi_cur = -1; return false; }
         const double rms = std::sqrt(*h->h_ldi_fro / (double)h->ldi_np);    // rms eigenvalue of R = I - S^ X before the last step
         const bool ok = std::isfinite(rms) && rms < h->ldi_fro_limit && (h->ldi_state == 1 || h->ldi_update_ok);
-        h->ldi_last_rms = rms;
         if (ok) { h->ldi_cur = h->ldi_next; h->ldi_tag = h->ldi_next_tag; if (h->ldi_state == 1) h->ldi_rejects = 0; h->ldi_state = 2; }
         else {
             // a seed that did not contract in its Newton-Schulz steps (an operator whose preconditioned condition number is

@@ -28,7 +28,6 @@
 #define PS_XCG_RBATCH 6                       // records of a node loaded together by k_xcg_coarse_rt
 #endif
 #define PS_XCG_DROWS 256                      // rows per workgroup of the prolongation
-#define PS_XCG_MAXNODES 1024                  // coarse nodes of the explicit form (t of the big coarse kernel in LDS: 48 KB)
 
 PS_DEV double xcg_total(const double* __restrict__ part, int n, double* lds) {
     double v = 0.0;

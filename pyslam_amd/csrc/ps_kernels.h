@@ -21,6 +21,7 @@
 // the end (linearize, pcg_classic, cg_fused, xcg, coarse, band, tail), in pipeline order.
 #pragma once
 #include "ps_math.h"
+#include "ps_limits.h"
 
 struct __attribute__((aligned(32))) LObs {   // one reprojection observation, 32 B
     double u, v, d;

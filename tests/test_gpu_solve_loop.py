@@ -83,6 +83,33 @@ def test_a_solve_on_a_used_handle_equals_the_solve_on_a_fresh_one():
     used.close()
 
 
+def test_a_solve_on_a_used_handle_equals_the_solve_on_a_fresh_one_on_the_explicit_path():
+    """The same on the explicit two-level PCG (the test above runs the folded CG with the lagged inverse): its lagged coarse
+    inverse, the tags and holds that decide whether it is kept, and its launch-count predictions.  96 poses with
+    cg_explicit_min_rows = 0: the smallest graph on which the explicit form runs with a coarse level of its own."""
+    from pyslam_amd.device import DeviceProblem
+    lp, _ = synthetic.pose_graph(num_poses=96, num_loops=200, dof=6)
+    opt = _options(allow_nondecreasing_steps=True, max_nondecreasing_steps=3)
+    fresh = DeviceProblem(lp)
+    fresh.set_option('cg_explicit_min_rows', 0)
+    want_h, want_s = device_solve(fresh, opt)
+    want_p = fresh.get_params()
+    info = fresh.get_info()
+    # (the folded CG of a system this small runs in one launch, with the lagged inverse once it has settled: neither happened)
+    assert info['cg_persist_solves'] == 0 and info['ldi_solves'] == 0 and info['cg_kernel_launches'] > 0
+    fresh.close()
+    used = DeviceProblem(lp)
+    used.set_option('cg_explicit_min_rows', 0)
+    for _ in range(7):
+        used.gn_iteration(0.0, 1e-12, 2000, True)
+    used.set_params(lp.poses, lp.points)
+    got_h, got_s = device_solve(used, opt)
+    got_p = used.get_params()
+    used.close()
+    assert got_h == want_h and got_s == want_s
+    assert np.array_equal(got_p[0], want_p[0]) and np.array_equal(got_p[1], want_p[1])
+
+
 def test_a_linearisation_enqueued_ahead_does_not_survive_a_staged_tail():
     """ps_solve may leave the NEXT linearisation in the queue (enqueued behind a converged tail while the host waited).  Anything
     that moves the parameters afterwards -- here the staged tail ps_gn_finish, which applies the last step once more -- must
