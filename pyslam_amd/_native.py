@@ -152,6 +152,10 @@ SIGNATURES = {
     'ps_twoview_score': (C.c_int, [c_f64p, C.c_int32, c_f64p, c_f64p, C.c_int32, c_f64p, C.c_double, c_u8p, c_i32p]),
     'ps_twoview_ransac': (C.c_int, [c_f64p, c_f64p, C.c_int32, c_i32p, C.c_int32, c_f64p, C.c_double, C.c_int32, c_f64p, c_f64p,
                                     c_u8p, c_i32p, c_f64p]),
+    'ps_pnp_hypotheses': (C.c_int, [c_f64p, c_f64p, C.c_int32, c_i32p, C.c_int32, c_f64p, C.c_double, c_f64p, c_i32p, c_u8p]),
+    'ps_pnp_score': (C.c_int, [c_f64p, C.c_int32, c_f64p, c_f64p, C.c_int32, c_f64p, C.c_double, c_u8p, c_i32p]),
+    'ps_pnp_ransac': (C.c_int, [c_f64p, c_f64p, C.c_int32, c_i32p, C.c_int32, c_f64p, C.c_double, C.c_int32, c_f64p, c_u8p, c_i32p,
+                                c_f64p, c_f64p]),
     'ps_photometric_create': (C.c_int, [C.POINTER(PhotoDesc), C.c_void_p, C.POINTER(H)]),
     'ps_photometric_destroy': (C.c_int, [H]),
     'ps_photometric_set_pose': (C.c_int, [H, c_f64p]),

@@ -25,6 +25,7 @@
 #include "ps_kernels.h"
 #include "ps_ransac.h"
 #include "ps_k_twoview.h"
+#include "ps_k_pnp.h"
 #include "ps_photo.h"
 #include "ps_k_dense.h"
 #include "ps_k_feat.h"
@@ -659,6 +660,7 @@ extern "C" {
 #include "ps_abi_triang.h"
 #include "ps_abi_small.h"
 #include "ps_abi_twoview.h"
+#include "ps_abi_pnp.h"
 #include "ps_abi_dense.h"
 #include "ps_abi_feat.h"
 

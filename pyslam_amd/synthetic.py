@@ -642,3 +642,24 @@ def _two_view_scene(num_pts, seed, rotvec, t):
 def two_view_points(num_pts=192, seed=11, rotvec=(0.02, -0.05, 0.03), t=(0.5, -0.05, 0.1)):
     """The true points (N, 3) of two_view's scene, in the frame of camera 1."""
     return _two_view_scene(num_pts, seed, rotvec, t)[0]
+
+
+# ---------------------------------------------------------------------------
+# a third monocular view of two_view's scene: 2-D - 3-D correspondences with outliers (pipelines/pnp.py)
+# ---------------------------------------------------------------------------
+def pnp_scene(num_pts=192, seed=11, outlier_fraction=0.3, pixel_noise=0.5, rotvec=(-0.03, 0.08, -0.02), t=(-0.6, 0.1, 0.3)):
+    """A third pinhole view of two_view_points(num_pts, seed), TWO_VIEW_CAMERA, at the pose p_3 = R p_1 + t with R = exp(rotvec)
+    (another pose than two_view's second).  Gaussian pixel noise; the LAST ``outlier_fraction * num_pts`` rows of obs are replaced
+    by uniform pixels (two_view replaces the first rows: the two outlier sets are disjoint up to 50 %).
+    -> (pts_w (N, 3) the true points in the frame of camera 1, obs (N, 2), T_cw (4, 4) truth, outlier mask (N,) bool)."""
+    pts, T = _two_view_scene(num_pts, seed, rotvec, t)
+    cu, cv, fu, fv, w, h = TWO_VIEW_CAMERA
+    rng = np.random.default_rng([seed, 2])
+    p3 = pts @ T[:3, :3].T + T[:3, 3]
+    obs = np.stack([fu * p3[:, 0] / p3[:, 2] + cu, fv * p3[:, 1] / p3[:, 2] + cv], axis=1)
+    obs = obs + pixel_noise * rng.standard_normal(obs.shape)
+    n_out = int(outlier_fraction * num_pts)
+    outlier = np.arange(num_pts) >= num_pts - n_out
+    if n_out:
+        obs[num_pts - n_out:] = rng.uniform([0., 0.], [w, h], size=(n_out, 2))
+    return pts, obs, T, outlier
