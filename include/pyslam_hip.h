@@ -736,6 +736,21 @@ int ps_feat_read_matches(ps_feat* h, int32_t num_matches, double* matches8, int3
    most `capacity` of them: uv (2 x int32 each, raster order), response R, descriptors (32 bytes each).  Tests. */
 int ps_feat_read_features(ps_feat* h, int32_t which, int32_t capacity, int32_t* num_features, int32_t* uv, int64_t* response,
                           uint8_t* descriptors);
+/* Matching by projection (step 8 of the definition).  ps_feat_set_map uploads num_points (0 .. 2^20) map points -- points_w:
+   num_points x 3 doubles in the world frame, descriptors: 32 bytes each, as ps_feat_read_features returns them -- to the handle,
+   where they stay; its buffers are allocated at the first call and grow with num_points (a handle that never sets a map holds
+   what it was created with).  ps_feat_match_map computes the features of the current frame's left image if it has none under
+   these parameters, projects every point with T_cw (4 x 4, row-major) and cam5 = (cu, cv, fu, fv, b; b is not read), takes the
+   best feature within `radius` pixels of the rounded projection, lets every feature go to one point only and refines the
+   positions; it waits once, for the number of matched points and the results, which one copy brings to the host with it.
+   ps_feat_read_map_matches hands them out without touching the device: one entry per map point, no compaction
+   -- feature index or -1; status 0 matched, 1 not visible, 2 no candidate within match_cost_max, 3 lost its feature to a point
+   with a lower (cost, index); cost, -1 unless the status is 0 or 3; uv (2 doubles), -1 unless the status is 0.  Any output may
+   be NULL. */
+int ps_feat_set_map(ps_feat* h, int32_t num_points, const double* points_w, const uint8_t* descriptors);
+int ps_feat_match_map(ps_feat* h, const double* T_cw, const double* cam5, int32_t radius, const ps_feat_params* params,
+                      int32_t* num_matched);
+int ps_feat_read_map_matches(ps_feat* h, int32_t num_points, int32_t* feature, int32_t* status, int32_t* cost, double* uv);
 /* number of images whose features were computed since create (a recognised frame adds none) */
 int ps_feat_feature_passes(ps_feat* h, int64_t* passes);
 int ps_feat_device_bytes(ps_feat* h, int64_t* bytes);

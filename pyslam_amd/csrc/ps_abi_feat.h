@@ -5,7 +5,9 @@
 // two-frame window does, and one more as a cache.  A pushed frame whose bytes equal a frame the handle holds is not
 // uploaded and its features are not computed again: the sparse pipelines push the active keyframe in front of every
 // tracking frame.  Everything is allocated at create time; a match is a fixed sequence of launches on the handle's
-// stream with one synchronisation at its end.
+// stream with one synchronisation at its end.  The one exception is the map of matching by projection (ps_feat_set_map,
+// step 8 of the definition): its buffers are allocated at the first ps_feat_set_map and grow with the map, so a handle
+// that never sets one holds exactly what it was created with.
 
 extern "C++" {
 struct PsFeatImage {
@@ -43,6 +45,16 @@ struct ps_feat {
     int2* raw_uv = nullptr;
     double* m8 = nullptr;
     int h_n_match = 0;
+    // the map of matching by projection: nothing of it exists before the first ps_feat_set_map
+    bool map_set = false;
+    int map_n = 0, map_cap = 0, h_n_map_matched = 0, map_matched_n = -1;
+    double* map_pts = nullptr;
+    uint32_t* map_desc = nullptr;
+    uint8_t* map_out = nullptr;             // [count, 16 bytes | uv 2N doubles | feature N | status N | cost N] of the N matched last
+    std::vector<uint8_t> h_map_out;         // its copy on the host: one download per match, read from there
+    unsigned long long* map_claim = nullptr;
+    std::vector<void*> map_allocs;          // the buffers that grow with the map
+    int64_t map_bytes = 0;
     int alloc_bytes(void** p, size_t b) {
         if (hipMalloc(p, std::max<size_t>(b, 16)) != hipSuccess) return fail("hipMalloc failed");
         allocs.push_back(*p);
@@ -50,7 +62,19 @@ struct ps_feat {
         return 0;
     }
     template <typename T> int alloc(T** p, size_t n) { return alloc_bytes((void**)p, n * sizeof(T)); }
-    ~ps_feat() { for (void* p : allocs) hipFree(p); }
+    template <typename T> int alloc_map(T** p, size_t n) {
+        const size_t b = std::max<size_t>(n * sizeof(T), 16);
+        if (hipMalloc((void**)p, b) != hipSuccess) return fail("hipMalloc failed");
+        map_allocs.push_back((void*)*p);
+        map_bytes += (int64_t)b; bytes += (int64_t)b;
+        return 0;
+    }
+    void free_map() {
+        for (void* p : map_allocs) hipFree(p);
+        map_allocs.clear();
+        bytes -= map_bytes; map_bytes = 0; map_cap = 0;
+    }
+    ~ps_feat() { for (void* p : map_allocs) hipFree(p); for (void* p : allocs) hipFree(p); }
 };
 }  // extern "C++"
 
@@ -218,6 +242,89 @@ int ps_feat_read_matches(ps_feat* f, int32_t num_matches, double* matches8, int3
     if (matches8) HIP_OK(hipMemcpyAsync(matches8, f->m8, (size_t)num_matches * 8 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
     if (indices4) HIP_OK(hipMemcpyAsync(indices4, f->idx4, (size_t)num_matches * 4 * sizeof(int), hipMemcpyDeviceToHost, f->stream));
     HIP_OK(hipStreamSynchronize(f->stream));
+    return 0;
+}
+
+int ps_feat_set_map(ps_feat* f, int32_t num_points, const double* points_w, const uint8_t* descriptors) {
+    if (!f) return fail("null handle");
+    if (num_points < 0 || num_points > (1 << 20)) return fail("num_points must be 0 .. 2^20");
+    if (num_points > 0 && (!points_w || !descriptors)) return fail("null argument");
+    hipStream_t s = f->stream;
+    if (!f->map_claim && f->alloc(&f->map_claim, (size_t)f->max_features)) return -1;
+    if (num_points > f->map_cap) {
+        HIP_OK(hipStreamSynchronize(s));                   // a match of the old map may still read its buffers
+        f->free_map();
+        f->map_set = false;
+        const size_t n = num_points;
+        if (f->alloc_map(&f->map_pts, 3 * n) || f->alloc_map(&f->map_desc, 8 * n) || f->alloc_map(&f->map_out, 16 + 28 * n)) {
+            f->free_map();
+            return -1;
+        }
+        f->map_cap = num_points;
+    }
+    if (num_points > 0) {
+        HIP_OK(hipMemcpyAsync(f->map_pts, points_w, (size_t)num_points * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(f->map_desc, descriptors, (size_t)num_points * 32, hipMemcpyHostToDevice, s));
+        HIP_OK(hipStreamSynchronize(s));                   // the caller's arrays are free on return
+    }
+    f->map_n = num_points;
+    f->map_set = true;
+    f->map_matched_n = -1;
+    return 0;
+}
+
+int ps_feat_match_map(ps_feat* f, const double* T_cw, const double* cam5, int32_t radius, const ps_feat_params* params,
+                      int32_t* num_matched) {
+    if (!f || !T_cw || !cam5 || !params || !num_matched) return fail("null argument");
+    *num_matched = 0;
+    const ps_feat_params& p = *params;
+    if (p.nms_n < 1 || p.nms_n > 3) return fail("nms_n must be 1..3");
+    if (p.max_features < 1 || p.max_features > f->max_features) return fail("max_features outside the handle's capacity");
+    if (radius < 0) return fail("negative matching radius");
+    if (f->cur < 0) return fail("push a frame before matching the map");
+    if (!f->map_set) return fail("set a map before matching it");
+    PsFeatFrame& Cf = f->frame[f->cur];
+    if (feat_frame_features(f, Cf, p)) return -1;
+    f->map_matched_n = f->map_n;
+    f->h_n_map_matched = 0;
+    const int N = f->map_n, h = Cf.h, w = Cf.w;
+    if (N == 0) return 0;
+    FeatMapView V;
+    for (int k = 0; k < 12; ++k) V.T[k] = T_cw[k];
+    V.cu = cam5[0]; V.cv = cam5[1]; V.fu = cam5[2]; V.fv = cam5[3];
+    // one block for everything that goes back: the count, then the four arrays (doubles first: aligned)
+    uint8_t* o = f->map_out;
+    const size_t n = N, total = 16 + 28 * n;
+    int* count = (int*)o;
+    const FeatMapOut out{(int*)(o + 16 + 16 * n), (int*)(o + 16 + 20 * n), (int*)(o + 16 + 24 * n), (double*)(o + 16)};
+    const int r = std::min((int)radius, std::max(h, w));   // a window over the whole image is as large as it gets
+    hipStream_t s = f->stream;
+    HIP_OK(hipMemsetAsync(f->map_claim, 0xff, (size_t)f->max_features * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_feat_map_search, dim3(cdiv((long)N * 64, 256)), dim3(256), 0, s, N, (const double*)f->map_pts,
+                       (const uint32_t*)f->map_desc, V, Cf.im[0].list(), h, w, (int)p.max_features, r, (int)p.match_cost_max, out,
+                       f->map_claim, count);
+    hipLaunchKernelGGL(k_feat_map_resolve, dim3(cdiv(N, 256)), dim3(256), 0, s, N, (const uint32_t*)f->map_desc, Cf.im[0].list(), h, w,
+                       (int)p.max_features, (int)p.refinement, out, (const unsigned long long*)f->map_claim, count);
+    HIP_OK(hipGetLastError());
+    f->h_map_out.resize(total);
+    HIP_OK(hipMemcpyAsync(f->h_map_out.data(), o, total, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    memcpy(&f->h_n_map_matched, f->h_map_out.data(), sizeof(int));
+    *num_matched = f->h_n_map_matched;
+    return 0;
+}
+
+int ps_feat_read_map_matches(ps_feat* f, int32_t num_points, int32_t* feature, int32_t* status, int32_t* cost, double* uv) {
+    if (!f) return fail("null handle");
+    if (f->map_matched_n < 0) return fail("match the map before reading its matches");
+    if (num_points < 0 || num_points > f->map_matched_n) return fail("more points asked for than the map that was matched holds");
+    const size_t n = num_points, N = f->map_matched_n;
+    if (n == 0) return 0;
+    const uint8_t* o = f->h_map_out.data();                // the match brought everything to the host already
+    if (uv) memcpy(uv, o + 16, n * 2 * sizeof(double));
+    if (feature) memcpy(feature, o + 16 + 16 * N, n * sizeof(int));
+    if (status) memcpy(status, o + 16 + 20 * N, n * sizeof(int));
+    if (cost) memcpy(cost, o + 16 + 24 * N, n * sizeof(int));
     return 0;
 }
 

@@ -15,8 +15,11 @@
 //   k_feat_chain        thread / start feature                    : follow the legs, flag the chains that close
 //   k_feat_compact_match 256 start features / block               : the closed chains in order -> feature indices
 //   k_feat_subpix       thread / match                            : positions with the sub-pixel refinement (fp64)
+//   k_feat_map_search   wave / map point                          : projection, best feature in the window, claim (step 8)
+//   k_feat_map_resolve  thread / map point                        : one point per feature, positions of the owners
 //
-// Every compaction is the stable ballot / popcount one (raster order is part of the definition); plain vector stores only.
+// Every compaction is the stable ballot / popcount one (raster order is part of the definition); plain vector stores only, and in
+// step 8 two integer vector atomics whose results do not depend on their order (a minimum and a count).
 #pragma once
 #include "ps_k_dense.h"
 
@@ -206,22 +209,14 @@ struct FeatList {               // the features of one image
     const short *du, *dv;
 };
 
-// one wave per feature of A: the candidates of B are a contiguous range of its raster-ordered list (rows v + dv_lo ..
-// v + dv_hi); lanes stride over it, test the u window, and the wave takes the minimum of (cost << 32 | index)
-__global__ __launch_bounds__(256) void k_feat_match(FeatList A, FeatList B, int h, int max_features, int du_lo, int du_hi, int dv_lo,
-                                                     int dv_hi, int cost_max, int* __restrict__ out)
-{
-    const int a = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-    if (a >= min(*A.n, max_features)) return;
-    const int2 pa = A.uv[a];
-    uint32_t da[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) da[q] = A.desc[8 * (size_t)a + q];
-    const int k0 = B.row_start[min(max(pa.y + dv_lo, 0), h)], k1 = B.row_start[min(max(pa.y + dv_hi + 1, 0), h)];
+// the best candidate of a descriptor among features k0 .. k1 - 1 of B (a contiguous range of its raster-ordered list: whole
+// rows) whose u lies in u_lo .. u_hi: lanes stride over the range, test the u window, and the wave takes the minimum of
+// (cost << 32 | index) -- lowest cost, ties to the lower index; ~0 without a candidate.  Every lane of the wave calls it.
+PS_DEV unsigned long long feat_best_candidate(const uint32_t* da, const FeatList& B, int k0, int k1, int u_lo, int u_hi, int lane) {
     unsigned long long best = ~0ull;
     for (int k = k0 + lane; k < k1; k += 64) {
-        const int d = B.uv[k].x - pa.x;
-        if (d < du_lo || d > du_hi) continue;
+        const int u = B.uv[k].x;
+        if (u < u_lo || u > u_hi) continue;
         const uint4 b0 = *(const uint4*)(B.desc + 8 * (size_t)k), b1 = *(const uint4*)(B.desc + 8 * (size_t)k + 4);
         unsigned c = __builtin_amdgcn_sad_u8(da[0], b0.x, 0u);
         c = __builtin_amdgcn_sad_u8(da[1], b0.y, c);
@@ -239,6 +234,21 @@ __global__ __launch_bounds__(256) void k_feat_match(FeatList A, FeatList B, int 
         const unsigned long long o = __shfl_xor(best, off);
         best = o < best ? o : best;
     }
+    return best;
+}
+
+// one wave per feature of A: the candidates of B are the rows v + dv_lo .. v + dv_hi of its list
+__global__ __launch_bounds__(256) void k_feat_match(FeatList A, FeatList B, int h, int max_features, int du_lo, int du_hi, int dv_lo,
+                                                     int dv_hi, int cost_max, int* __restrict__ out)
+{
+    const int a = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (a >= min(*A.n, max_features)) return;
+    const int2 pa = A.uv[a];
+    uint32_t da[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) da[q] = A.desc[8 * (size_t)a + q];
+    const int k0 = B.row_start[min(max(pa.y + dv_lo, 0), h)], k1 = B.row_start[min(max(pa.y + dv_hi + 1, 0), h)];
+    const unsigned long long best = feat_best_candidate(da, B, k0, k1, pa.x + du_lo, pa.x + du_hi, lane);
     if (lane == 0) out[a] = (best != ~0ull && (int)(best >> 32) <= cost_max) ? (int)(unsigned)best : -1;
 }
 
@@ -299,6 +309,13 @@ PS_DEV double feat_subpixel(int cm, int c0, int cp) {
     return fabs(d) < 1.0 ? d : 0.0;
 }
 
+// sub-pixel offsets (step 7) of pixel p of image T against a source descriptor: in u, and in v for a temporal leg
+PS_DEV void feat_refine(const FeatList& T, int h, int w, int2 p, const uint32_t* d, bool temporal, double& ou, double& ov) {
+    const int c0 = feat_cost_at(T, h, w, p.x, p.y, d);
+    ou = feat_subpixel(feat_cost_at(T, h, w, p.x - 1, p.y, d), c0, feat_cost_at(T, h, w, p.x + 1, p.y, d));
+    ov = temporal ? feat_subpixel(feat_cost_at(T, h, w, p.x, p.y - 1, d), c0, feat_cost_at(T, h, w, p.x, p.y + 1, d)) : 0.0;
+}
+
 __global__ __launch_bounds__(256) void k_feat_subpix(const int* __restrict__ n_match, int max_features, const int* __restrict__ idx4,
                                                       FeatChain ch, FeatList n0, FeatList n1, FeatList n2, FeatList n3, int h, int w,
                                                       int refinement, double* __restrict__ m8)
@@ -317,10 +334,10 @@ __global__ __launch_bounds__(256) void k_feat_subpix(const int* __restrict__ n_m
             uint32_t d[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) d[q] = node[k - 1].desc[8 * (size_t)prev + q];
-            const int c0 = feat_cost_at(node[k], h, w, p.x, p.y, d);
-            offu = offu + feat_subpixel(feat_cost_at(node[k], h, w, p.x - 1, p.y, d), c0, feat_cost_at(node[k], h, w, p.x + 1, p.y, d));
-            if (ch.temporal[k])
-                offv = offv + feat_subpixel(feat_cost_at(node[k], h, w, p.x, p.y - 1, d), c0, feat_cost_at(node[k], h, w, p.x, p.y + 1, d));
+            double ou, ov;
+            feat_refine(node[k], h, w, p, d, ch.temporal[k] != 0, ou, ov);
+            offu = offu + ou;
+            if (ch.temporal[k]) offv = offv + ov;
         }
         row[2 * ch.col[k]] = (double)p.x + offu;
         row[2 * ch.col[k] + 1] = (double)p.y + offv;
@@ -328,4 +345,85 @@ __global__ __launch_bounds__(256) void k_feat_subpix(const int* __restrict__ n_m
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) m8[8 * (size_t)i + q] = row[q];
+}
+
+// ---- matching by projection (step 8): the map's points against the features of one image ----
+struct FeatMapView {            // pose and calibration of a projection, by value
+    double T[12];               // rows 0..2 of T_cw
+    double cu, cv, fu, fv;
+};
+
+struct FeatMapOut {             // one entry per map point
+    int *feature, *status, *cost;
+    double* uv;
+};
+
+// one wave per map point: project, search the window around the rounded projection, claim the best feature with an integer
+// atomicMin of (cost << 32 | point) -- order-independent, so the owner of every feature is the same in every run
+__global__ __launch_bounds__(256) void k_feat_map_search(int num_points, const double* __restrict__ pts, const uint32_t* __restrict__ desc,
+                                                          FeatMapView V, FeatList B, int h, int w, int max_features, int radius,
+                                                          int cost_max, FeatMapOut out, unsigned long long* __restrict__ claim,
+                                                          int* __restrict__ n_matched)
+{
+#pragma clang fp contract(off)
+    const int i = (int)(((size_t)blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *n_matched = 0;       // counted by k_feat_map_resolve, the next launch
+    if (i >= num_points) return;
+    const double x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
+    const double xc = ((V.T[0] * x + V.T[1] * y) + V.T[2] * z) + V.T[3];
+    const double yc = ((V.T[4] * x + V.T[5] * y) + V.T[6] * z) + V.T[7];
+    const double zc = ((V.T[8] * x + V.T[9] * y) + V.T[10] * z) + V.T[11];
+    const double u = (V.fu * xc) / zc + V.cu, v = (V.fv * yc) / zc + V.cv;
+    const double cen_u = floor(u + 0.5), cen_v = floor(v + 0.5);
+    const bool visible = zc > 0.0 && isfinite(xc) && isfinite(yc) && isfinite(zc) && isfinite(u) && isfinite(v) && cen_u >= 0.0 &&
+                         cen_u < (double)w && cen_v >= 0.0 && cen_v < (double)h;
+    int status = 1, feature = -1, cost = -1;
+    if (visible) {                                                  // uniform over the wave
+        const int ui = (int)cen_u, vi = (int)cen_v;
+        uint32_t da[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) da[q] = desc[8 * (size_t)i + q];
+        const int k0 = B.row_start[min(max(vi - radius, 0), h)], k1 = B.row_start[min(max(vi + radius + 1, 0), h)];
+        const unsigned long long best = feat_best_candidate(da, B, k0, k1, ui - radius, ui + radius, lane);
+        status = 2;
+        if (best != ~0ull && (int)(best >> 32) <= cost_max) {
+            status = 0; feature = (int)(unsigned)best; cost = (int)(best >> 32);
+        }
+    }
+    if (lane != 0) return;
+    if (status == 0 && feature < max_features) atomicMin(claim + feature, ((unsigned long long)(unsigned)cost << 32) | (unsigned)i);
+    out.feature[i] = feature; out.status[i] = status; out.cost[i] = cost;
+}
+
+// thread per map point: a point that does not own its feature loses it (status 3); the owners get their position
+__global__ __launch_bounds__(256) void k_feat_map_resolve(int num_points, const uint32_t* __restrict__ desc, FeatList B, int h, int w,
+                                                           int max_features, int refinement, FeatMapOut out,
+                                                           const unsigned long long* __restrict__ claim, int* __restrict__ n_matched)
+{
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    bool matched = false;
+    if (i < num_points) {
+        double pu = -1.0, pv = -1.0;
+        const int f = out.feature[i];
+        if (out.status[i] == 0 && f >= 0 && f < max_features) {
+            if ((int)(unsigned)claim[f] != i) {
+                out.status[i] = 3; out.feature[i] = -1;
+            } else {
+                matched = true;
+                const int2 p = B.uv[f];
+                double ou = 0.0, ov = 0.0;
+                if (refinement) {
+                    uint32_t d[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) d[q] = desc[8 * (size_t)i + q];
+                    feat_refine(B, h, w, p, d, true, ou, ov);
+                }
+                pu = (double)p.x + ou; pv = (double)p.y + ov;
+            }
+        }
+        out.uv[2 * (size_t)i] = pu; out.uv[2 * (size_t)i + 1] = pv;
+    }
+    const unsigned long long m = __ballot(matched);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_matched, __popcll(m));
 }

@@ -26,10 +26,19 @@ integer up to the one division of the sub-pixel step:
    source descriptor against the target pixel and its two neighbours at +-1: in ``u`` for stereo legs, in ``u`` and
    ``v`` for temporal legs.  A position is its integer pixel plus the offset accumulated up to its leg, so the chain
    follows one scene point; the closing leg refines nothing.
+8. ``match_map`` (matching by projection): a map point ``(x, y, z)`` with its descriptor is projected with ``T_cw`` and
+   ``cam = (cu, cv, fu, fv, ...)`` in float64, one rounding per operation: ``x_c = ((r00 x + r01 y) + r02 z) + t0`` (``y_c``,
+   ``z_c`` likewise), ``u = (fu x_c) / z_c + cu``, ``v = (fv y_c) / z_c + cv``; the window centre is ``ui = floor(u + 0.5)``,
+   ``vi`` likewise.  Status 1 (not visible): ``z_c <= 0``, a non-finite value, or a centre outside the image.  Candidates are
+   the frame's features with ``|u_k - ui| <= radius`` and ``|v_k - vi| <= radius``; cost, winner and tie rule as in step 5;
+   status 2 without a candidate or with the best cost above ``match_cost_max``.  A feature goes to one point only: among the
+   points whose best feature it is, the lowest ``(cost, point index)`` keeps it, the others get status 3 and feature -1 (no
+   second choice).  The position of a matched point (status 0) is the feature's pixel plus the offsets of step 7's temporal
+   leg (map descriptor against the frame's gradient images); with ``refinement`` = 0 the pixel itself.
 """
 import numpy as np
 
-__all__ = ['Params', 'OFFSETS', 'BORDER', 'R_NONE', 'gradients', 'response', 'features', 'match_leg', 'match', 'Frame']
+__all__ = ['Params', 'OFFSETS', 'BORDER', 'R_NONE', 'gradients', 'response', 'features', 'match_leg', 'match', 'match_map', 'Frame']
 
 BORDER = 5
 R_NONE = np.iinfo(np.int64).min
@@ -248,3 +257,71 @@ def match(prev, cur, mode, params=None):
         m[:, 2 * col] = fr.uv[ids, 0] + offu
         m[:, 2 * col + 1] = fr.uv[ids, 1] + offv
     return m, idx
+
+
+def match_map(frame, points_w, descriptors, T_cw, cam, radius, params=None):
+    """Map points matched into a frame by projection (step 8) -> ``(feature, status, cost, uv)``, one entry per point:
+    feature index or -1 (int32), status 0 matched / 1 not visible / 2 no candidate / 3 lost its feature to a better point
+    (int32), cost or -1 unless the status is 0 or 3 (int32), position (N, 2) float64 or -1 unless the status is 0."""
+    p = params or Params()
+    pts = np.asarray(points_w, dtype=np.float64).reshape(-1, 3)
+    desc = np.asarray(descriptors, dtype=np.uint8).reshape(-1, 32)
+    N = pts.shape[0]
+    if desc.shape[0] != N:
+        raise ValueError('match_map: {} points and {} descriptors'.format(N, desc.shape[0]))
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError('match_map: negative radius')
+    T = np.asarray(T_cw, dtype=np.float64).reshape(4, 4)
+    cu, cv, fu, fv = (float(c) for c in tuple(cam)[:4])
+    h, w = frame.du.shape
+    feature = np.full(N, -1, dtype=np.int32)
+    status = np.full(N, 1, dtype=np.int32)
+    cost = np.full(N, -1, dtype=np.int32)
+    uv = np.full((N, 2), -1.0)
+    X, Y, Z = pts[:, 0], pts[:, 1], pts[:, 2]
+    with np.errstate(all='ignore'):
+        xc = ((T[0, 0] * X + T[0, 1] * Y) + T[0, 2] * Z) + T[0, 3]
+        yc = ((T[1, 0] * X + T[1, 1] * Y) + T[1, 2] * Z) + T[1, 3]
+        zc = ((T[2, 0] * X + T[2, 1] * Y) + T[2, 2] * Z) + T[2, 3]
+        u, v = (fu * xc) / zc + cu, (fv * yc) / zc + cv
+        cen_u, cen_v = np.floor(u + 0.5), np.floor(v + 0.5)
+        visible = (zc > 0.) & np.isfinite(xc) & np.isfinite(yc) & np.isfinite(zc) & np.isfinite(u) & np.isfinite(v) & \
+            (cen_u >= 0.) & (cen_u < w) & (cen_v >= 0.) & (cen_v < h)
+    r = min(radius, max(h, w))                                 # a window over the whole image is as large as it gets
+    bd = frame.desc.astype(np.int16)
+    for i in np.nonzero(visible)[0]:
+        ui, vi = int(cen_u[i]), int(cen_v[i])
+        status[i] = 2
+        k0, k1 = frame.row_start[min(max(vi - r, 0), h)], frame.row_start[min(max(vi + r + 1, 0), h)]
+        if k1 <= k0:
+            continue
+        d = frame.uv[k0:k1, 0] - ui
+        cand = np.nonzero((d >= -r) & (d <= r))[0]
+        if cand.shape[0] == 0:
+            continue
+        c = np.abs(bd[k0 + cand] - desc[i].astype(np.int16)).sum(axis=1)
+        j = int(np.argmin(c))                                  # first minimum: the lower feature index
+        if c[j] <= int(p.match_cost_max):
+            feature[i], cost[i], status[i] = k0 + cand[j], c[j], 0
+    # one landmark per feature: the lowest (cost, point index) keeps it
+    cand = np.nonzero(status == 0)[0]
+    order = cand[np.lexsort((cand, cost[cand], feature[cand]))]
+    lost = order[1:][feature[order[1:]] == feature[order[:-1]]]
+    status[lost], feature[lost] = 3, -1
+    won = np.nonzero(status == 0)[0]
+    if won.shape[0]:
+        f = feature[won]
+        uv[won] = frame.uv[f]
+        if p.refinement:
+            ou, ov = _refine(_Descriptors(desc), won, frame, f, True)
+            uv[won, 0] += ou
+            uv[won, 1] += ov
+    return feature, status, cost, uv
+
+
+class _Descriptors:
+    """The one attribute _refine reads of its source frame."""
+
+    def __init__(self, desc):
+        self.desc = desc

@@ -11,6 +11,9 @@ A pushed frame whose bytes equal a frame the matcher holds -- the previous one, 
 them -- is not processed again: the pipelines push the active keyframe in front of every tracking frame.
 ``feature_passes`` counts the images whose features were computed.  ``matches_array()`` returns the matches as arrays
 (the pipelines use it instead of building one Python object per match).
+
+``setMap`` / ``matchMap`` are matching by projection (step 8 of the definition): the map's points, each with the
+descriptor it was created with, against the features of the current frame around their projections under a pose prior.
 """
 import ctypes as C
 
@@ -62,6 +65,8 @@ class Matcher:
         self._lib = None
         self._n = 0
         self._passes_before = 0
+        self._map = None            # (points_w, descriptors) of setMap, kept so that a rebuilt handle gets the map again
+        self._map_on = None         # the handle the map was uploaded to
 
     def setIntrinsics(self, *args):
         """Accepted and ignored (libviso2 uses the calibration for its 3-D outlier checks; RANSAC follows here)."""
@@ -132,6 +137,49 @@ class Matcher:
         nat.check(self._lib.ps_feat_read_features(self._h, int(which), cap, C.byref(n), nat.i32p(uv),
                                                   R.ctypes.data_as(C.POINTER(C.c_int64)), d.ctypes.data_as(nat.c_u8p)))
         return uv[:n.value].copy(), R[:n.value].copy(), d[:n.value].copy()
+
+    def setMap(self, points_w, descriptors):
+        """The map of matching by projection: ``points_w`` (N, 3) float64 in the world frame and their descriptors (N, 32)
+        uint8, as ``features`` returns them.  It stays on the device until the next ``setMap``."""
+        pts = np.ascontiguousarray(np.asarray(points_w, dtype=np.float64).reshape(-1, 3))
+        desc = np.asarray(descriptors)
+        if desc.dtype != np.uint8:
+            raise TypeError('Matcher: descriptors must be uint8, got {}'.format(desc.dtype))
+        desc = np.ascontiguousarray(desc.reshape(-1, 32))
+        if desc.shape[0] != pts.shape[0]:
+            raise ValueError('Matcher: {} points and {} descriptors'.format(pts.shape[0], desc.shape[0]))
+        self._map, self._map_on = (pts, desc), None
+        if self._h is not None:
+            self._upload_map()
+
+    def _upload_map(self):
+        pts, desc = self._map
+        nat.check(self._lib.ps_feat_set_map(self._h, pts.shape[0], nat.f64p(pts), desc.ctypes.data_as(nat.c_u8p)))
+        self._map_on = self._h
+
+    def matchMap(self, T_cw, camera, radius):
+        """The map's points matched into the current frame's (left) image by projection with the pose prior ``T_cw`` (4 x 4
+        or an SE3) and ``camera`` (an object with cu cv fu fv, or a tuple beginning with them), inside a window of ``radius``
+        pixels around every projection -> ``(feature, status, cost, uv)``, one entry per map point: feature index or -1,
+        status 0 matched / 1 not visible / 2 no candidate / 3 lost its feature to a better point, cost (-1 unless the status
+        is 0 or 3), position (N, 2) with the sub-pixel refinement (-1 unless the status is 0)."""
+        if self._h is None:
+            raise nat.NativeError('Matcher: push a frame before matching the map')
+        if self._map is not None and self._map_on is not self._h:
+            self._upload_map()
+        T = np.ascontiguousarray(T_cw.as_matrix() if hasattr(T_cw, 'as_matrix') else T_cw, dtype=np.float64).reshape(4, 4)
+        cam = np.zeros(5)
+        cam[:4] = [camera.cu, camera.cv, camera.fu, camera.fv] if hasattr(camera, 'cu') else [float(c) for c in tuple(camera)[:4]]
+        n = C.c_int32()
+        p = self.params._native()
+        nat.check(self._lib.ps_feat_match_map(self._h, nat.f64p(T), nat.f64p(cam), int(radius), C.byref(p), C.byref(n)))
+        self.num_map_matched = n.value
+        N = self._map[0].shape[0]
+        feature, status, cost = (np.zeros(N, dtype=np.int32) for _ in range(3))
+        uv = np.zeros((N, 2))
+        if N:
+            nat.check(self._lib.ps_feat_read_map_matches(self._h, N, nat.i32p(feature), nat.i32p(status), nat.i32p(cost), nat.f64p(uv)))
+        return feature, status, cost, uv
 
     @property
     def feature_passes(self):

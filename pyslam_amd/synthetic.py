@@ -523,6 +523,14 @@ def stereo_sequence(h=96, w=128, n_frames=8, seed=0, step=(0.02, -0.01, 0.04, 0.
     return dict(left=left, right=right, depth=depth, cam=(cu, cv, fu, fv, baseline, w, h), T_c_w=T_c_w)
 
 
+def mono_sequence(h=96, w=128, n_frames=8, seed=0, **kw):
+    """The left camera of ``stereo_sequence`` (same arguments) as a monocular sequence: ``images`` (n, h, w) uint8, ``depth``
+    (n, h, w) true camera z of every pixel, ``T_c_w`` (n, 4, 4) and ``cam`` = (cu, cv, fu, fv, w, h)."""
+    seq = stereo_sequence(h, w, n_frames, seed=seed, **kw)
+    cu, cv, fu, fv = seq['cam'][:4]
+    return dict(images=seq['left'], depth=seq['depth'], T_c_w=seq['T_c_w'], cam=(cu, cv, fu, fv, w, h))
+
+
 def stereo_correspondence(seq, f0, f1, uv):
     """True positions of the left pixels ``uv`` (n, 2; integer) of frame f0 of a stereo_sequence in the other images:
     (n, 8) with the columns u1p v1p u2p v2p u1c v1c u2c v2c (1 left, 2 right; p frame f0, c frame f1)."""
