@@ -14,11 +14,16 @@
 //   * per iteration ONE exchange: a wave publishes the six sums of its task as self-tagged 8-byte granules {tag | half of the
 //     double} with write-through stores, every workgroup gathers all of them with relaxed agent-scope loads (no flags, no
 //     fences, no grid barrier: the data is the flag -- /opt/skills/guides/cdna_hip_programming.md guideline 16, form R2),
-//     double-buffered by the parity of the iteration (a workgroup can only be one exchange ahead of the slowest);
-//   * gamma = r.r and delta = w.r are summed by every workgroup itself, in the same order.
+//     double-buffered by the parity of the iteration (a workgroup can only be one exchange ahead of the slowest).  A thread
+//     loads the granules of ITS four entries' tasks itself and adds them in task order: no staging in LDS, and TWO workgroup
+//     barriers per iteration (r_new in LDS before the products; the partial sums of delta), not three;
+//   * gamma = r.r and delta = w.r are summed by every workgroup itself, in the same order;
+//   * gamma_new = r_new . r_new is known BEFORE the exchange, with the same bits everywhere: a solve that has converged leaves
+//     there, without the exchange whose w_new and delta nothing would read -- K exchanges for K iterations, not K + 1.
 // Measured on the chip before it was built (tools/probes/allgather_probe.hip): 2.0-2.7 us per exchange for 32 workgroups of 512
 // threads, whatever their number -- against 5.4 us per launch.  In the kernel: ~4.5 us per CG iteration at C3 (58 workgroups),
-// 3.6 on a 100-pose graph; two instantiations by the number of exchanged sums per thread (6: up to 512 tasks, 12: up to 1 024).
+// 3.6 on a 100-pose graph (the flat gather through LDS of round 5, two instantiations by the number of exchanged sums per
+// thread; with the gather per entry there is one per D, up to 1 024 tasks, and an iteration at C3 is ~0.45 us shorter).
 // Every spin is bounded: a workgroup that does not see its granules within `spin_limit` passes or one second reports a breakdown
 // (ST_PCG_DONE = 2, ST_PERSIST_FAIL) and leaves; the host then solves with the launch-per-iteration kernels and stops using
 // this one on the handle.
@@ -29,8 +34,9 @@
 #define PS_CP_NQ 6                      // blocks per lane slot: a task has at most 8 * PS_CP_NQ blocks
 #define PS_CP_TASKB (8 * PS_CP_NQ)
 #define PS_CP_NV 4                      // vector entries per thread: n <= PS_CP_NV * PS_CP_NT
-#define PS_CP_NE_MAX 12                 // exchanged sums per thread (template NE: 6 or 12): tasks * D <= NE * PS_CP_NT
+#define PS_CP_MAXEX (12 * PS_CP_NT)     // exchanged sums per iteration: tasks * D <= PS_CP_MAXEX (1 024 tasks of SE(3) rows)
 #define PS_CP_MAXN (PS_CP_NV * PS_CP_NT)
+#define PS_CP_LONG 4                    // tasks of a long row (more than two tasks) gathered at a time
 // Wall-clock bound of a spin (wall_clock64: 100 MHz), beside the bound in passes: ONE SECOND.  Round 6 first took the 20 ms
 // k_xcg_persist had: with two PROCESSES on one device (tests/test_gpu_sharded.py: two ranks on one GPU) the scheduler suspends a
 // process's queues for whole time slices, a spin that straddles a slice sees the clock jump by more than that, and one solve in
@@ -64,7 +70,13 @@ PS_DEV void cp_put(ps_u64* g, unsigned tag, double v) {
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(g), "v"(q) : "memory");
 }
 
-template <int D, int NE>
+// one granule, `off` bytes into the exchange buffer (32-bit offset arithmetic: with a 64-bit index per load the 24 loads of a
+// gather pass took the D = 6 kernel to 60 bytes of scratch per lane; so it has none, at 256 VGPRs)
+PS_DEV ps_u64 cp_get(const ps_u64* buf, unsigned off) {
+    return __hip_atomic_load((const ps_gu64*)((const char*)buf + off), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <int D>
 __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
     int n /* augmented unknowns */, int ntasks, const CpTask* __restrict__ tasks,
     const int32_t* __restrict__ row_task0 /* first task of every block row; [rows] = ntasks */,
@@ -78,7 +90,7 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
 {
     constexpr int DD = D * D;
     __shared__ double rn[PS_CP_MAXN];
-    __shared__ double wex[NE * PS_CP_NT];              // the exchanged sums of one iteration
+    __shared__ double yc[PS_CP_MAXN];                  // the recovery's y (the exchanged sums go from the granules straight to registers)
     __shared__ double red[2][2][PS_CP_NT / 64];
     __shared__ int bad;
     const int t = threadIdx.x, wv = t >> 6, lane = t & 63, kk = lane >> 3, r = lane & 7;
@@ -116,6 +128,9 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
             e0[v] = ta * D + (i - row * D); en[v] = row_task0[row + 1] - ta;
         }
     }
+    int lv = -1, le0 = 0, len = 0;                           // the thread's first entry of a row of more than two tasks
+#pragma unroll
+    for (int v = PS_CP_NV - 1; v >= 0; --v) if (en[v] > 2) { lv = v; le0 = e0[v]; len = en[v]; }
     if (status[ST_PCG_DONE]) return;                         // (as every launch of the per-iteration form)
     // (1 / gamma_prev and 1 / alpha_prev are formed while the exchange is in flight: ONE division between an iteration's dot
     //  products and its recurrences -- the per-launch kernels do three, which changes the last bits of alpha and beta, not more)
@@ -166,6 +181,16 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
         double gamma_next = 0.0;                             // r_new . r_new, known before the exchange
 #pragma unroll
         for (int w2 = 0; w2 < PS_CP_NT / 64; ++w2) gamma_next += rd[0][w2];
+        // ---- converged already?  Then pass k + 1 would only find that out and leave: nothing reads the w_new and delta of this
+        // pass (x and p are final above, w and s are never written back), so leave HERE, before the exchange, exactly as the top
+        // of pass k + 1 does.  Only where that pass would have run (k + 1 < nlaunch - 1: at the launch cap nothing changes).
+        // The decision may depend ONLY on what every workgroup holds with the same bits -- gamma_next, thresh, k, nlaunch -- and
+        // never on what one workgroup knows alone (`bad`): a workgroup that stays would wait for granules nobody publishes.
+        if (k >= 0 && k + 1 < nlaunch - 1 && !(gamma_next > thresh)) {
+            if (chief) { status[ST_PCG_DONE] = (gamma_next != gamma_next) ? 2 : 1; scalars[SC_RRFINAL] = gamma_next; }
+            converged = !(gamma_next != gamma_next);
+            break;
+        }
         // ---- this wave's task: six sums of S^(row, its blocks) r_new, published as tagged granules
         const unsigned tag = salt * 4096u + (unsigned)(k + 2);
         ps_u64* buf = exch + (size_t)(k & 1) * nex * 2;
@@ -182,28 +207,69 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
             acc += __shfl_xor(acc, 32, 64);
             if (task < ntasks && lane < D) cp_put(buf + 2 * ((size_t)task * D + lane), tag, acc);
         }
+        if (dbg) ck[6] += 1;                                 // (measurement build: exchanges of this launch)
         if (k >= 0) { inv_gprev = 1.0 / gamma_now; inv_aprev = 1.0 / alpha_now; }     // (while the exchange is in flight)
         PS_CP_CLK(2);
-        // ---- gather every published sum (flat: the loads of a pass are independent, one round trip), then w_new of every entry
-        // = the sum of its row's tasks, in task order, from LDS
+        // ---- gather: every thread loads the granules of ITS entries' tasks itself and sums them in task order from 0.0 (what the
+        // flat gather + LDS redistribution summed, bit for bit) -- no staging array, no barrier between gather and dots.  The loads
+        // of a pass are issued before any is waited on (one round trip): two tasks per entry unrolled (every fine row), tasks
+        // 2 .. 2 + PS_CP_LONG - 1 of the thread's first long entry beside them (a coarse row at C3 has five tasks); what is left
+        // (longer rows, a thread's further long entries) follows PS_CP_LONG tasks at a time, in the same pass.
         {
-            double gv[NE];
             bool ok = false;
             const long long t_enter = (long long)wall_clock64();        // (bounded in wall-clock time too: PS_PERSIST_TIMEOUT_TICKS)
             for (unsigned spins = 0; !ok; ++spins) {
                 ok = true;
+                ps_u64 ga[PS_CP_NV][2], gb[PS_CP_NV][2], xa[PS_CP_LONG], xb[PS_CP_LONG];
 #pragma unroll
-                for (int v = 0; v < NE; ++v) {
-                    const int j = t + v * PS_CP_NT;
-                    gv[v] = 0.0;
-                    if (j < (int)nex) {
-                        const ps_u64* g = buf + 2 * (size_t)j;
-                        const ps_u64 a = __hip_atomic_load((const ps_gu64*)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const ps_u64 b = __hip_atomic_load((const ps_gu64*)(g + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ok = ok && (unsigned)(a >> 32) == tag && (unsigned)(b >> 32) == tag;
-                        gv[v] = __longlong_as_double((long long)((a & 0xffffffffull) | (b << 32)));
+                for (int v = 0; v < PS_CP_NV; ++v)
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) {
+                        ga[v][m] = gb[v][m] = 0;
+                        if (m < en[v]) {
+                            ga[v][m] = cp_get(buf, 16u * (unsigned)e0[v] + 16u * (m * D));
+                            gb[v][m] = cp_get(buf, 16u * (unsigned)e0[v] + 16u * (m * D) + 8u);
+                        }
+                    }
+#pragma unroll
+                for (int j = 0; j < PS_CP_LONG; ++j) {
+                    xa[j] = xb[j] = 0;
+                    if (2 + j < len) {
+                        xa[j] = cp_get(buf, 16u * (unsigned)le0 + 16u * ((2 + j) * D));
+                        xb[j] = cp_get(buf, 16u * (unsigned)le0 + 16u * ((2 + j) * D) + 8u);
                     }
                 }
+#define PS_CP_TAKE(a_, b_) do { ok = ok && (unsigned)((a_) >> 32) == tag && (unsigned)((b_) >> 32) == tag;                   \
+                                wsum += __longlong_as_double((long long)(((a_) & 0xffffffffull) | ((b_) << 32))); } while (0)
+#pragma unroll
+                for (int v = 0; v < PS_CP_NV; ++v) {
+                    double wsum = 0.0;
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) if (m < en[v]) PS_CP_TAKE(ga[v][m], gb[v][m]);
+                    if (en[v] > 2) {                                 // a long row
+                        int m0 = 2;
+                        if (v == lv) {
+#pragma unroll
+                            for (int j = 0; j < PS_CP_LONG; ++j) if (2 + j < len) PS_CP_TAKE(xa[j], xb[j]);
+                            m0 = 2 + PS_CP_LONG;
+                        }
+                        for (; m0 < en[v]; m0 += PS_CP_LONG) {
+                            ps_u64 ya[PS_CP_LONG], yb[PS_CP_LONG];
+#pragma unroll
+                            for (int j = 0; j < PS_CP_LONG; ++j) {
+                                ya[j] = yb[j] = 0;
+                                if (m0 + j < en[v]) {
+                                    ya[j] = cp_get(buf, 16u * (unsigned)(e0[v] + m0 * D) + 16u * (j * D));
+                                    yb[j] = cp_get(buf, 16u * (unsigned)(e0[v] + m0 * D) + 16u * (j * D) + 8u);
+                                }
+                            }
+#pragma unroll
+                            for (int j = 0; j < PS_CP_LONG; ++j) if (m0 + j < en[v]) PS_CP_TAKE(ya[j], yb[j]);
+                        }
+                    }
+                    vw[v] = wsum;
+                }
+#undef PS_CP_TAKE
                 ok = __all(ok);
                 if (!ok) {
                     if (spins > spin_limit || (long long)wall_clock64() - t_enter > PS_PERSIST_TIMEOUT_TICKS) { bad = 1; break; }
@@ -211,18 +277,8 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
                     ck[7] += 1;
                 }
             }
-#pragma unroll
-            for (int v = 0; v < NE; ++v) { const int j = t + v * PS_CP_NT; if (j < (int)nex) wex[j] = gv[v]; }
         }
         PS_CP_CLK(3);
-        __syncthreads();
-        PS_CP_CLK(4);
-#pragma unroll
-        for (int v = 0; v < PS_CP_NV; ++v) {
-            double wsum = 0.0;
-            for (int m = 0; m < en[v]; ++m) wsum += wex[e0[v] + m * D];
-            vw[v] = wsum;
-        }
         // ---- gamma = r.r, delta = w.r over all entries, by every workgroup in the same order
         double ds = 0.0;
 #pragma unroll
@@ -245,7 +301,7 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
     if (blockIdx.x == 0) {
         if (converged && rec.x) {                            // the recovery of k_coarse_recover, on x^ as this workgroup holds it
             const int nc = rec.ncb * D, nf = rec.nr * D;
-            __syncthreads();                                 // (every wave has left the loop: rn, wex are free)
+            __syncthreads();                                 // (every wave has left the loop: rn is free)
 #pragma unroll
             for (int v = 0; v < PS_CP_NV; ++v) { const int i = t + v * PS_CP_NT; if (i < n) rn[i] = vx[v]; }
             __syncthreads();
@@ -255,7 +311,7 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
                 double v = 0.0;
                 if (kq < nc) for (int m = kq + sub; m < nc; m += 8) v += rec.Lci[(size_t)m * nc + kq] * xc[m];
                 v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-                if (kq < nc && sub == 0) wex[kq] = v;
+                if (kq < nc && sub == 0) yc[kq] = v;
             }
             __syncthreads();
             for (int e = t; e < nf; e += PS_CP_NT) {
@@ -263,7 +319,7 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
                 const double w0 = rec.pw0[i], w1 = rec.pw1[i];
                 double z[D];
 #pragma unroll
-                for (int m = 0; m < D; ++m) z[m] = w0 * wex[q * D + m] + ((q + 1 < rec.ncb) ? w1 * wex[(q + 1) * D + m] : 0.0);
+                for (int m = 0; m < D; ++m) z[m] = w0 * yc[q * D + m] + ((q + 1 < rec.ncb) ? w1 * yc[(q + 1) * D + m] : 0.0);
                 double v = 0.0;
 #pragma unroll
                 for (int a = 0; a < D; ++a) {

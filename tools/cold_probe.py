@@ -28,6 +28,7 @@ if '--stages' in sys.argv:    # an event pair around every stage: per solve, the
 start = (lp.poses.copy(), lp.points.copy())
 opt = bench.example_options()
 tot, its = 0.0, 0
+pcg_total = 0        # CG iterations of every solve, the first included: beside the exchange count of PS_CP_CLOCKS (measurement build)
 all_ms, all_dt = [], []
 for s in range(solves + 1):
     dev.reset_solver_state(); dev.set_params(*start); torch.cuda.synchronize()
@@ -39,6 +40,7 @@ for s in range(solves + 1):
     if s:
         tot += dt; its += len(ms); all_ms.append(ms); all_dt.append(dt)
     print('solve %d: %.4f ms, calls %s, pcg %s, outside the calls %.4f ms' % (s, dt, ['%.4f' % m for m in ms], [a for a, _ in stats], dt - sum(ms)))
+    pcg_total += sum(a for a, _ in stats)
     if '--stages' in sys.argv:
         st = dev.stage_times(reset=True)
         print('   stages (ms summed over the solve, launches): ' + ', '.join('%s %.4f/%d' % (k, v[0], v[1]) for k, v in st.items() if v[1]))
@@ -49,4 +51,5 @@ print('%s %d %d%s %s loop, median over %d solves: solve %.4f ms = %.4f ms per it
     'graph' if '--pg' in sys.argv else 'BA', kf, lm, (' [' + ' '.join(o[6:] for o in opts) + ']') if opts else '', 'core' if core_loop else 'python',
     solves, float(np.median(all_dt)), float(np.median(all_dt)) / n_calls, ['%.4f' % float(np.median([m[k] for m in all_ms])) for k in range(n_calls)],
     [a for a, _ in stats]))
+print('CG iterations over all %d solves: %d' % (solves + 1, pcg_total))
 dev.close()
