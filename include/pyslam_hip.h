@@ -751,6 +751,18 @@ int ps_feat_set_map(ps_feat* h, int32_t num_points, const double* points_w, cons
 int ps_feat_match_map(ps_feat* h, const double* T_cw, const double* cam5, int32_t radius, const ps_feat_params* params,
                       int32_t* num_matched);
 int ps_feat_read_map_matches(ps_feat* h, int32_t num_points, int32_t* feature, int32_t* status, int32_t* cost, double* uv);
+/* Matching without a prior (step 9 of the definition): every point of the map against every feature of the current frame's left
+   image (computed first if it has none under these parameters), no projection.  A point's best feature is the one with the lowest
+   (cost, index); it is accepted when the cost is at most match_cost_max and ratio_den * cost < ratio_num * second-best cost
+   (0 < ratio_num <= ratio_den <= 32768; a frame with one feature has no second-best cost and accepts).  Features then go to one
+   point only and positions are refined as in ps_feat_match_map.  One wait; ps_feat_read_map_matches hands out feature / status /
+   cost / uv of this match -- status 0 matched, 2 no feature within match_cost_max, 3 lost its feature, 4 ambiguous (cost kept,
+   feature -1); 1 does not occur -- and ps_feat_read_map_second the second-best costs (-1 where there is none or the status is 2).
+   Room for the second-best costs (4 bytes per point of the map's capacity) is allocated at the first global match
+   (ps_feat_device_bytes grows by it then).
+   ps_feat_read_map_second fails unless the last map match was a global one. */
+int ps_feat_match_map_global(ps_feat* h, int32_t ratio_num, int32_t ratio_den, const ps_feat_params* params, int32_t* num_matched);
+int ps_feat_read_map_second(ps_feat* h, int32_t num_points, int32_t* second);
 /* number of images whose features were computed since create (a recognised frame adds none) */
 int ps_feat_feature_passes(ps_feat* h, int64_t* passes);
 int ps_feat_device_bytes(ps_feat* h, int64_t* bytes);

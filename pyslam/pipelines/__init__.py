@@ -6,4 +6,4 @@ from pyslam_amd.pipelines.dense import DenseVOPipeline, DenseRGBDPipeline  # noq
 from pyslam_amd.pipelines.keyframes import (Keyframe, DenseKeyframe, DenseRGBDKeyframe,  # noqa: F401
                                             SparseStereoKeyframe, SparseRGBDKeyframe)
 from pyslam_amd.pipelines.sparse import SparseVOPipeline, SparseStereoPipeline, SparseRGBDPipeline  # noqa: F401
-from pyslam_amd.pipelines.mono import track_frame, SparseMonoPipeline, SparseMonoKeyframe  # noqa: F401
+from pyslam_amd.pipelines.mono import track_frame, relocalise_frame, SparseMonoPipeline, SparseMonoKeyframe  # noqa: F401

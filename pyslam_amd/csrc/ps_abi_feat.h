@@ -7,7 +7,8 @@
 // tracking frame.  Everything is allocated at create time; a match is a fixed sequence of launches on the handle's
 // stream with one synchronisation at its end.  The one exception is the map of matching by projection (ps_feat_set_map,
 // step 8 of the definition): its buffers are allocated at the first ps_feat_set_map and grow with the map, so a handle
-// that never sets one holds exactly what it was created with.
+// that never sets one holds exactly what it was created with.  Likewise the second-best costs of matching without a prior
+// (ps_feat_match_map_global, step 9): the map's result block has room for them from the first such match on.
 
 extern "C++" {
 struct PsFeatImage {
@@ -48,10 +49,14 @@ struct ps_feat {
     // the map of matching by projection: nothing of it exists before the first ps_feat_set_map
     bool map_set = false;
     int map_n = 0, map_cap = 0, h_n_map_matched = 0, map_matched_n = -1;
+    bool map_global_used = false, map_matched_global = false;      // a global match has run; the last map match was one
+    // the second-best costs of a global match lie behind the block of map_out, which is that much larger (map_cap ints, at least
+    // 16 bytes) from the first global match on
     double* map_pts = nullptr;
     uint32_t* map_desc = nullptr;
     uint8_t* map_out = nullptr;             // [count, 16 bytes | uv 2N doubles | feature N | status N | cost N] of the N matched last
-    std::vector<uint8_t> h_map_out;         // its copy on the host: one download per match, read from there
+    std::vector<uint8_t> h_map_out;         // its copy on the host: one download per match, read from there (a global match:
+                                            // with the N second-best costs behind the cost array)
     unsigned long long* map_claim = nullptr;
     std::vector<void*> map_allocs;          // the buffers that grow with the map
     int64_t map_bytes = 0;
@@ -73,6 +78,19 @@ struct ps_feat {
         for (void* p : map_allocs) hipFree(p);
         map_allocs.clear();
         bytes -= map_bytes; map_bytes = 0; map_cap = 0;
+    }
+    static size_t map_out_bytes(size_t n, bool with_second) { return 16 + 28 * n + (with_second ? std::max<size_t>(4 * n, 16) : 0); }
+    // the first global match: map_out makes room for the second-best costs (its contents are on the host already)
+    int grow_map_out_for_second() {
+        void* old = map_cap ? map_out : nullptr;           // a map that never held a point has no block yet: room for the costs alone
+        const int64_t old_b = (int64_t)map_out_bytes(map_cap, false);
+        if (alloc_map(&map_out, old ? map_out_bytes(map_cap, true) : 16)) { map_out = (uint8_t*)old; return -1; }
+        if (old) {
+            hipFree(old);
+            map_allocs.erase(std::find(map_allocs.begin(), map_allocs.end(), old));
+            map_bytes -= old_b; bytes -= old_b;
+        }
+        return 0;
     }
     ~ps_feat() { for (void* p : map_allocs) hipFree(p); for (void* p : allocs) hipFree(p); }
 };
@@ -256,7 +274,8 @@ int ps_feat_set_map(ps_feat* f, int32_t num_points, const double* points_w, cons
         f->free_map();
         f->map_set = false;
         const size_t n = num_points;
-        if (f->alloc_map(&f->map_pts, 3 * n) || f->alloc_map(&f->map_desc, 8 * n) || f->alloc_map(&f->map_out, 16 + 28 * n)) {
+        if (f->alloc_map(&f->map_pts, 3 * n) || f->alloc_map(&f->map_desc, 8 * n) ||
+            f->alloc_map(&f->map_out, ps_feat::map_out_bytes(n, f->map_global_used))) {
             f->free_map();
             return -1;
         }
@@ -286,6 +305,7 @@ int ps_feat_match_map(ps_feat* f, const double* T_cw, const double* cam5, int32_
     PsFeatFrame& Cf = f->frame[f->cur];
     if (feat_frame_features(f, Cf, p)) return -1;
     f->map_matched_n = f->map_n;
+    f->map_matched_global = false;
     f->h_n_map_matched = 0;
     const int N = f->map_n, h = Cf.h, w = Cf.w;
     if (N == 0) return 0;
@@ -325,6 +345,57 @@ int ps_feat_read_map_matches(ps_feat* f, int32_t num_points, int32_t* feature, i
     if (feature) memcpy(feature, o + 16 + 16 * N, n * sizeof(int));
     if (status) memcpy(status, o + 16 + 20 * N, n * sizeof(int));
     if (cost) memcpy(cost, o + 16 + 24 * N, n * sizeof(int));
+    return 0;
+}
+
+int ps_feat_match_map_global(ps_feat* f, int32_t ratio_num, int32_t ratio_den, const ps_feat_params* params, int32_t* num_matched) {
+    if (!f || !params || !num_matched) return fail("null argument");
+    *num_matched = 0;
+    const ps_feat_params& p = *params;
+    if (p.nms_n < 1 || p.nms_n > 3) return fail("nms_n must be 1..3");
+    if (p.max_features < 1 || p.max_features > f->max_features) return fail("max_features outside the handle's capacity");
+    if (ratio_num < 1 || ratio_num > ratio_den || ratio_den > 32768) return fail("the ratio must satisfy 0 < num <= den <= 32768");
+    if (f->cur < 0) return fail("push a frame before matching the map");
+    if (!f->map_set) return fail("set a map before matching it");
+    PsFeatFrame& Cf = f->frame[f->cur];
+    if (feat_frame_features(f, Cf, p)) return -1;
+    if (!f->map_global_used) {
+        HIP_OK(hipStreamSynchronize(f->stream));           // nothing in flight reads the block that is replaced
+        if (f->grow_map_out_for_second()) return -1;
+        f->map_global_used = true;
+    }
+    f->map_matched_n = f->map_n;
+    f->map_matched_global = true;
+    f->h_n_map_matched = 0;
+    const int N = f->map_n, h = Cf.h, w = Cf.w;
+    if (N == 0) return 0;
+    // the block of ps_feat_match_map with the second-best costs behind it
+    uint8_t* o = f->map_out;
+    const size_t n = N, total = 16 + 32 * n;
+    int* count = (int*)o;
+    const FeatMapOut out{(int*)(o + 16 + 16 * n), (int*)(o + 16 + 20 * n), (int*)(o + 16 + 24 * n), (double*)(o + 16)};
+    hipStream_t s = f->stream;
+    HIP_OK(hipMemsetAsync(f->map_claim, 0xff, (size_t)f->max_features * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_feat_map_search_all, dim3(cdiv(N, 64)), dim3(256), 0, s, N, (const uint32_t*)f->map_desc, Cf.im[0].list(),
+                       (int)p.max_features, (int)p.match_cost_max, (int)ratio_num, (int)ratio_den, out, (int*)(o + 16 + 28 * n),
+                       f->map_claim, count);
+    hipLaunchKernelGGL(k_feat_map_resolve, dim3(cdiv(N, 256)), dim3(256), 0, s, N, (const uint32_t*)f->map_desc, Cf.im[0].list(), h, w,
+                       (int)p.max_features, (int)p.refinement, out, (const unsigned long long*)f->map_claim, count);
+    HIP_OK(hipGetLastError());
+    f->h_map_out.resize(total);
+    HIP_OK(hipMemcpyAsync(f->h_map_out.data(), o, total, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    memcpy(&f->h_n_map_matched, f->h_map_out.data(), sizeof(int));
+    *num_matched = f->h_n_map_matched;
+    return 0;
+}
+
+int ps_feat_read_map_second(ps_feat* f, int32_t num_points, int32_t* second) {
+    if (!f) return fail("null handle");
+    if (f->map_matched_n < 0 || !f->map_matched_global) return fail("the last map match was not a global one: no second-best costs");
+    if (num_points < 0 || num_points > f->map_matched_n) return fail("more points asked for than the map that was matched holds");
+    const size_t n = num_points, N = f->map_matched_n;
+    if (n && second) memcpy(second, f->h_map_out.data() + 16 + 28 * N, n * sizeof(int));
     return 0;
 }
 

@@ -35,10 +35,17 @@ integer up to the one division of the sub-pixel step:
    points whose best feature it is, the lowest ``(cost, point index)`` keeps it, the others get status 3 and feature -1 (no
    second choice).  The position of a matched point (status 0) is the feature's pixel plus the offsets of step 7's temporal
    leg (map descriptor against the frame's gradient images); with ``refinement`` = 0 the pixel itself.
+9. ``match_map_global`` (matching without a prior): every map descriptor against every one of the frame's ``F`` features, no
+   projection.  ``c(i, k)`` is step 5's cost; ``best`` is the feature with the lowest ``(c, k)``, ``c1`` its cost, ``c2`` the lowest
+   cost over the features ``k != best`` (none when ``F < 2``).  Status 2 (no candidate): ``F == 0`` or ``c1 > match_cost_max``;
+   else status 4 (ambiguous) when ``c2`` exists and ``ratio_den c1 >= ratio_num c2`` (``0 < ratio_num <= ratio_den <= 32768``,
+   64-bit products: a minimum reached by two features is always ambiguous, and so is ``c1 = c2 = 0``); else status 0, after which
+   step 8's one-landmark-per-feature rule (status 3) and sub-pixel position apply unchanged.  Status 1 does not occur.  ``cost``
+   is ``c1`` and ``second`` is ``c2`` (-1 where it does not exist) for the statuses 0, 3 and 4, both -1 for status 2.
 """
 import numpy as np
 
-__all__ = ['Params', 'OFFSETS', 'BORDER', 'R_NONE', 'gradients', 'response', 'features', 'match_leg', 'match', 'match_map', 'Frame']
+__all__ = ['Params', 'OFFSETS', 'BORDER', 'R_NONE', 'gradients', 'response', 'features', 'match_leg', 'match', 'match_map', 'match_map_global', 'Frame']
 
 BORDER = 5
 R_NONE = np.iinfo(np.int64).min
@@ -304,7 +311,13 @@ def match_map(frame, points_w, descriptors, T_cw, cam, radius, params=None):
         j = int(np.argmin(c))                                  # first minimum: the lower feature index
         if c[j] <= int(p.match_cost_max):
             feature[i], cost[i], status[i] = k0 + cand[j], c[j], 0
-    # one landmark per feature: the lowest (cost, point index) keeps it
+    _claim_and_refine(frame, desc, feature, status, cost, uv, p)
+    return feature, status, cost, uv
+
+
+def _claim_and_refine(frame, desc, feature, status, cost, uv, p):
+    """The end of steps 8 and 9, in place: one landmark per feature -- the lowest (cost, point index) keeps it, the others get
+    status 3 and feature -1 -- and the positions of the owners."""
     cand = np.nonzero(status == 0)[0]
     order = cand[np.lexsort((cand, cost[cand], feature[cand]))]
     lost = order[1:][feature[order[1:]] == feature[order[:-1]]]
@@ -317,7 +330,41 @@ def match_map(frame, points_w, descriptors, T_cw, cam, radius, params=None):
             ou, ov = _refine(_Descriptors(desc), won, frame, f, True)
             uv[won, 0] += ou
             uv[won, 1] += ov
-    return feature, status, cost, uv
+
+
+def match_map_global(frame, descriptors, ratio=(4, 5), params=None):
+    """Map descriptors matched into a frame without a prior (step 9) -> ``(feature, status, cost, second, uv)``, one entry per map
+    point: feature index or -1 (int32), status 0 matched / 2 no candidate / 3 lost its feature to a better point / 4 ambiguous
+    (int32), best cost and second-best cost (int32; -1 for status 2, ``second`` also where the frame has a single feature),
+    position (N, 2) float64 or -1 unless the status is 0.  ``ratio`` = (num, den): accepted when ``den * cost < num * second``."""
+    p = params or Params()
+    num, den = int(ratio[0]), int(ratio[1])
+    if not 0 < num <= den <= 32768:
+        raise ValueError('match_map_global: the ratio must satisfy 0 < num <= den <= 32768, got {}'.format(tuple(ratio)))
+    desc = np.asarray(descriptors, dtype=np.uint8).reshape(-1, 32)
+    N, F = desc.shape[0], len(frame)
+    feature = np.full(N, -1, dtype=np.int32)
+    status = np.full(N, 2, dtype=np.int32)
+    cost = np.full(N, -1, dtype=np.int32)
+    second = np.full(N, -1, dtype=np.int32)
+    uv = np.full((N, 2), -1.0)
+    bd = frame.desc.astype(np.int16)
+    for i in range(N if F else 0):
+        c = np.abs(bd - desc[i].astype(np.int16)).sum(axis=1).astype(np.int64)
+        j = int(np.argmin(c))                                  # first minimum: the lower feature index
+        c1 = int(c[j])
+        if c1 > int(p.match_cost_max):
+            continue
+        cost[i] = c1
+        if F >= 2:
+            c[j] = np.iinfo(np.int64).max
+            second[i] = c2 = int(c.min())
+            if den * c1 >= num * c2:
+                status[i] = 4
+                continue
+        feature[i], status[i] = j, 0
+    _claim_and_refine(frame, desc, feature, status, cost, uv, p)
+    return feature, status, cost, second, uv
 
 
 class _Descriptors:

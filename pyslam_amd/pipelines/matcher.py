@@ -14,6 +14,7 @@ them -- is not processed again: the pipelines push the active keyframe in front 
 
 ``setMap`` / ``matchMap`` are matching by projection (step 8 of the definition): the map's points, each with the
 descriptor it was created with, against the features of the current frame around their projections under a pose prior.
+``matchMapGlobal`` is matching without a prior (step 9): every map point against every feature, with a second-best ratio test.
 """
 import ctypes as C
 
@@ -180,6 +181,29 @@ class Matcher:
         if N:
             nat.check(self._lib.ps_feat_read_map_matches(self._h, N, nat.i32p(feature), nat.i32p(status), nat.i32p(cost), nat.f64p(uv)))
         return feature, status, cost, uv
+
+    def matchMapGlobal(self, ratio=(4, 5)):
+        """The map's points matched into the current frame's (left) image without a pose: every point against every feature,
+        accepted when ``ratio[1] * cost < ratio[0] * second-best cost`` (integers, ``0 < num <= den <= 32768``) ->
+        ``(feature, status, cost, second, uv)``, one entry per map point: feature index or -1, status 0 matched / 2 no feature
+        within ``match_cost_max`` / 3 lost its feature to a better point / 4 ambiguous, best and second-best cost (-1 for status
+        2, ``second`` also where the frame has one feature), position (N, 2) with the sub-pixel refinement (-1 unless the status
+        is 0)."""
+        if self._h is None:
+            raise nat.NativeError('Matcher: push a frame before matching the map')
+        if self._map is not None and self._map_on is not self._h:
+            self._upload_map()
+        n = C.c_int32()
+        p = self.params._native()
+        nat.check(self._lib.ps_feat_match_map_global(self._h, int(ratio[0]), int(ratio[1]), C.byref(p), C.byref(n)))
+        self.num_map_matched = n.value
+        N = self._map[0].shape[0]
+        feature, status, cost, second = (np.zeros(N, dtype=np.int32) for _ in range(4))
+        uv = np.zeros((N, 2))
+        if N:
+            nat.check(self._lib.ps_feat_read_map_matches(self._h, N, nat.i32p(feature), nat.i32p(status), nat.i32p(cost), nat.f64p(uv)))
+            nat.check(self._lib.ps_feat_read_map_second(self._h, N, nat.i32p(second)))
+        return feature, status, cost, second, uv
 
     @property
     def feature_passes(self):

@@ -1,4 +1,4 @@
-"""Monocular tracking against a map: ``track_frame`` and ``SparseMonoPipeline``.
+"""Monocular tracking against a map: ``track_frame``, ``relocalise_frame`` and ``SparseMonoPipeline``.
 
 The reference has no counterpart (it has no monocular camera).  Both are compositions of pieces that run on the device and are
 pinned one by one: the matcher's matching by projection (``Matcher.setMap`` / ``matchMap``), the
@@ -8,6 +8,10 @@ flow match, ``twoview.bootstrap``, ``pnp.register_frame``, ``triangulate_tables`
 ``track_frame`` registers one image against given landmarks: every landmark is projected with the pose prior, matched to the
 image's features inside a small window around its projection -- every feature goes to one landmark only -- and P3P RANSAC over
 the matched pairs gives the pose.
+
+``relocalise_frame`` registers one image against given landmarks without a pose prior: every landmark is compared with every feature
+of the image (``Matcher.matchMapGlobal``, step 9: best against second-best cost), P3P RANSAC over the unambiguous pairs gives a pose,
+and one guided pass -- ``track_frame``'s match and RANSAC with that pose as prior -- widens the inlier set.
 
 ``SparseMonoPipeline.track(image)`` is the whole chain.  The first frame is the reference keyframe; every further frame is
 flow-matched to it until ``bootstrap`` succeeds (a frame on which it does not has the pose ``None``), which makes that frame the
@@ -21,7 +25,11 @@ after which landmarks behind one of their cameras are dropped.
 
 The map lives on the host as arrays -- ``points_w`` (L, 3), ``descriptors`` (L, 32), ``alive`` (L,) and the observation table
 ``obs_kf`` / ``obs_lm`` / ``obs_uv`` -- and is uploaded to the matcher when the landmarks tracked against change.  Its scale is
-that of the initialisation; nothing corrects its drift (no loop closure, no scale prior: DESIGN.md section 7, limits)."""
+that of the initialisation; nothing corrects its drift (no loop closure, no scale prior: DESIGN.md section 7, limits).
+
+Tracking loss (``relocalise``): a frame on which ``register_frame`` raises ValueError is relocalised against all live landmarks.
+Where that fails too the frame's pose is ``None`` and the pipeline is ``lost``: every further frame is relocalised until one
+succeeds (its index joins ``relocalised``), after which tracking goes on as before."""
 import numpy as np
 
 from pyslam_amd.liegroups import SE3
@@ -31,7 +39,7 @@ from pyslam_amd.pipelines.matcher import Matcher, Matcher_parameters
 from pyslam_amd.pipelines.pnp import PnPRANSAC, register_frame, _pts3
 from pyslam_amd.pipelines.twoview import EssentialRANSAC, bootstrap
 
-__all__ = ['track_frame', 'SparseMonoPipeline', 'SparseMonoKeyframe', 'window_tables']
+__all__ = ['track_frame', 'relocalise_frame', 'SparseMonoPipeline', 'SparseMonoKeyframe', 'window_tables']
 
 
 def _set_map_if_changed(matcher, pts, desc):
@@ -66,6 +74,44 @@ def track_frame(camera, matcher, image, points_w, descriptors, T_prior, radius=1
     search window in pixels (doubled once when fewer than ``ransac.min_inliers`` landmarks match), ``seed`` / ``ransac`` as in
     ``register_frame``.  ValueError on an empty map and where ``register_frame`` raises it."""
     return _track(camera, matcher, image, points_w, descriptors, T_prior, radius, seed, ransac)[:3]
+
+
+def _relocalise(camera, matcher, image, points_w, descriptors, ratio, radius, seed, ransac):
+    if np.asarray(points_w).size == 0:
+        raise ValueError('relocalise_frame: the map is empty')
+    pts = _pts3(points_w, 'points_w')
+    desc = np.ascontiguousarray(np.asarray(descriptors, dtype=np.uint8).reshape(-1, 32))
+    if desc.shape[0] != pts.shape[0]:
+        raise ValueError('relocalise_frame: {} landmarks and {} descriptors'.format(pts.shape[0], desc.shape[0]))
+    rs = ransac if ransac is not None else PnPRANSAC(camera)
+    matcher.pushBack(image)
+    _set_map_if_changed(matcher, pts, desc)
+    feature, status, _, _, uv = matcher.matchMapGlobal(ratio)
+    idx = np.nonzero(status == 0)[0]
+    T_cw, inl = register_frame(camera, pts[idx], uv[idx], seed=seed, ransac=rs)
+    keep = idx[inl]
+    first = T_cw, keep, uv[keep], feature[keep]
+    # the guided pass: matching by projection with the pose just found
+    feature, status, _, uv = matcher.matchMap(T_cw, camera, int(radius))
+    idx = np.nonzero(status == 0)[0]
+    try:
+        T_cw, inl = register_frame(camera, pts[idx], uv[idx], seed=None if seed is None else seed + 1, ransac=rs)
+    except ValueError:
+        return first
+    if len(inl) < first[1].shape[0]:
+        return first
+    keep = idx[inl]
+    return T_cw, keep, uv[keep], feature[keep]
+
+
+def relocalise_frame(camera, matcher, image, points_w, descriptors, ratio=(4, 5), radius=12, seed=None, ransac=None):
+    """One monocular image registered against landmarks without a pose prior -> ``(T_cw: SE3, landmark_indices, obs)`` as
+    ``track_frame`` returns them.  Two passes: every landmark against every feature of the image (``Matcher.matchMapGlobal`` with
+    ``ratio``) and ``register_frame`` over the status-0 pairs with ``seed``; then ``matchMap`` with the pose just found and
+    ``radius``, and ``register_frame`` over its status-0 pairs (with ``seed + 1`` when a seed was given).  The second pass's result
+    is returned unless it raises ValueError or has fewer inliers than the first, whose result is returned then.  ValueError on an
+    empty map and where the first ``register_frame`` raises it."""
+    return _relocalise(camera, matcher, image, points_w, descriptors, ratio, radius, seed, ransac)[:3]
 
 
 def window_tables(camera, poses, held, points, obs_kf, obs_lm, obs_uv, loss=None):
@@ -169,6 +215,14 @@ class SparseMonoPipeline:
         that went in and the ones that came back"""
         self.landmark_counts = []
         """Number of live landmarks after every keyframe"""
+        self.relocalise = True
+        """Relocalise a frame that cannot be tracked against all live landmarks (False: its ValueError propagates)"""
+        self.reloc_ratio = (4, 5)
+        """(num, den) of the second-best ratio test of the relocalisation's matching without a prior"""
+        self.lost = False
+        """The last frame could be neither tracked nor relocalised"""
+        self.relocalised = []
+        """Indices into ``T_c_w`` of the frames whose pose comes from a relocalisation"""
 
     def set_mode(self, mode):
         """Set the localization mode to ['map'|'track']"""
@@ -246,10 +300,27 @@ class SparseMonoPipeline:
         return uv, desc
 
     def _track(self, image):
-        T_prior = next(T for T in reversed(self.T_c_w) if T is not None)
-        local = self.local_landmarks()
-        T_cw, keep, obs, feature = _track(self.camera, self.matcher, image, self.points_w[local], self.descriptors[local], T_prior,
-                                          self.search_radius, None, self.ransac)
+        tracked = None
+        if not self.lost:
+            T_prior = next(T for T in reversed(self.T_c_w) if T is not None)
+            local = self.local_landmarks()
+            try:
+                tracked = _track(self.camera, self.matcher, image, self.points_w[local], self.descriptors[local], T_prior,
+                                 self.search_radius, None, self.ransac)
+            except ValueError:
+                if not self.relocalise:
+                    raise
+        if tracked is None:                                    # lost, now or before: against every live landmark, no prior
+            local = np.nonzero(self.alive)[0]
+            try:
+                tracked = _relocalise(self.camera, self.matcher, image, self.points_w[local], self.descriptors[local],
+                                      self.reloc_ratio, self.search_radius, None, self.ransac)
+            except ValueError:
+                self.lost = True
+                return None
+            self.lost = False
+            self.relocalised.append(len(self.T_c_w))
+        T_cw, keep, obs, feature = tracked
         lm = local[keep]
         active = self.keyframes[-1]
         T_rel = T_cw.as_matrix() @ np.linalg.inv(active.T_c_w.as_matrix())
