@@ -498,6 +498,14 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
                               workgroups of the pose pass; every other block is stored by the pair kernel.  Live on a handle with the
                               untiled pipelined pair kernel ("schur_pipeline"), SE(3) poses and no landmark shard (ps_get_option tells);
                               every other handle, and 0, keep the fill over all of [S | g | cost | status].  Speed only
+     "setup_ride"         [1; 0 / 1] the block-Jacobi factors that head the fused CG's set-up (L_i^-1, g^, the zeroed CG vectors, the coarse
+                              basis blocks) are formed by the waves of the Schur pair launch that finalise the diagonal blocks, and the
+                              kernel of their own is launched only for further set-ups on the same linearisation.  Live on a handle
+                              whose finalisation is in the pair launch (untiled pipelined pair kernel, SE(3) poses, no landmark observed
+                              twice from one pose), without pose-to-pose factors or host rows, that is no landmark shard and whose
+                              reduced system the fused CG takes (not the direct solve, the explicit or the classic PCG); ps_get_option
+                              tells.  Every other handle, and 0, launch the factor kernel in every set-up.  Speed only, same bits.
+                              Handled ahead of the option table, as "expect_next" and "solve_horizon" are
      "schur_pipeline"     [1; 0 / 1] the Schur pair kernel with two chunks per wave in flight (k_schur_pairs_db); 0: k_schur_pairs
      "lm_packed" [1; 0 / 1], "band_part" [1; 0 / 1], "band_part_chunk" [0 auto; 0 .. 4096 nodes], "sync_refactor" [1; 0 / 1],
      "hold_across_steps" [1; 0 / 1]: round-5 kernels and schedules against their predecessors (DESIGN.md sections 0 and 3)
@@ -515,7 +523,10 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
                               ablation); the product build accepts 0 and refuses every other value */
 int ps_set_option(ps_problem* h, const char* name, double value);
 /* What an option comes to on this handle.  "lin_zero_list": 1 if linearisations zero by the list, 0 if they keep the fill;
-   "lin_zero_launches" / "lin_fills": linearisations so far that did the one / the other. */
+   "lin_zero_launches" / "lin_fills": linearisations so far that did the one / the other.
+   "setup_ride": 1 if the pair launch also forms the block-Jacobi factors on this handle, else 0; "factors_ridden": linearisations
+   so far that did; "factor_launches": set-ups of the fused CG that launched the factor kernel themselves; "factor_plan_mismatches":
+   those among them that found ridden factors made for another set-up plan (lagged / exact, coarse buffer) than their own. */
 int ps_get_option(ps_problem* h, const char* name, double* value);
 
 /* hipEvent stage timers on the handle's stream (the reference has no tracing). */

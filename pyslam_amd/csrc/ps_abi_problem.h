@@ -971,7 +971,7 @@ int ps_set_host_rows(ps_problem* h, const double* rows, int64_t num, double cost
         HIP_OK(hipStreamSynchronize(h->stream));
     }
     h->host_cost = cost;
-    h->prelin_valid = false;                                 // (a linearisation enqueued ahead would lack these rows)
+    h->prelin_valid = h->ride_valid = false;                 // (a linearisation enqueued ahead would lack these rows)
     h->last_cost = h->prev_cost = -1.0;                      // the core's own costs miss the caller's blocks: no cost history
     return 0;
 }

@@ -80,7 +80,7 @@ int ps_shard_pack(ps_problem* h) {
 
 int ps_shard_unpack(ps_problem* h) {
     if (!h) return fail("null argument");
-    h->prelin_valid = h->prelm_valid = false;            // S and g are overwritten with the all-reduced system
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;            // S and g are overwritten with the all-reduced system
     if (ensure_shard_pack(h)) return -1;
     const long ntail = (long)h->nr * h->D + 2;
     const int nb = (int)std::min<long>(4096, cdiv(h->pack_count, 256));
@@ -142,7 +142,7 @@ int ps_step_norm2(ps_problem* h, double* norm2) {
 
 int ps_apply_update(ps_problem* h, double step) {
     if (!h) return fail("null argument");
-    h->prelin_valid = h->prelm_valid = false;
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     h->last_cost = h->prev_cost = -1.0;                     // parameters move without a cost: history unknown from here
     return apply_update(h, step);
 }
@@ -163,7 +163,7 @@ int ps_snapshot_params(ps_problem* h) {
 static int restore_params_by_exchange(ps_problem* h) {
     if (!h->snap_valid) return fail("ps_solve: no snapshot to restore");
     h->params_moved_since_lin = true;
-    h->prelin_valid = h->prelm_valid = false;
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     h->last_cost = h->snap_cost; h->prev_cost = -1.0;
     std::swap(h->poses, h->poses_snap);
     std::swap(h->points, h->points_snap);
@@ -175,7 +175,7 @@ int ps_restore_params(ps_problem* h) {
     if (!h) return fail("null argument");
     if (!h->snap_valid) return fail("ps_restore_params: no snapshot (none taken, or ps_solve has consumed it)");
     h->params_moved_since_lin = true;
-    h->prelin_valid = h->prelm_valid = false;
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     h->last_cost = h->snap_cost; h->prev_cost = -1.0;       // the snapshot's own cost (if it was known), no step history
     const size_t n1 = (size_t)h->P * h->PW, n2 = (size_t)h->L * 3;
     if (n1 + n2)
@@ -195,7 +195,7 @@ int ps_get_params(ps_problem* h, double* poses, double* points) {
 int ps_set_params(ps_problem* h, const double* poses, const double* points) {
     if (!h) return fail("null argument");
     h->params_moved_since_lin = true;
-    h->prelin_valid = h->prelm_valid = false;
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     h->last_cost = h->prev_cost = -1.0;
     if (poses && h->P) HIP_OK(hipMemcpyAsync(h->poses, poses, (size_t)h->P * h->PW * sizeof(double), hipMemcpyDefault, h->stream));
     if (points && h->L) HIP_OK(hipMemcpyAsync(h->points, points, (size_t)h->L * 3 * sizeof(double), hipMemcpyDefault, h->stream));
@@ -286,7 +286,7 @@ static int exchange_reduced_system(ps_problem* h) {
         { StageTimer tpk(h, PS_ST_PACK); if (ps_shard_unpack(h)) return -1; }
         return 0;
     }
-    h->prelin_valid = h->prelm_valid = false;            // (as ps_shard_unpack: S and g are overwritten with the summed system)
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;            // (as ps_shard_unpack: S and g are overwritten with the summed system)
     const long T = 3, ntail = (long)h->nr * h->D + 2;
     const unsigned nb1 = (unsigned)std::min<long>(2048, cdiv(h->seg_maxlen, 256)), nb2 = (unsigned)std::min<long>(4096, cdiv(h->seg_ndst + T, 256));
     {
@@ -701,7 +701,7 @@ int ps_solve_lm(ps_problem* h, const ps_lm_options* o, double pcg_tol, int pcg_m
 int ps_motion_only_solve(ps_problem* h, const ps_solve_options* o, double* cost_history, int32_t cap, int32_t* n_history,
                          int32_t* iterations, double* last_dx_norm, double* pose12_out) {
     if (!h || !o || !cost_history || !n_history) return fail("null argument");
-    h->prelin_valid = h->prelm_valid = false;
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     const bool eligible = h->mo_fused && !h->hybrid && h->nv == 0 && h->F == 0 && h->nr == 1 && h->P == 1 && h->D == 6 && h->N == h->Np &&
                           h->pcg_variant == 1 && h->max_pose_obs <= 2048;
     const int need = o->max_iters + 2;                        // the start cost + at most max_iters + 1 iterations
@@ -744,7 +744,7 @@ int ps_covariance_begin(ps_problem* h) {
     if (!h) return fail("null argument");
     cov_release(h);
     ++h->cov_epoch;
-    h->prelin_valid = h->prelm_valid = false;
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     if (linearize(h, 0.0)) return -1;
     if (h->nr > 0 && h->pcg_variant == 1 && !use_direct(h) && !h->coarse_built && build_coarse(h)) return -1;
     if (h->nr > 0 && h->pcg_variant == 1 && !use_direct(h) && !h->cg_explicit) {
@@ -909,7 +909,14 @@ int ps_set_option(ps_problem* h, const char* name, double value) {
     // what a caller's own loop says about its next call leaves what was computed ahead in place
     if (!std::strcmp(name, "expect_next")) { h->expect_next = value != 0 && !h->hybrid; return 0; }      // (hybrid: see ps_problem_create_hybrid)
     if (!std::strcmp(name, "solve_horizon")) { h->solve_horizon = value < 0 ? -1 : (int)std::min(value, 1e6); return 0; }
-    h->prelin_valid = h->prelm_valid = false;
+    // the block-Jacobi factor of the fused CG's set-up rides in the pair launch (csrc/ps_core.hip: setup_ride); 0: a launch of its own
+    if (!std::strcmp(name, "setup_ride")) {
+        h->setup_ride = value != 0 ? 1 : 0;
+        h->prelin_valid = h->prelm_valid = false;
+        relook_launch_gates(h);
+        return 0;
+    }
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     const char* refusal = nullptr;
     const int fx = ps_option_apply(*h, name, value, &refusal);
     if (fx == PS_OPT_UNKNOWN) return fail(std::string("unknown option: ") + name);
@@ -930,6 +937,10 @@ int ps_get_option(ps_problem* h, const char* name, double* value) {
     if (n == "lin_zero_list") *value = h->lin_zero_gate ? 1.0 : 0.0;
     else if (n == "lin_fills") *value = (double)h->lin_fills;
     else if (n == "lin_zero_launches") *value = (double)h->lin_zero_launches;
+    else if (n == "setup_ride") *value = h->ride_gate ? 1.0 : 0.0;
+    else if (n == "factor_launches") *value = (double)h->bjf_launches;
+    else if (n == "factors_ridden") *value = (double)h->bjf_ridden;
+    else if (n == "factor_plan_mismatches") *value = (double)h->bjf_mismatches;
     else return fail("ps_get_option: no read-back for option: " + n);
     return 0;
 }
@@ -942,7 +953,7 @@ int ps_get_option(ps_problem* h, const char* name, double* value) {
 // (Problem.solve; bench.py's cold solves).
 int ps_reset_solver_state(ps_problem* h) {
     if (!h) return fail("null argument");
-    h->prelin_valid = h->prelm_valid = false;
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     if (!h->solver_touched) {                               // nothing linearised since creation / the last reset: only the history
         static_cast<PsCostHistory&>(*h) = PsCostHistory{};
         return 0;

@@ -52,7 +52,7 @@ int ps_triangulate(ps_problem* h, int64_t n, const int32_t* vids, int refine_ite
                            h->lobs, h->poses, h->points, h->ogroups, wl, refine_iters, cos_min, write_back ? 1 : 0, d_pts, d_status);
     if (write_back) {                                           // the parameters moved: as ps_set_params
         h->params_moved_since_lin = true;
-        h->prelin_valid = h->prelm_valid = false;
+        h->prelin_valid = h->prelm_valid = h->ride_valid = false;
         h->last_cost = h->prev_cost = -1.0;
     }
     // without a list the kernel ran in slot order: back to the caller's vid order on the host

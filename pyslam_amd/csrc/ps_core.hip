@@ -292,6 +292,17 @@ struct ps_problem : PsOptions, PsCostHistory, PsCarried {
     bool has_extra_pairs = false;   // created with extra pattern blocks: a landmark shard (pyslam_amd/distributed.py)
     bool lin_zero_gate = false;     // the option is on and this handle is eligible (relook_launch_gates)
     long lin_fills = 0, lin_zero_launches = 0;   // linearisations that ran the fill / that zeroed by the list
+    // option "setup_ride" (ps_set_option, ahead of the table): the block-Jacobi factor kernel that heads the fused CG's set-up
+    // rides in a launch that is there anyway -- the factor of a pose is formed by the wave of the pair launch that has just finalised
+    // its diagonal block (ride_gate: the handle is eligible, relook_launch_gates; ride_valid: Linv, g^, the zeroed CG vectors and the
+    // basis blocks in ride_basis belong to the S and g on the device -- set by linearize(), consumed by the first set-up, cleared
+    // by whatever changes S, g, the parameters or an option in between; ride_lagged / ride_use / ride_basis: the set-up plan the
+    // ridden factor was run for, cg_setup_plan).
+    int setup_ride = 1;
+    bool ride_gate = false, ride_valid = false, ride_lagged = false;
+    int ride_use = 0;
+    double* ride_basis = nullptr;
+    long bjf_launches = 0, bjf_ridden = 0, bjf_mismatches = 0;   // factor launches of the fused CG's set-up / linearisations that rode the factor / ridden for another plan than the set-up's
     std::vector<int32_t> h_row_ptr, h_col_idx;
     std::vector<int32_t> h_vid_of_slot;   // landmarks are stored in locality order; external order is vid
     // pcg
@@ -643,6 +654,14 @@ inline void cov_release(ps_problem* h) {
 inline void relook_launch_gates(ps_problem* h) {
     const bool shard = (h->nccl_allreduce && h->nccl_comm) || h->seg_allgather || h->shard_pack || h->has_extra_pairs;
     h->lin_zero_gate = h->lin_zero_list && h->zero_slots && !h->Spart && h->schur_pipeline && h->npitems > 0 && h->D == 6 && !shard;
+    // "setup_ride": the finalisation is in the pair launch (fin_in_pairs of linearize(): untiled, pipelined, SE(3), no task writes a
+    // diagonal block), nothing adds into the diagonal blocks behind that launch (pose-to-pose factors, host rows) and the system is
+    // not exchanged and summed over ranks afterwards; and the fused CG takes the system -- not k_direct_solve, the classic PCG or
+    // (known once the coarse level is built: linearize() looks again) the explicit PCG.
+    h->ride_gate = h->setup_ride && !h->Spart && h->schur_pipeline && h->npitems > 0 && h->npair_items > 0 && !h->has_diag_tasks &&
+                   h->D == 6 && h->F == 0 && h->FH == 0 && !shard && h->pcg_variant == 1 && h->nr > 0 &&
+                   h->nr * h->D > h->direct_max && !(h->coarse_built && h->cg_explicit);
+    h->ride_valid = false;
 }
 
 #include "ps_host_cg.h"

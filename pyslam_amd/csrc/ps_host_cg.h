@@ -47,6 +47,7 @@ void drain_timers(ps_problem* h) {      // call after a stream synchronisation
 int side_kick(ps_problem* h);
 int ldi_side_kick(ps_problem* h);
 int linearize(ps_problem* h, double lambda, bool allow_prelm = false);
+bool use_direct(const ps_problem* h);
 
 // stage timers whose end event has completed (a speculative linearisation enqueued behind the iteration's end is still running
 // when the host leaves wait_published: its events stay pending)
@@ -701,11 +702,34 @@ int xcg_coarse_inverse(ps_problem* h, hipStream_t st, int buf, int32_t* stat) {
     return 0;
 }
 
+// What a full set-up of the fused CG will do, from the handle's state alone: the lagged three-launch path (everything coarse
+// from the previous iteration: buffer `use`, the current basis goes to the other one) or the exact one, and where the
+// block-Jacobi factor kernel writes the basis blocks.  cg_fused_setup follows it; linearize() asks for it ahead of the pair
+// launch whose finalising waves run that factor ("setup_ride") -- lci_next as the side stream's pending kick will leave it.
+struct CgSetupPlan { bool lagged; int use; double* basis_out; };
+inline CgSetupPlan cg_setup_plan(const ps_problem* h, bool allow_lag, int lci_next) {
+    CgSetupPlan p{};
+    p.lagged = h->G && h->lagx_ok && h->lagx && allow_lag && h->coarse_lag && lci_next >= 0;
+    if (p.lagged) { p.use = lci_next; p.basis_out = h->Bmat2[lci_next ^ 1]; }
+    else { p.use = h->lagx_ok ? h->lci_cur : 0; p.basis_out = h->G ? h->Bmat2[p.use] : nullptr; }
+    return p;
+}
+
+// the block-Jacobi factors of this S and g are in place for `plan` (the pair launch's finalising waves ran them): consumed here,
+// so every later set-up on the same linearisation -- a second staged solve, a restart, a repeated solve -- launches the kernel
+inline bool ride_consume(ps_problem* h, const CgSetupPlan& plan) {
+    if (!h->ride_valid) return false;
+    h->ride_valid = false;
+    if (plan.lagged == h->ride_lagged && plan.use == h->ride_use && plan.basis_out == h->ride_basis) return true;
+    ++h->bjf_mismatches;                                    // (the same result by the kernel's own launch, one launch later)
+    return false;
+}
+
 template <int D>
 int cg_fused_setup(ps_problem* h, int max_iters, bool allow_lag = false, bool rhs_only = false) {
     const int nr = h->nr, cap = h->hist_cap;
     if (max_iters + 2 > cap) return fail("pcg max_iters exceeds the history buffer (4096)");
-    if (!h->coarse_built && build_coarse(h)) return -1;
+    if (!h->coarse_built) { h->ride_valid = false; if (build_coarse(h)) return -1; }      // (a rebuilt level: other buffers, another plan)
     h->cg_max_launches = max_iters + 2;
     h->cp_recovered = false;
     h->cg_two_level_reduce = h->nr_aug > 2048 || h->cg_split;
@@ -730,15 +754,19 @@ int cg_fused_setup(ps_problem* h, int max_iters, bool allow_lag = false, bool rh
         HIP_OK(hipStreamWaitEvent(h->stream, h->ev_chol, 0));
         h->side_pending = false;
     }
-    if (G && h->lagx_ok && h->lagx && allow_lag && h->coarse_lag && h->lci_next >= 0) {
+    const CgSetupPlan plan = cg_setup_plan(h, allow_lag, h->lci_next);
+    const bool ridden = ride_consume(h, plan);              // ("setup_ride": the pair launch's finalising waves ran the factor)
+    if (!ridden) ++h->bjf_launches;
+    if (plan.lagged) {
         // ---- three launches: everything coarse (basis, factor, X = P L_c^-T) is the previous iteration's
         const int ncb = h->ncb, nc = h->nc;
-        const int use = h->lci_next, nb = use ^ 1;
+        const int use = plan.use, nb = use ^ 1;
         h->lci_cur = use;
         h->Bmat = h->Bmat2[use];
-        hipLaunchKernelGGL(k_block_jacobi_factor<D>, dim3(cdiv(nr, 4)), dim3(256), 0, h->stream, nr, h->diag_slot,
-                           h->S, h->Linv, h->status, h->g, h->cg_r[0], h->cg_w[0], h->cg_s[0], h->cg_p, h->cg_xh,
-                           h->poses, h->pose_of_rid, h->coarse_basis, h->Bmat2[nb], h->bgv);
+        if (!ridden)
+            hipLaunchKernelGGL(k_block_jacobi_factor<D>, dim3(cdiv(nr, 4)), dim3(256), 0, h->stream, nr, h->diag_slot,
+                               h->S, h->Linv, h->status, h->g, h->cg_r[0], h->cg_w[0], h->cg_s[0], h->cg_p, h->cg_xh,
+                               h->poses, h->pose_of_rid, h->coarse_basis, plan.basis_out, h->bgv);
         if (!h->rows_attr_set) {
             if (ensure_dynamic_lds((const void*)k_rows_setup<D>, (size_t)(h->rows_lds))) return -1;
             h->rows_attr_set = true;
@@ -759,11 +787,12 @@ int cg_fused_setup(ps_problem* h, int max_iters, bool allow_lag = false, bool rh
     }
     h->last_setup_lagx = false;
     h->side_todo = false;                                   // the exact path below recomputes everything coarse
-    if (G) h->Bmat = h->Bmat2[h->lagx_ok ? h->lci_cur : 0];
+    if (G) h->Bmat = plan.basis_out;
     // block-Jacobi factors + the start vectors of the scaled system (r = Linv g, w = s = p = x = 0)
-    hipLaunchKernelGGL(k_block_jacobi_factor<D>, dim3(cdiv(nr, 4)), dim3(256), 0, h->stream, nr, h->diag_slot,
-                       h->S, h->Linv, h->status, h->g, h->cg_r[0], h->cg_w[0], h->cg_s[0], h->cg_p, h->cg_xh,
-                       h->poses, h->pose_of_rid, h->coarse_basis, G ? h->Bmat : (double*)nullptr, h->bgv);
+    if (!ridden)
+        hipLaunchKernelGGL(k_block_jacobi_factor<D>, dim3(cdiv(nr, 4)), dim3(256), 0, h->stream, nr, h->diag_slot,
+                           h->S, h->Linv, h->status, h->g, h->cg_r[0], h->cg_w[0], h->cg_s[0], h->cg_p, h->cg_xh,
+                           h->poses, h->pose_of_rid, h->coarse_basis, plan.basis_out, h->bgv);
     hipLaunchKernelGGL(k_scale_blocks<D>, dim3(h->nnzb), dim3(64), 0, h->stream, nr, h->row_ptr, h->col_idx,
                        h->brow_of, h->Linv, h->S, h->aug_slot, h->Saug, G ? h->Bmat : (const double*)nullptr, h->SB);
     if (G) {
@@ -1038,6 +1067,32 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
     // ran ahead in the previous tail reports through the pinned words -- lin_lmfail_tag --, its status word is cleared either way.)
     const bool zero_by_list = h->lin_zero_gate;
     const bool lm_here = h->nv > 0 && !lm_done;
+    // option "setup_ride": the finalising waves of the pair launch also run the block-Jacobi factor of the fused CG's set-up, for
+    // the plan that set-up will find (whole-iteration calls may lag; the side stream's kick at the end of this function moves
+    // lci_next to its buffer first).  Only where the fused CG takes the system: the coarse level says so, so it is built here.
+    BjFactorOut ride{};
+    h->ride_valid = false;
+    if (h->ride_gate && h->nr > 0 && h->pcg_variant == 1 && !use_direct(h)) {
+        if (!h->coarse_built && build_coarse(h)) return -1;
+        if (h->cg_explicit) h->ride_gate = false;           // (known only now: the read-back says 0 from here on)
+        else {
+            const int lci = (h->side_todo && h->side_ready) ? h->side_buf : h->lci_next;
+            const CgSetupPlan plan = cg_setup_plan(h, allow_prelm, lci);
+            // The next set-up may be asked for the other plan (ps_linearize plans exact; ps_gn_solve_finish behind it may lag), and
+            // then runs the kernel itself -- but a basis that is still to be read must be there for it: the previous iteration's,
+            // which a lagged set-up takes beside that iteration's X and factor (buffer lci), and the one the side stream's next
+            // operator is still to be formed from (side_buf while side_todo: cg_side_kick reads it without an event).
+            // Only an exact plan (basis to lci_cur) or a kick that is not ready can point there: such a linearisation does not ride.
+            const CgSetupPlan lag = cg_setup_plan(h, true, lci);
+            const bool held = plan.basis_out && ((lag.lagged && plan.basis_out == h->Bmat2[lag.use]) ||
+                                                 (h->side_todo && plan.basis_out == h->Bmat2[h->side_buf]));
+            if (!held) {
+                ride = BjFactorOut{h->Linv, h->status, h->cg_r[0], h->cg_w[0], h->cg_s[0], h->cg_p, h->cg_xh, h->poses, h->pose_of_rid,
+                                   h->coarse_basis, plan.basis_out, h->bgv};
+                h->ride_lagged = plan.lagged; h->ride_use = plan.use; h->ride_basis = plan.basis_out;
+            }
+        }
+    }
     if (!zero_by_list) {
         HIP_OK(hipMemsetAsync(h->red, 0, h->red_count * sizeof(double) + ST_NWORDS * sizeof(int32_t), h->stream));   // [S | g | cost | status]
         ++h->lin_fills;
@@ -1108,9 +1163,13 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
 #else
                 auto k = k_schur_pairs_db<0>;                   // (the ablation instantiations exist in the measurement build only)
 #endif
-                hipLaunchKernelGGL(k, dim3(nblk + (fin_in_pairs ? cdiv(h->nr, 4) : 0)), dim3(256), lds, h->stream, h->pair_per_xcd,
+                // (finalising workgroups: behind the pair items; in front of them when they also factor -- ps_k_schur2.h)
+                const int nfin = fin_in_pairs ? cdiv(h->nr, 4) : 0;
+                const int lead = (fin_in_pairs && ride.Linv) ? (nfin + 7) / 8 * 8 : 0;
+                hipLaunchKernelGGL(k, dim3(nblk + (lead ? lead : nfin)), dim3(256), lds, h->stream, h->pair_per_xcd,
                                    h->pair_xitems, h->pairs, h->Z, h->S, h->Spart, from, to, nblk, fin_in_pairs ? h->nr : 0,
-                                   h->pitem_ptr, h->ppartial, h->diag_slot, lambda, h->g);
+                                   h->pitem_ptr, h->ppartial, h->diag_slot, lambda, h->g, fin_in_pairs ? ride : BjFactorOut{}, lead);
+                if (fin_in_pairs && ride.Linv) { h->ride_valid = true; ++h->bjf_ridden; }
             }
         };
         launch_pairs(8 * (halfp / 4), lds_pad, 0, halfp);
@@ -1255,7 +1314,7 @@ int step_norm(ps_problem* h) {
 
 int apply_update(ps_problem* h, double step, const int32_t* gate = nullptr, bool with_norm = false, long long* hearly = nullptr, long long eseq = 0) {
     h->params_moved_since_lin = true;
-    h->prelin_valid = h->prelm_valid = false;   // the parameters move: a linearisation enqueued ahead is of the old point (set again by
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;   // the parameters move: a linearisation enqueued ahead is of the old point (set again by
                                         // gn_iteration_impl AFTER its tail, for the speculative one enqueued behind that tail)
     StageTimer t(h, PS_ST_UPDATE);
     if (h->nr > 0) {
@@ -1307,7 +1366,7 @@ int lm_cost_enqueue(ps_problem* h, double lambda, const int32_t* gate) {
 // the cost at the current parameters (all blocks) into scalars[scalar_slot], by the landmark pass: the next linearisation at
 // this point and this lambda finds its landmark pass done
 int lm_cost_pass(ps_problem* h, double lambda, int scalar_slot) {
-    h->prelin_valid = false;                                 // (Z, C^-1, c are rewritten -- with the same values if nothing moved)
+    h->prelin_valid = h->ride_valid = false;                 // (Z, C^-1, c are rewritten -- with the same values if nothing moved)
     const int n = lm_cost_enqueue(h, lambda, nullptr);
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, h->stream, n, h->cost_partials, h->scalars + scalar_slot);
     h->prelm_pending = false; h->prelm_valid = true;
@@ -1318,7 +1377,7 @@ int lm_cost_pass(ps_problem* h, double lambda, int scalar_slot) {
 // status words) makes every kernel a no-op until the CG has flagged convergence.
 int gn_tail(ps_problem* h, int linesearch, const int32_t* gate, bool publish = false) {
     h->params_moved_since_lin = true;
-    h->prelin_valid = h->prelm_valid = false;   // (as apply_update: every tail moves the parameters)
+    h->prelin_valid = h->prelm_valid = h->ride_valid = false;   // (as apply_update: every tail moves the parameters)
     h->prelm_pending = false;
     // line-search order (cost AFTER the step): back-substitution, landmark update and pose retraction
     // are one launch when the problem has landmarks (then D == 6)

@@ -13,10 +13,9 @@
 // previous launch, so the only global dependency is the launch boundary itself.
 // The k = -1 launch (alpha = beta = 0) initialises w = S^ g^ and the first partials.
 // ---------------------------------------------------------------------------
-// One WAVE per pose (4 poses per workgroup), lane (r, c) of the D x D block: the factorisation is a right-looking
-// Cholesky with one column scaled and one rank-1 update applied per step by all lanes at once, the inverse six
-// independent forward substitutions -- a few hundred instructions per wave instead of the ~3 000 of one thread
-// working through the whole block (11 us -> 4 us at C3: this kernel heads the critical path of every reduced solve).
+// One WAVE per pose (4 poses per workgroup): block_jacobi_factor_wave (ps_k_bjfactor.h) -- a few hundred instructions per wave
+// instead of the ~3 000 of one thread working through the whole block (11 us -> 4 us at C3).  This kernel heads the reduced
+// solve's set-up wherever the finalising waves of the pair launch have not run the same function already ("setup_ride").
 template <int D>
 __global__ __launch_bounds__(256) void k_block_jacobi_factor(
     int nr, const int32_t* __restrict__ diag_slot, const double* __restrict__ S,
@@ -24,81 +23,20 @@ __global__ __launch_bounds__(256) void k_block_jacobi_factor(
     // fused CG only (g != NULL): also the start vectors of the scaled system, r = Linv g, w = s = p = x = 0
     const double* __restrict__ g, double* __restrict__ r0, double* __restrict__ w0, double* __restrict__ s0,
     double* __restrict__ p0, double* __restrict__ x0,
-    // two-level CG (Bmat != NULL): the coarse basis block of this pose, B_i = L_i^T Ad(T_i) (basis 1: a
-    // coarse unknown is a BODY-frame twist eta, the fine correction is x_i = Ad(T_i) eta, x^_i = L_i^T x_i)
-    // or the identity (basis 0: hats directly in the scaled coordinates), and bg_i = B_i^T r_i
+    // two-level CG (Bmat != NULL): the coarse basis blocks and bg_i = B_i^T r_i (BjFactorOut)
     const double* __restrict__ poses, const int32_t* __restrict__ pose_of_rid, int basis,
     double* __restrict__ Bmat, double* __restrict__ bg)
 {
     constexpr int DD = D * D;
-    __shared__ double sA[4][DD], sLi[4][DD], sB[4][DD], sR[4][D];
+    __shared__ double sc[4][PS_BJF_SCRATCH(D)];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + wv;
-    if (g && blockIdx.x == 0 && threadIdx.x == 0) { status[ST_PCG_DONE] = 0; status[ST_PCG_ITERS] = 0; }
     if (i >= nr) return;                                    // whole waves
-    const bool act = lane < DD;
-    const int r = act ? lane / D : 0, c = act ? lane % D : 0;
-    double* A = sA[wv];
-    double* Li = sLi[wv];
-    if (act) { A[lane] = S[(size_t)diag_slot[i] * DD + lane]; Li[lane] = 0.0; }
-    __builtin_amdgcn_wave_barrier();
-    bool ok = true;
-    // A = L L^T in place: after step j column j of A (rows >= j) holds L[:, j]
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        const double d = A[j * D + j];
-        ok = ok && (d > 0.0);
-        const double l = sqrt(d);
-        __builtin_amdgcn_wave_barrier();
-        if (act && c == j && r >= j) A[lane] = (r == j) ? l : A[lane] / l;
-        __builtin_amdgcn_wave_barrier();
-        if (act && r > j && c > j) A[lane] -= A[r * D + j] * A[c * D + j];
-        __builtin_amdgcn_wave_barrier();
-    }
-    // L^-1: lane c < D runs the forward substitution of column c
-    if (lane < D) {
-        const int cc = lane;
-        double col[D];
-#pragma unroll
-        for (int rr = 0; rr < D; ++rr) {
-            double v = (rr == cc) ? 1.0 : 0.0;
-#pragma unroll
-            for (int k = 0; k < rr; ++k) v -= (k >= cc) ? A[rr * D + k] * col[k] : 0.0;
-            col[rr] = (rr >= cc) ? v / A[rr * D + rr] : 0.0;
-            Li[rr * D + cc] = col[rr];
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (!ok && lane == 0) atomicAdd(&status[ST_DIAG_FAIL], 1);
-    if (act) Linv[(size_t)i * DD + lane] = Li[lane];
-    if (g && lane < D) {
-        double v = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) v += Li[lane * D + k] * g[(size_t)i * D + k];
-        const size_t o = (size_t)i * D + lane;
-        r0[o] = v; w0[o] = 0.0; s0[o] = 0.0; p0[o] = 0.0; x0[o] = 0.0;
-        sR[wv][lane] = v;
-    }
-    if (!Bmat) return;
-    if (act) {
-        typedef PoseOps<D> G;
-        double v = (r == c) ? 1.0 : 0.0;
-        if (basis == 1) {
-            const double* Tp = poses + G::W * (size_t)pose_of_rid[i];      // (c differs per lane: entries straight from memory)
-            v = 0.0;
-#pragma unroll
-            for (int m2 = 0; m2 < D; ++m2) v += (m2 >= r) ? A[m2 * D + r] * G::adj_mem(Tp, m2, c) : 0.0;     // (L^T Ad)[r][c]
-        }
-        Bmat[(size_t)i * DD + lane] = v;
-        sB[wv][lane] = v;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (g && lane < D) {
-        double v = 0.0;
-#pragma unroll
-        for (int a = 0; a < D; ++a) v += sB[wv][a * D + lane] * sR[wv][a];
-        bg[(size_t)i * D + lane] = v;
-    }
+    double a_in = 0.0;
+    if (lane < DD) a_in = S[(size_t)diag_slot[i] * DD + lane];
+    if (g && lane < D) sc[wv][3 * DD + D + lane] = g[(size_t)i * D + lane];
+    const BjFactorOut o{Linv, status, g ? r0 : nullptr, w0, s0, p0, x0, poses, pose_of_rid, basis, Bmat, bg};
+    block_jacobi_factor_wave<D>(i, lane, a_in, sc[wv], o);
 }
 
 // Sout[out_slot[b]] = Linv_i S_ij Linv_j^T  (one 64-thread workgroup per block; S itself is kept)

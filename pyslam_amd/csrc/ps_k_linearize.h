@@ -353,9 +353,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PS_POSE_WAV
 }
 
 // one wave (64 lanes, 33 active) per reduced pose: chunk partials -> diagonal S block, g
+// (s_new / g_new: what lane < 36 / lane < 6 has just stored, for a caller that goes on with the block -- ps_k_schur2.h)
 PS_DEV void pose_finalize_wave(int rid, int lane, const int32_t* __restrict__ pitem_ptr,
                                const double* __restrict__ partial, const int32_t* __restrict__ diag_slot,
-                               double lambda, double* __restrict__ S, double* __restrict__ g, double* v /* LDS, 33 */)
+                               double lambda, double* __restrict__ S, double* __restrict__ g, double* v /* LDS, 33 */,
+                               double* s_new = nullptr, double* g_new = nullptr)
 {
     if (lane < PS_NPOSE_ACC) {
         double s = 0.0;
@@ -363,15 +365,20 @@ PS_DEV void pose_finalize_wave(int rid, int lane, const int32_t* __restrict__ pi
         v[lane] = s;
     }
     __builtin_amdgcn_wave_barrier();
+    double sn = 0.0, gn = 0.0;
     if (lane < 36) {
         const int r = lane / 6, c = lane % 6;
         const int a = r < c ? r : c, b = r < c ? c : r;
         const int idx = a * 6 - (a * (a - 1)) / 2 + (b - a);   // upper-triangle packed index
         double val = v[idx];
         if (r == c) val += lambda * v[27 + r];
-        S[(size_t)diag_slot[rid] * 36 + lane] += val;
+        const size_t o = (size_t)diag_slot[rid] * 36 + lane;
+        sn = S[o] + val;
+        S[o] = sn;
     }
-    if (lane < 6) g[(size_t)rid * 6 + lane] += v[21 + lane];
+    if (lane < 6) { const size_t o = (size_t)rid * 6 + lane; gn = g[o] + v[21 + lane]; g[o] = gn; }
+    if (s_new) *s_new = sn;
+    if (g_new) *g_new = gn;
 }
 
 __global__ __launch_bounds__(64) void k_pose_finalize(

@@ -117,7 +117,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     // untiled lists have no combine launch to finalize the pose pass in: workgroups beyond the pair items do it here
     // (fin_nr > 0; never when a task writes a diagonal block) -- one launch less on the critical path
     int fin_first_block, int fin_nr, const int32_t* __restrict__ pitem_ptr, const double* __restrict__ ppartial,
-    const int32_t* __restrict__ diag_slot, double lambda, double* __restrict__ g)
+    const int32_t* __restrict__ diag_slot, double lambda, double* __restrict__ g,
+    // option "setup_ride" (ride.Linv != NULL): a finalising wave goes on and factors the diagonal block it has just written --
+    // what k_block_jacobi_factor would do in a launch of its own at the head of the reduced solve's set-up.  Such waves do a
+    // few microseconds of dependent work: in the trailing workgroups that is the kernel's tail, so they are the LEADING fin_lead
+    // workgroups then (a multiple of 8: the pair items keep their XCDs) and run beside the pair work.
+    BjFactorOut ride, int fin_lead)
 {
     constexpr int ablate = ABL;
     __shared__ __attribute__((aligned(16))) double sbuf[2 * 4 * PS_SQ_BUF];      // [buffer][wave][64 rows x 12]
@@ -126,14 +131,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     double* const buf0 = sbuf + wv * PS_SQ_BUF;
     double* const buf1 = buf0 + 4 * PS_SQ_BUF;
     int32_t* const islot = sidx + wv * 256;
-    if ((int)blockIdx.x >= fin_first_block) {
-        const int rid = ((int)blockIdx.x - fin_first_block) * 4 + wv;
-        if (rid < fin_nr) pose_finalize_wave(rid, lane, pitem_ptr, ppartial, diag_slot, lambda, S, g, buf0);
+    const int bid = (int)blockIdx.x - fin_lead;
+    if (bid < 0 || bid >= fin_first_block) {
+        const int rid = (bid < 0 ? (int)blockIdx.x : bid - fin_first_block) * 4 + wv;
+        if (rid < fin_nr) {
+            double sv, gv;
+            pose_finalize_wave(rid, lane, pitem_ptr, ppartial, diag_slot, lambda, S, g, buf0, &sv, &gv);
+            if (ride.Linv) {
+                // (the values are handed over in registers and LDS: the same wave, no trip through memory; the scratch is
+                //  behind the 33 sums of the finalisation in this wave's slice of sbuf)
+                static_assert(64 + PS_BJF_SCRATCH(6) <= PS_SQ_BUF, "the factor's scratch fits the wave's chunk buffer");
+                double* sc = buf0 + 64;
+                if (lane < 6) sc[3 * 36 + 6 + lane] = gv;
+                block_jacobi_factor_wave<6>(rid, lane, sv, sc, ride);
+            }
+        }
         return;
     }
-    const int local = first + (blockIdx.x >> 3) * 4 + wv;
+    const int local = first + (bid >> 3) * 4 + wv;
     if (local >= last) return;
-    const size_t pos = (size_t)(blockIdx.x & 7) * per_xcd + local;
+    const size_t pos = (size_t)(bid & 7) * per_xcd + local;
     PairItem it = xitems[pos];
     // one item per wave: scalar registers (uniform branches in the pipeline below, no exec-mask loop)
     it.slot = __builtin_amdgcn_readfirstlane(it.slot); it.slotT = __builtin_amdgcn_readfirstlane(it.slotT);
