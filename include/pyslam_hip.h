@@ -506,6 +506,11 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
                               reduced system the fused CG takes (not the direct solve, the explicit or the classic PCG); ps_get_option
                               tells.  Every other handle, and 0, launch the factor kernel in every set-up.  Speed only, same bits.
                               Handled ahead of the option table, as "expect_next" and "solve_horizon" are
+     "rows_regs"          [1; 0 / 1] the scaled-block products of the fused CG's set-up (S^ = L_i^-1 S_ij L_j^-T, S^ B) by one thread per
+                              block row in registers; the lagged set-up forms K_i only over the coarse nodes its row reaches; and where
+                              the lagged set-up applies, the exact set-up's block scaling and coarse row sums are one launch of the rows
+                              kernel.  0: one wave per block through LDS, the two launches.  Speed only, same bits.  Handled ahead of
+                              the option table
      "schur_pipeline"     [1; 0 / 1] the Schur pair kernel with two chunks per wave in flight (k_schur_pairs_db); 0: k_schur_pairs
      "lm_packed" [1; 0 / 1], "band_part" [1; 0 / 1], "band_part_chunk" [0 auto; 0 .. 4096 nodes], "sync_refactor" [1; 0 / 1],
      "hold_across_steps" [1; 0 / 1]: round-5 kernels and schedules against their predecessors (DESIGN.md sections 0 and 3)
@@ -526,7 +531,10 @@ int ps_set_option(ps_problem* h, const char* name, double value);
    "lin_zero_launches" / "lin_fills": linearisations so far that did the one / the other.
    "setup_ride": 1 if the pair launch also forms the block-Jacobi factors on this handle, else 0; "factors_ridden": linearisations
    so far that did; "factor_launches": set-ups of the fused CG that launched the factor kernel themselves; "factor_plan_mismatches":
-   those among them that found ridden factors made for another set-up plan (lagged / exact, coarse buffer) than their own. */
+   those among them that found ridden factors made for another set-up plan (lagged / exact, coarse buffer) than their own.
+   "rows_regs": the option; "rows_setups": lagged set-ups launched so far (k_rows_setup); "exact_row_setups": exact set-ups so far
+   whose block scaling and row sums were the rows kernel's one launch; "rows_lci_in_lds": 1 if the rows kernel holds the lagged
+   coarse factor in LDS on this handle (0 before the coarse level is built, and where the lagged set-up does not apply). */
 int ps_get_option(ps_problem* h, const char* name, double* value);
 
 /* hipEvent stage timers on the handle's stream (the reference has no tracing). */

@@ -916,6 +916,12 @@ int ps_set_option(ps_problem* h, const char* name, double value) {
         relook_launch_gates(h);
         return 0;
     }
+    // the set-up's block products in registers and its exact head in the rows kernel (csrc/ps_core.hip: rows_regs); 0: the forms before
+    if (!std::strcmp(name, "rows_regs")) {
+        h->rows_regs = value != 0 ? 1 : 0;
+        h->prelin_valid = h->prelm_valid = h->ride_valid = false;
+        return 0;
+    }
     h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     const char* refusal = nullptr;
     const int fx = ps_option_apply(*h, name, value, &refusal);
@@ -941,6 +947,10 @@ int ps_get_option(ps_problem* h, const char* name, double* value) {
     else if (n == "factor_launches") *value = (double)h->bjf_launches;
     else if (n == "factors_ridden") *value = (double)h->bjf_ridden;
     else if (n == "factor_plan_mismatches") *value = (double)h->bjf_mismatches;
+    else if (n == "rows_regs") *value = (double)h->rows_regs;
+    else if (n == "rows_setups") *value = (double)h->rows_setups;
+    else if (n == "exact_row_setups") *value = (double)h->exact_row_setups;
+    else if (n == "rows_lci_in_lds") *value = h->coarse_built && h->lagx_ok && h->rows_lci_lds ? 1.0 : 0.0;
     else return fail("ps_get_option: no read-back for option: " + n);
     return 0;
 }

@@ -330,7 +330,14 @@ struct ps_problem : PsOptions, PsCostHistory, PsCarried {
     double host_wait_ns = 0.0, host_call_ns = 0.0;   // PS_HOST_TIMING
     long host_waits = 0, host_calls = 0;
     size_t rows_lds = 0;
-    bool rows_attr_set = false, rows_lci_lds = false;
+    int rows_attr_set = 0;          // bit m: the dynamic-LDS attribute of k_rows_setup<D, m> covers rows_lds
+    bool rows_lci_lds = false;
+    // option "rows_regs" (ps_set_option, ahead of the table): the scaled-block products of the set-up by one thread per block
+    // row in registers (scaled_block_row) -- k_rows_setup<D, PS_RS_REGS>, which also forms K_i only over the coarse nodes of
+    // the row; and, where lagx_ok, the exact set-up's k_scale_blocks + k_coarse_rowsums as ONE launch of the rows kernel
+    // (PS_RS_EXACT).  0: the wave-per-block form and the two launches.  Every value is the same either way.
+    int rows_regs = 1;
+    long rows_setups = 0, exact_row_setups = 0;      // lagged set-ups launched / exact set-ups headed by the rows kernel
     int32_t *ent_ptr = nullptr, *ent_q = nullptr, *ent_lo = nullptr, *ent_hi = nullptr;   // explicit PCG: non-empty (row, node) runs
     int32_t *seg_ptr = nullptr, *seg_ent = nullptr, *seg_row = nullptr;                     // ... grouped by (node, node') for A_c
     int max_row_ents = 0;

@@ -456,7 +456,7 @@ int build_coarse(ps_problem* h) {
     h->Bmat = h->Bmat2[0];
     // lagged three-launch setup: folded single-launch CG only, LDS-resident coarse factor, rows that fit the LDS layout
     h->lagx_ok = !h->cg_explicit && !split && h->nc <= 96 && maxlen <= PS_RS_MAXROW;
-    h->side_todo = false; h->rows_attr_set = false;
+    h->side_todo = false; h->rows_attr_set = 0;
     if (h->lagx_ok) {
         if (h->alloc(&h->Bmat2[1], (size_t)nr * D * D) || h->alloc(&h->X2[0], (size_t)nr * D * h->nc) ||
             h->alloc(&h->X2[1], (size_t)nr * D * h->nc) || h->alloc(&h->Mpart, (size_t)nr * h->nc * (h->nc + 1))) return -1;
@@ -707,6 +707,21 @@ int xcg_coarse_inverse(ps_problem* h, hipStream_t st, int buf, int32_t* stat) {
 // block-Jacobi factor kernel writes the basis blocks.  cg_fused_setup follows it; linearize() asks for it ahead of the pair
 // launch whose finalising waves run that factor ("setup_ride") -- lci_next as the side stream's pending kick will leave it.
 struct CgSetupPlan { bool lagged; int use; double* basis_out; };
+
+// k_rows_setup<D, MODE> on the solver stream (MODE: ps_k_coarse.h); basis_lag / basis_cur, factor and X as the mode reads them
+template <int D, int MODE>
+int launch_rows_setup(ps_problem* h, const double* basis_lag, const double* basis_cur, const double* LciT, const double* X) {
+    if (!(h->rows_attr_set >> MODE & 1)) {
+        if (ensure_dynamic_lds((const void*)k_rows_setup<D, MODE>, (size_t)(h->rows_lds))) return -1;
+        h->rows_attr_set |= 1 << MODE;
+    }
+    static const int rs_ablate = ps_env("PS_RS_ABLATE") ? atoi(ps_env("PS_RS_ABLATE")) : 0;    // (measurement build only)
+    hipLaunchKernelGGL((k_rows_setup<D, MODE>), dim3(h->nr), dim3(PS_RS_THREADS), h->rows_lds, h->stream, h->nr, h->ncb, h->row_ptr,
+                       h->col_idx, h->aug_slot, h->S, h->Linv, basis_lag, basis_cur, h->arow_ptr, h->fine_nnz,
+                       h->run_lo, h->run_hi, h->pnode, h->pw0, h->pw1, LciT, X, h->cg_r[0],
+                       h->Saug, h->SB, h->Mpart, h->SZ, h->BSZ, h->rows_lci_lds ? 1 : 0, rs_ablate);
+    return 0;
+}
 inline CgSetupPlan cg_setup_plan(const ps_problem* h, bool allow_lag, int lci_next) {
     CgSetupPlan p{};
     p.lagged = h->G && h->lagx_ok && h->lagx && allow_lag && h->coarse_lag && lci_next >= 0;
@@ -767,15 +782,9 @@ int cg_fused_setup(ps_problem* h, int max_iters, bool allow_lag = false, bool rh
             hipLaunchKernelGGL(k_block_jacobi_factor<D>, dim3(cdiv(nr, 4)), dim3(256), 0, h->stream, nr, h->diag_slot,
                                h->S, h->Linv, h->status, h->g, h->cg_r[0], h->cg_w[0], h->cg_s[0], h->cg_p, h->cg_xh,
                                h->poses, h->pose_of_rid, h->coarse_basis, plan.basis_out, h->bgv);
-        if (!h->rows_attr_set) {
-            if (ensure_dynamic_lds((const void*)k_rows_setup<D>, (size_t)(h->rows_lds))) return -1;
-            h->rows_attr_set = true;
-        }
-        static const int rs_ablate = ps_env("PS_RS_ABLATE") ? atoi(ps_env("PS_RS_ABLATE")) : 0;    // (measurement build only)
-        hipLaunchKernelGGL(k_rows_setup<D>, dim3(nr), dim3(PS_RS_THREADS), h->rows_lds, h->stream, nr, ncb, h->row_ptr, h->col_idx,
-                           h->aug_slot, h->S, h->Linv, h->Bmat2[use], h->Bmat2[nb], h->arow_ptr, h->fine_nnz,
-                           h->run_lo, h->run_hi, h->pnode, h->pw0, h->pw1, h->LciT2[use], h->X2[use], h->cg_r[0],
-                           h->Saug, h->SB, h->Mpart, h->rows_lci_lds ? 1 : 0, rs_ablate);
+        if (h->rows_regs ? launch_rows_setup<D, PS_RS_REGS>(h, h->Bmat2[use], h->Bmat2[nb], h->LciT2[use], h->X2[use])
+                         : launch_rows_setup<D, PS_RS_WAVES>(h, h->Bmat2[use], h->Bmat2[nb], h->LciT2[use], h->X2[use])) return -1;
+        ++h->rows_setups;
         hipLaunchKernelGGL(k_coarse_mreduce<D>, dim3(cdiv((long)nc * (nc + 1) * 8, 256)), dim3(256), 0, h->stream, nr, ncb,
                            h->shi, h->Mpart, h->pnode, h->arow_ptr, h->Saug, h->cg_r[0], h->cg_w[0], h->cg_s[0], h->cg_p,
                            h->cg_xh, h->lag_status, h->status, h->h_setup_dev, ++h->setup_seq);
@@ -793,16 +802,20 @@ int cg_fused_setup(ps_problem* h, int max_iters, bool allow_lag = false, bool rh
         hipLaunchKernelGGL(k_block_jacobi_factor<D>, dim3(cdiv(nr, 4)), dim3(256), 0, h->stream, nr, h->diag_slot,
                            h->S, h->Linv, h->status, h->g, h->cg_r[0], h->cg_w[0], h->cg_s[0], h->cg_p, h->cg_xh,
                            h->poses, h->pose_of_rid, h->coarse_basis, plan.basis_out, h->bgv);
-    hipLaunchKernelGGL(k_scale_blocks<D>, dim3(h->nnzb), dim3(64), 0, h->stream, nr, h->row_ptr, h->col_idx,
-                       h->brow_of, h->Linv, h->S, h->aug_slot, h->Saug, G ? h->Bmat : (const double*)nullptr, h->SB);
+    // S^ -> matrix, S^ B -> SB, the row sums SZ and BSZ: one launch of the rows kernel where the lagged set-up's layout holds
+    // (its rows are whole in LDS), else k_scale_blocks and k_coarse_rowsums
+    const bool exact_rows = G && h->lagx_ok && h->rows_regs;
+    if (exact_rows) {
+        if (launch_rows_setup<D, PS_RS_EXACT>(h, nullptr, h->Bmat, nullptr, nullptr)) return -1;
+        ++h->exact_row_setups;
+    } else
+        hipLaunchKernelGGL(k_scale_blocks<D>, dim3(h->nnzb), dim3(64), 0, h->stream, nr, h->row_ptr, h->col_idx,
+                           h->brow_of, h->Linv, h->S, h->aug_slot, h->Saug, G ? h->Bmat : (const double*)nullptr, h->SB);
     if (G) {
         const int ncb = h->ncb, nc = h->nc;
-        if (h->side_pending) {                  // the side-stream factorisation still reads A_c / writes its buffer
-            HIP_OK(hipStreamWaitEvent(h->stream, h->ev_chol, 0));
-            h->side_pending = false;
-        }
-        hipLaunchKernelGGL(k_coarse_rowsums<D>, dim3(nr), dim3(256), (size_t)(ncb + 1) * D * D * sizeof(double), h->stream,
-                           nr, ncb, h->run_lo, h->run_hi, h->acol_idx, h->pnode, h->pw0, h->pw1, h->SB, h->SZ, h->Bmat, h->BSZ);
+        if (!exact_rows)
+            hipLaunchKernelGGL(k_coarse_rowsums<D>, dim3(nr), dim3(256), (size_t)(ncb + 1) * D * D * sizeof(double), h->stream,
+                               nr, ncb, h->run_lo, h->run_hi, h->acol_idx, h->pnode, h->pw0, h->pw1, h->SB, h->SZ, h->Bmat, h->BSZ);
         hipLaunchKernelGGL(k_coarse_matrix<D>, dim3(cdiv((long)ncb * ncb * D * D, 256)), dim3(256), 0, h->stream,
                            nr, ncb, h->slo, h->shi, h->pnode, h->pw0, h->pw1, h->BSZ, h->Ac);
         // Exact: factor this iteration's A_c on the solver stream (51 us at C3, serial).  Lagged

@@ -84,6 +84,43 @@ __global__ __launch_bounds__(64) void k_scale_blocks(
     }
 }
 
+// Row r of the scaled-block products of ONE block, in registers (option "rows_regs"): nothing is stored between the stages,
+// the caller's thread owns the row.
+//   T[r][c] = sum_a L_i^-1[r][a] S[a][c];  S^[r][c] = sum_a T[r][a] L_j^-1[c][a];  (S^ B)[r][c] = sum_a S^[r][a] B[a][c]
+// Every sum is the chain fma(., ., v) over a = 0 .. D-1 from v = 0.0 -- what the compiler emits for the `v += x * y` loops
+// of k_scale_blocks (v_fma_f64 with a zero addend, then v_fmac_f64) -- written out, so that the bits stay with the source.
+// Li_r: row r of L_i^-1; S, Lj, B0, B1: whole D x D blocks, row-major, in LDS or memory; B0 / B1 may be NULL (uniform).
+template <int D>
+PS_DEV void scaled_block_row(const double* Li_r, const double* S, const double* Lj, const double* B0, const double* B1,
+                             double (&sh)[D], double (&o0)[D], double (&o1)[D])
+{
+    double tr[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        double v = 0.0;
+#pragma unroll
+        for (int a = 0; a < D; ++a) v = fma(Li_r[a], S[a * D + c], v);
+        tr[c] = v;
+    }
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        double v = 0.0;
+#pragma unroll
+        for (int a = 0; a < D; ++a) v = fma(tr[a], Lj[c * D + a], v);
+        sh[c] = v;
+    }
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        double v = 0.0, u = 0.0;
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            if (B0) v = fma(sh[a], B0[a * D + c], v);
+            if (B1) u = fma(sh[a], B1[a * D + c], u);
+        }
+        o0[c] = v; o1[c] = u;
+    }
+}
+
 // The same for big reduced systems (explicit two-level PCG): one WAVE takes PS_SCB_NB consecutive blocks and requests all
 // their inputs before it touches any -- two memory round trips per PS_SCB_NB blocks instead of per block (a block per
 // 64-thread workgroup is a chain of index load -> operand loads -> three LDS phases with nothing to overlap it but the

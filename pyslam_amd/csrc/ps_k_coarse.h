@@ -764,10 +764,20 @@ __global__ __launch_bounds__(256) void k_coarse_recover(
 // The next X~ (row sums with the current basis, A_c, its factorisation, k_coarse_xbuild) is formed on the low-priority
 // side stream at the start of the NEXT call, beside the linearisation kernels.
 // ---------------------------------------------------------------------------
+// MODE (option "rows_regs", csrc/ps_core.hip) -- one kernel, the phases are shared:
+//   PS_RS_WAVES  the products by one wave per block through LDS (rows_regs 0)
+//   PS_RS_REGS   the products by one thread per block row in registers (scaled_block_row); K_i only over the coarse nodes
+//                the row's columns hang on
+//   PS_RS_EXACT  the head of the EXACT set-up (the first call of a solve) in this kernel's shape: loads, the products and the
+//                SZ runs with the CURRENT basis (Bcur), BSZ_i = B_i^T SZ_i; writes Saug, SB, SZ, BSZ and stops -- what
+//                k_scale_blocks + k_coarse_rowsums do in two launches, sum for sum
 #define PS_RS_THREADS 1024
 #define PS_RS_MAXROW 96                 // fine blocks per row the LDS layout holds (4 x 96 x 288 B + strips < 160 KB)
+#define PS_RS_WAVES 0
+#define PS_RS_REGS 1
+#define PS_RS_EXACT 2
 
-template <int D>
+template <int D, int MODE>
 __global__ __launch_bounds__(PS_RS_THREADS) void k_rows_setup(
     int nr, int ncb, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col_idx,
     const int32_t* __restrict__ aug_slot, const double* __restrict__ S, const double* __restrict__ Linv,
@@ -778,9 +788,12 @@ __global__ __launch_bounds__(PS_RS_THREADS) void k_rows_setup(
     const double* __restrict__ LciT /* lagged L~^-1, transposed */, const double* __restrict__ X /* lagged X~: nr x D x nc */,
     const double* __restrict__ ghat /* g^ (nr x D) */,
     double* __restrict__ Saug, double* __restrict__ SB, double* __restrict__ Mpart /* nr x nc x (nc + 1) */,
+    double* __restrict__ SZ, double* __restrict__ BSZ /* PS_RS_EXACT: nr x ncb x D x D each */,
     int lci_in_lds /* the LDS allocation has room for L~^-T (nc x nc) */, int ablate)
 {
     constexpr int DD = D * D;
+    constexpr bool EXACT = MODE == PS_RS_EXACT;
+    static_assert(PS_RS_MAXROW * D <= PS_RS_THREADS, "a thread per block row");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int i = blockIdx.x, t = threadIdx.x, NT = blockDim.x;
     const int nc = ncb * D, nf = row_ptr[i + 1] - row_ptr[i], rp = row_ptr[i], n36 = nf * DD;
@@ -798,13 +811,14 @@ __global__ __launch_bounds__(PS_RS_THREADS) void k_rows_setup(
     int32_t* sSlot = sI;                    // nf: slot of block k in the augmented matrix
     int32_t* sRun = sSlot + PS_RS_MAXROW;   // 2 ncb: run_lo / run_hi of this row, relative to its first block
     int32_t* sCrow = sRun + 2 * 64;         // ncb: first block of coarse row q
+    int32_t* sSpan = sCrow + 62;            // 2: first and one-past-last column of SZ~_i that a run fills (ncb <= 32: the words are free)
     // ---- every input of the row in one memory round trip (the gathers through col_idx: two)
     const int a_rp = arow_ptr[i];
     for (int idx = t; idx < n36; idx += NT) {
         const int k = idx / DD, e = idx - k * DD, b = rp + k, j = col_idx[b];
         sS[idx] = S[(size_t)b * DD + e];
         sLj[idx] = Linv[(size_t)j * DD + e];
-        sBl[idx] = Blag[(size_t)j * DD + e];
+        if (!EXACT) sBl[idx] = Blag[(size_t)j * DD + e];
         sBc[idx] = Bcur[(size_t)j * DD + e];
     }
     for (int k = t; k < nf; k += NT) {
@@ -814,17 +828,37 @@ __global__ __launch_bounds__(PS_RS_THREADS) void k_rows_setup(
     }
     for (int q = t; q < ncb; q += NT) {
         sRun[q] = run_lo[i * ncb + q] - a_rp; sRun[64 + q] = run_hi[i * ncb + q] - a_rp;
-        sCrow[q] = arow_ptr[nr + q];
+        if (!EXACT) sCrow[q] = arow_ptr[nr + q];
     }
-    for (int idx = t; idx < D * nc; idx += NT) sX[idx] = X[(size_t)i * D * nc + idx];
-    if (lci_in_lds && !(ablate & 1)) for (int idx = t; idx < nc * nc; idx += NT) sL[idx] = LciT[idx];
+    if (!EXACT) {
+        for (int idx = t; idx < D * nc; idx += NT) sX[idx] = X[(size_t)i * D * nc + idx];
+        if (lci_in_lds && !(ablate & 1)) for (int idx = t; idx < nc * nc; idx += NT) sL[idx] = LciT[idx];
+        if (t < D) sK[t * (nc + 1) + nc] = ghat[(size_t)i * D + t];
+    } else if (t < DD) sK[t] = Bcur[(size_t)i * DD + t];          // B_i (the strip of K_i is free here)
     if (t < DD) sLi[t] = Linv[(size_t)i * DD + t];
-    if (t < D) sK[t * (nc + 1) + nc] = ghat[(size_t)i * D + t];
     const int row_slot = a_rp + fine_nnz[i];                        // first coarse column block of row i
     const int a0 = pnode[i] * D;
     __syncthreads();
-    // ---- per block, by ONE wave (lane = entry (r, c); wave barriers only): S^_ij = L_i^-1 S_ij L_j^-T -> matrix;
-    // S^_ij B~_j (lagged basis: this iteration's borders); S^_ij B_j (current basis: the side stream's input)
+    // ---- per block ROW, by one thread in registers: S^_ij = L_i^-1 S_ij L_j^-T -> matrix; S^_ij B~_j (lagged basis: this
+    // iteration's borders) -> LDS, behind a barrier (the other rows of the block read B~_j); S^_ij B_j (current basis: the
+    // side stream's input, and the EXACT variant's only one)
+    if (MODE != PS_RS_WAVES) {
+        const bool act = t < nf * D && (EXACT || !(ablate & 2));
+        const int k = act ? t / D : 0, r = act ? t - k * D : 0;
+        double sh[D], o0[D], o1[D];
+        if (act) {
+            scaled_block_row<D>(sLi + r * D, sS + k * DD, sLj + k * DD, EXACT ? nullptr : sBl + k * DD, sBc + k * DD, sh, o0, o1);
+            const size_t o = (size_t)sSlot[k] * DD + r * D;
+#pragma unroll
+            for (int c = 0; c < D; ++c) { Saug[o + c] = sh[c]; SB[o + c] = o1[c]; }
+        }
+        if (!EXACT) __syncthreads();
+        if (act) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) sBl[k * DD + r * D + c] = EXACT ? o1[c] : o0[c];
+        }
+    } else
+    // ---- (rows_regs 0) per block, by ONE wave (lane = entry (r, c); wave barriers only), the same three products
     {
         // (stage by stage over ALL of the wave's blocks, so that the LDS latencies of independent blocks overlap)
         constexpr int NB = (PS_RS_MAXROW + PS_RS_THREADS / 64 - 1) / (PS_RS_THREADS / 64);
@@ -882,6 +916,11 @@ __global__ __launch_bounds__(PS_RS_THREADS) void k_rows_setup(
         }
     }
     __syncthreads();
+    // the columns of SZ~_i that a run fills: everything outside is exactly +0.0 (an empty run leaves acc as it began)
+    if (MODE == PS_RS_REGS && t < 64) {
+        const unsigned long long m = __ballot(t < ncb && sRun[64 + t] > sRun[t]);
+        if (t == 0) { sSpan[0] = m ? (__ffsll((long long)m) - 1) * D : 0; sSpan[1] = m ? (64 - __clzll((long long)m)) * D : 0; }
+    }
     // ---- SZ~_i[q] = sum over the run of row i's blocks whose column lies in supp(q) of w(j, q) S^_ij B~_j
     for (int idx = t; idx < ncb * DD; idx += NT) {
         const int q = idx / DD, e = idx - q * DD, r = e / D, c = e - r * D;
@@ -889,17 +928,33 @@ __global__ __launch_bounds__(PS_RS_THREADS) void k_rows_setup(
         double acc = 0.0;
         for (int k = k0; k < k1; ++k)
             acc += sBl[k * DD + e] * (((int)sW[2 * PS_RS_MAXROW + k] == q) ? sW[2 * k] : sW[2 * k + 1]);
-        sT[r * nc + q * D + c] = acc;
+        if (EXACT) { sT[idx] = acc; SZ[(size_t)i * ncb * DD + idx] = acc; }     // (k_coarse_rowsums' layout: node, then entry)
+        else sT[r * nc + q * D + c] = acc;
     }
     __syncthreads();
-    // ---- K_i = SZ~_i L~^-T, to both borders of the augmented matrix
+    if (EXACT) {
+        // ---- BSZ_i[q] = B_i^T SZ_i[q], the summand of A_c = P^T S^ P
+        for (int idx = t; idx < ncb * DD; idx += NT) {
+            const int q = idx / DD, e = idx - q * DD, r = e / D, c = e - r * D;
+            double acc = 0.0;
+#pragma unroll
+            for (int m = 0; m < D; ++m) acc += sK[m * D + r] * sT[q * DD + m * D + c];
+            BSZ[(size_t)i * ncb * DD + idx] = acc;
+        }
+        return;
+    }
+    // ---- K_i = SZ~_i L~^-T, to both borders of the augmented matrix.  PS_RS_REGS: only the terms whose SZ~ column a run
+    // fills -- the others add +-0 to a partial sum that began at +0.0 and leave its bits (L~^-T finite: a failed lagged factor is
+    // reported through lag_status and the solve repeated)
     const double* Lt = lci_in_lds ? sL : LciT;
+    const int klo = MODE == PS_RS_REGS ? sSpan[0] : 0, khi = MODE == PS_RS_REGS ? sSpan[1] : nc;
     for (int idx = t; idx < 2 * D * nc && !(ablate & 4); idx += NT) {      // two lanes per entry: even / odd terms of the sum
         const int o = idx >> 1, par = idx & 1;
         const int r = o / nc, c = o - r * nc, q = c / D, cc = c - q * D;
+        const int kend = min(c, khi - 1);
         double v = 0.0;
 #pragma unroll 8
-        for (int k = par; k <= c; k += 2) v += sT[r * nc + k] * Lt[(size_t)k * nc + c];     // = L~^-1[c][k]
+        for (int k = klo + ((klo ^ par) & 1); k <= kend; k += 2) v += sT[r * nc + k] * Lt[(size_t)k * nc + c];     // = L~^-1[c][k]
         v += __shfl_xor(v, 1, 64);
         if (par) continue;
         sK[r * (nc + 1) + c] = v;
