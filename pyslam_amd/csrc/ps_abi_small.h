@@ -1,5 +1,6 @@
 // ps_abi_small.h -- C ABI: frame-to-frame RANSAC and dense photometric alignment.
-// Part of ps_core.hip (one translation unit; included from there, in this order).
+// Part of ps_core.hip (one translation unit; included from there, in this order, after ps_host_ransac.h: the host side of a
+// RANSAC call that the three front ends share).
 
 // ---- frame-to-frame RANSAC (reference pyslam/pipelines/ransac.py) -------------------------------
 int ps_ransac_transforms(const double* pts_1, const double* pts_2, int32_t batch, int32_t n, double* T_out) {
@@ -18,65 +19,72 @@ int ps_ransac_transforms(const double* pts_1, const double* pts_2, int32_t batch
     return 0;
 }
 
+extern "C++" {
+namespace {
+struct F2fLayout {                   // the parts of a call's device block (RcBlock, ps_host_ransac.h)
+    size_t pts1, pts2, obs2, cam, idx;                              // in: pts_1 | pts_2 | obs_2 (3 N each) | cam (8) doubles | samples (int32)
+    size_t masks;                                                   // [H][N] bytes, only with own_masks (ps_ransac_cost's are rc_score_call's)
+    size_t model, T_best, counts, best, best_mask;                  // out: T_all (16 H) | T_best (16) doubles | counts (H) | best (2) int32 | best_mask (N bytes)
+    RcSpan in, out;                                                 // the upload, ps_ransac_frame_to_frame's download
+    size_t total;
+    F2fLayout(size_t N, size_t H, size_t set_size, bool own_masks) {
+        RcBlock B;
+        pts1 = B.part(3 * N * F64); pts2 = B.pack(3 * N * F64); obs2 = B.pack(3 * N * F64); cam = B.pack(8 * F64); idx = B.pack(H * set_size * I32);
+        in = B.span(pts1);
+        masks = B.part(own_masks ? H * N : 0);
+        model = B.part(16 * H * F64); T_best = B.pack(16 * F64); counts = B.pack(H * I32); best = B.pack(2 * I32); best_mask = B.pack(N);
+        out = B.span(model);
+        total = B.part(0);
+    }
+};
+
+// uploads pts_1 | pts_2 | obs_2 | cam | idx (pts_2 and idx may be NULL: scoring)
+int f2f_begin(const F2fLayout& L, char* d, const double* pts_1, const double* pts_2, const double* obs_2, int32_t num_pts,
+              const double* cam5, const int32_t* idx, size_t num_idx) {
+    const RcCam cam(cam5);
+    const size_t pb = 3 * F64 * num_pts;
+    return rc_upload(d, L.in, {{L.pts1, pts_1, pb}, {L.pts2, pts_2, pb}, {L.obs2, obs_2, pb}, {L.cam, cam.v, sizeof(cam.v)}, {L.idx, idx, num_idx * I32}});
+}
+
+// k_ransac_hypotheses on the uploaded samples (masks == NULL: the block's own) or, scoring, on the transforms at L.model
+void f2f_hypotheses(const F2fLayout& L, char* d, int32_t num_pts, int32_t set_size, int32_t num_hyp, double thresh, uint8_t* masks) {
+    hipLaunchKernelGGL(k_ransac_hypotheses, dim3(num_hyp), dim3(256), 0, 0, num_pts, set_size,
+                       masks ? (const int32_t*)nullptr : (const int32_t*)(d + L.idx), (const double*)(d + L.pts1),
+                       masks ? (const double*)nullptr : (const double*)(d + L.pts2), (const double*)(d + L.obs2), (const double*)(d + L.cam),
+                       thresh, (double*)(d + L.model), (int32_t*)(d + L.counts), masks ? masks : (uint8_t*)(d + L.masks));
+}
+}  // namespace
+}  // extern "C++"
+
 int ps_ransac_cost(const double* T, int32_t num_hyp, const double* pts_1, const double* obs_2, int32_t num_pts,
                    const double* cam5, double thresh, uint8_t* masks, int32_t* counts) {
     if (!T || !pts_1 || !obs_2 || !cam5 || num_hyp < 0 || num_pts < 0) return fail("bad argument");
     if (num_hyp == 0) return 0;
-    if (need_device()) return -1;
-    DevBuf dT, dp, dobs, dcam, dcnt, dmask;
-    const size_t pb = (size_t)num_pts * 3 * sizeof(double);
-    if (dT.get((size_t)num_hyp * 16 * sizeof(double)) || dp.get(pb) || dobs.get(pb) || dcam.get(5 * sizeof(double)) ||
-        dcnt.get((size_t)num_hyp * sizeof(int32_t)) || dmask.get((size_t)num_hyp * num_pts)) return -1;
-    HIP_OK(hipMemcpy(dT.p, T, (size_t)num_hyp * 16 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dp.p, pts_1, pb, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dobs.p, obs_2, pb, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dcam.p, cam5, 5 * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_ransac_hypotheses, dim3(num_hyp), dim3(256), 0, 0, num_pts, 0, (const int32_t*)nullptr,
-                       dp.as<double>(), (const double*)nullptr, dobs.as<double>(), dcam.as<double>(), thresh,
-                       dT.as<double>(), dcnt.as<int32_t>(), dmask.as<uint8_t>());
-    HIP_OK(hipGetLastError());
-    if (masks) HIP_OK(hipMemcpy(masks, dmask.p, (size_t)num_hyp * num_pts, hipMemcpyDeviceToHost));
-    if (counts) HIP_OK(hipMemcpy(counts, dcnt.p, (size_t)num_hyp * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_OK(hipDeviceSynchronize());
-    return 0;
+    const F2fLayout L((size_t)num_pts, (size_t)num_hyp, 0, false);
+    return rc_score_call(
+        L, T, 16 * F64 * num_hyp, num_hyp, num_pts, masks, counts,
+        [&](char* d) { return f2f_begin(L, d, pts_1, nullptr, obs_2, num_pts, cam5, nullptr, 0); },
+        [&](char* d, uint8_t* dmasks) { f2f_hypotheses(L, d, num_pts, 0, num_hyp, thresh, dmasks); });
 }
 
 int ps_ransac_frame_to_frame(const double* pts_1, const double* pts_2, const double* obs_2, int32_t num_pts,
                              const int32_t* sample_idx, int32_t num_hyp, int32_t set_size, const double* cam5,
                              double thresh, double* T_all, int32_t* counts, int32_t* best_index,
                              int32_t* best_count, double* T_best, uint8_t* best_mask) {
-    if (!pts_1 || !pts_2 || !obs_2 || !sample_idx || !cam5 || num_pts <= 0 || num_hyp <= 0 || set_size <= 0)
-        return fail("bad argument");
-    for (size_t k = 0; k < (size_t)num_hyp * set_size; ++k)
-        if (sample_idx[k] < 0 || sample_idx[k] >= num_pts) return fail("sample index out of range");
-    if (need_device()) return -1;
-    DevBuf dp1, dp2, dobs, dcam, didx, dT, dcnt, dmask, dbest, dTb, dbm;
-    const size_t pb = (size_t)num_pts * 3 * sizeof(double);
-    if (dp1.get(pb) || dp2.get(pb) || dobs.get(pb) || dcam.get(5 * sizeof(double)) ||
-        didx.get((size_t)num_hyp * set_size * sizeof(int32_t)) || dT.get((size_t)num_hyp * 16 * sizeof(double)) ||
-        dcnt.get((size_t)num_hyp * sizeof(int32_t)) || dmask.get((size_t)num_hyp * num_pts) ||
-        dbest.get(2 * sizeof(int32_t)) || dTb.get(16 * sizeof(double)) || dbm.get((size_t)num_pts)) return -1;
-    HIP_OK(hipMemcpy(dp1.p, pts_1, pb, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dp2.p, pts_2, pb, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dobs.p, obs_2, pb, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dcam.p, cam5, 5 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(didx.p, sample_idx, (size_t)num_hyp * set_size * sizeof(int32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_ransac_hypotheses, dim3(num_hyp), dim3(256), 0, 0, num_pts, set_size, didx.as<int32_t>(),
-                       dp1.as<double>(), dp2.as<double>(), dobs.as<double>(), dcam.as<double>(), thresh,
-                       dT.as<double>(), dcnt.as<int32_t>(), dmask.as<uint8_t>());
+    if (!pts_1 || !pts_2 || !obs_2 || !cam5 || num_pts <= 0) return fail("bad argument");
+    if (rc_check_samples(sample_idx, num_hyp, set_size, num_pts, nullptr)) return -1;
+    const F2fLayout L((size_t)num_pts, (size_t)num_hyp, (size_t)set_size, true);
+    DevBuf buf;
+    if (need_device() || buf.get(L.total)) return -1;
+    char* d = buf.as<char>();
+    if (f2f_begin(L, d, pts_1, pts_2, obs_2, num_pts, cam5, sample_idx, (size_t)num_hyp * set_size)) return -1;
+    f2f_hypotheses(L, d, num_pts, set_size, num_hyp, thresh, nullptr);
     HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(256), 0, 0, num_hyp, num_pts, dcnt.as<int32_t>(), dT.as<double>(),
-                       dmask.as<uint8_t>(), dbest.as<int32_t>(), dTb.as<double>(), dbm.as<uint8_t>());
+    hipLaunchKernelGGL(k_ransac_best, dim3(1), dim3(256), 0, 0, num_hyp, num_pts, (const int32_t*)(d + L.counts), (const double*)(d + L.model),
+                       (const uint8_t*)(d + L.masks), (int32_t*)(d + L.best), (double*)(d + L.T_best), (uint8_t*)(d + L.best_mask));
     HIP_OK(hipGetLastError());
-    int32_t bi[2];
-    HIP_OK(hipMemcpy(bi, dbest.p, sizeof(bi), hipMemcpyDeviceToHost));
-    if (best_index) *best_index = bi[0];
-    if (best_count) *best_count = bi[1];
-    if (T_best) HIP_OK(hipMemcpy(T_best, dTb.p, 16 * sizeof(double), hipMemcpyDeviceToHost));
-    if (best_mask) HIP_OK(hipMemcpy(best_mask, dbm.p, (size_t)num_pts, hipMemcpyDeviceToHost));
-    if (T_all) HIP_OK(hipMemcpy(T_all, dT.p, (size_t)num_hyp * 16 * sizeof(double), hipMemcpyDeviceToHost));
-    if (counts) HIP_OK(hipMemcpy(counts, dcnt.p, (size_t)num_hyp * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return 0;
+    return rc_download(d, L.out, {{L.model, T_all, 16 * F64 * num_hyp}, {L.T_best, T_best, 16 * F64}, {L.counts, counts, num_hyp * I32},
+                                  {L.best, best_index, I32}, {L.best + I32, best_count, I32}, {L.best_mask, best_mask, (size_t)num_pts}});
 }
 
 // ---- dense photometric alignment (reference pyslam/residuals/photometric_residual.py) ------------------

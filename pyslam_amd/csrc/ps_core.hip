@@ -23,6 +23,7 @@
 
 #include "pyslam_hip.h"
 #include "ps_kernels.h"
+#include "ps_ransac_core.h"
 #include "ps_ransac.h"
 #include "ps_k_twoview.h"
 #include "ps_k_pnp.h"
@@ -685,6 +686,7 @@ extern "C" {
 #include "ps_abi_solver.h"
 #include "ps_abi_cov.h"
 #include "ps_abi_triang.h"
+#include "ps_host_ransac.h"
 #include "ps_abi_small.h"
 #include "ps_abi_twoview.h"
 #include "ps_abi_pnp.h"

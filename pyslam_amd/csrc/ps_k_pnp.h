@@ -14,7 +14,7 @@
 //     polished by three Newton steps on the ORIGINAL quartic.
 //     u = ((r_1 - 1) v^2 - 2 r_1 cos beta v + 1 + r_1) / (2 (cos gamma - v cos alpha)), r_1 = (a^2 - c^2) / b^2;
 //     s_1^2 = b^2 / (1 + v^2 - 2 v cos beta);  Q_i = s_i f_i;  pose = rigid alignment of (P_i) onto (Q_i) by ransac_align's scheme
-//     (ps_ransac.h), written out again here for exactly three points (pnp_align3) so that ps_ransac.h stays as it is.
+//     (ps_ransac.h), for exactly three points and strictly evaluated (pnp_align3).
 //   A slot is EMPTY (T = 0, count 0, flag bit 0) when its root is not real (D < 0 or m not positive), not positive or not finite,
 //     when u <= 0, when s_1^2 is not positive, or when a denominator is zero (A_4, s, a Newton derivative, the denominators of u and
 //     s_1^2, a vanishing second singular value).  Nothing is NaN.
@@ -31,7 +31,7 @@
 // calls on the same input are bit-identical.  The four roots and poses live in LDS; the small solves use fully unrolled private
 // arrays (static indices only) or LDS.
 #pragma once
-#include "ps_math.h"
+#include "ps_ransac_core.h"
 
 // ---- scalar building blocks ----------------------------------------------------------------------------------------------------
 
@@ -144,8 +144,10 @@ PS_DEV void pnp_quartic_roots(const double* __restrict__ A, double* __restrict__
     }
 }
 
-// [R | t] (12, row-major 3 x 4) of the alignment Q_i ~ R P_i + t of three points (cf. ransac_align, tv_svd2).  false: the second
-// singular value vanishes.
+// [R | t] (12, row-major 3 x 4) of the alignment Q_i ~ R P_i + t of three points.  false: the second singular value vanishes.
+// The scheme is ransac_align's, but the Jacobi sweeps are written out here and not taken from rc_jacobi3 (ps_ransac_core.h):
+// this function is evaluated strictly (`fp contract(off)`, which is lexical), rc_jacobi3 under the default contraction, and the
+// contraction mode is part of the poses' bits.  Only the sort, which moves data and computes nothing, is shared.
 PS_DEV bool pnp_align3(const double* __restrict__ P /* 9 */, const double* __restrict__ Q /* 9 */, double* __restrict__ T) {
 #pragma clang fp contract(off)
     const double third = 1.0 / 3.0;
@@ -190,16 +192,7 @@ PS_DEV bool pnp_align3(const double* __restrict__ P /* 9 */, const double* __res
     double sg[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) sg[k] = sqrt(A[k][0] * A[k][0] + A[k][1] * A[k][1] + A[k][2] * A[k][2]);
-#define PNP_CSWAP(i, j)                                                                     \
-    if (sg[j] > sg[i]) {                                                                    \
-        double w_ = sg[i]; sg[i] = sg[j]; sg[j] = w_;                                       \
-        _Pragma("unroll") for (int r = 0; r < 3; ++r) {                                     \
-            w_ = A[i][r]; A[i][r] = A[j][r]; A[j][r] = w_;                                  \
-            w_ = V[i][r]; V[i][r] = V[j][r]; V[j][r] = w_;                                  \
-        }                                                                                   \
-    }
-    PNP_CSWAP(0, 1) PNP_CSWAP(0, 2) PNP_CSWAP(1, 2)
-#undef PNP_CSWAP
+    rc_sort3(sg, A, V);
     if (!(sg[0] > 0.0) || !(sg[1] > 1e-15 * sg[0]) || !(sg[0] < 1e300)) return false;
     double u1[3], u2[3], v1[3], v2[3];
 #pragma unroll
@@ -260,6 +253,21 @@ PS_DEV double pnp_sq_err(const double* __restrict__ T /* 12 */, double X, double
     return du * du + dv * dv;
 }
 
+// What a scoring pass needs beside the pose: the landmarks, their pixels, the camera and the threshold.
+struct PnpScore { const double* __restrict__ pts_w; const double* __restrict__ obs; double cu, cv, fu, fv, thresh; };
+
+PS_DEV PnpScore pnp_score(const double* __restrict__ pts_w, const double* __restrict__ obs, const double* __restrict__ cam, double thresh) {
+    return PnpScore{pts_w, obs, cam[0], cam[1], cam[2], cam[3], thresh};
+}
+
+// is point i an inlier of the pose T; *d: its squared reprojection error
+PS_DEV bool pnp_point_inlier(const PnpScore& s, const double* __restrict__ T /* 12 */, int i, double* __restrict__ d) {
+    bool front;
+    *d = pnp_sq_err(T, s.pts_w[3 * (size_t)i], s.pts_w[3 * (size_t)i + 1], s.pts_w[3 * (size_t)i + 2], s.obs[2 * (size_t)i],
+                    s.obs[2 * (size_t)i + 1], s.cu, s.cv, s.fu, s.fv, &front);
+    return front && *d < s.thresh;
+}
+
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void k_pnp_normalise(int num_pts, const double* __restrict__ obs, const double* __restrict__ cam,
@@ -281,7 +289,7 @@ __global__ __launch_bounds__(256) void k_pnp_hypotheses(
     double* __restrict__ T_all, int32_t* __restrict__ counts, uint8_t* __restrict__ flags, uint8_t* __restrict__ masks)
 {
     __shared__ double sT[4][12], sroot[4], scs[3], sr1b2[2];
-    __shared__ int sok[4], sdeg, scount[4][4];
+    __shared__ int sok[4], sdeg, scount[4 * 4];
     const int h = blockIdx.x, t = threadIdx.x;
     const bool solve = sample_idx != nullptr;
     if (solve) {
@@ -333,34 +341,22 @@ __global__ __launch_bounds__(256) void k_pnp_hypotheses(
         if (t < 4) sok[t] = t == 0 ? 1 : 0;
     }
     __syncthreads();
-    const double cu = cam[0], cv = cam[1], fu = cam[2], fv = cam[3];
+    const PnpScore score = pnp_score(pts_w, obs, cam, thresh);
     int cnt[4] = {0, 0, 0, 0};
     for (int i = t; i < num_pts; i += 256) {
-        const double X = pts_w[3 * (size_t)i], Y = pts_w[3 * (size_t)i + 1], Z = pts_w[3 * (size_t)i + 2];
-        const double ou = obs[2 * (size_t)i], ov = obs[2 * (size_t)i + 1];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            bool in = false;
-            if (sok[k]) {                                        // (uniform over the workgroup)
-                bool front;
-                const double d = pnp_sq_err(sT[k], X, Y, Z, ou, ov, cu, cv, fu, fv, &front);
-                in = front && d < thresh;
-            }
+            double d;
+            const bool in = sok[k] /* (uniform over the workgroup) */ && pnp_point_inlier(score, sT[k], i, &d);
             cnt[k] += in ? 1 : 0;
             if (masks && k == 0) masks[(size_t)h * num_pts + i] = in ? 1 : 0;
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) cnt[k] += __shfl_xor(cnt[k], off, 64);
-        if ((t & 63) == 0) scount[t >> 6][k] = cnt[k];
-    }
-    __syncthreads();
+    rc_block_partials(cnt, scount);
     if (solve) {
-        if (t < 4) counts[(size_t)h * 4 + t] = scount[0][t] + scount[1][t] + scount[2][t] + scount[3][t];
+        if (t < 4) counts[(size_t)h * 4 + t] = rc_block_total(scount, 4, t);
     } else if (t == 0) {
-        counts[h] = scount[0][0] + scount[1][0] + scount[2][0] + scount[3][0];
+        counts[h] = rc_block_total(scount, 4, 0);
     }
 }
 
@@ -374,35 +370,18 @@ __global__ __launch_bounds__(256) void k_pnp_best(
     __shared__ int32_t sc[256], si[256];
     __shared__ double sT[12];
     const int t = threadIdx.x;
-    int bc = -1, bi = 0x7fffffff;
-    for (int h = t; h < num_slots; h += 256) {
-        const int c = counts[h];
-        if (c > bc) { bc = c; bi = h; }                         // ascending h: keeps the first maximum of this thread
-    }
-    sc[t] = bc; si[t] = bi;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (t < off) {
-            const int c2 = sc[t + off], i2 = si[t + off];
-            if (c2 > sc[t] || (c2 == sc[t] && i2 < si[t])) { sc[t] = c2; si[t] = i2; }
-        }
-        __syncthreads();
-    }
-    const int hb = si[0];
+    const RcBest w = rc_first_max(num_slots, counts, sc, si);
+    const int hb = w.index;                                      // the flat slot: 4 * hypothesis + slot
     if (t < 16) {
         const double v = T_all[(size_t)hb * 16 + t];
         T_best[t] = v;
         if (t < 12) sT[t] = v;
     }
     __syncthreads();
-    const double cu = cam[0], cv = cam[1], fu = cam[2], fv = cam[3];
-    for (int i = t; i < num_pts; i += 256) {
-        bool front;
-        const double d = pnp_sq_err(sT, pts_w[3 * (size_t)i], pts_w[3 * (size_t)i + 1], pts_w[3 * (size_t)i + 2], obs[2 * (size_t)i],
-                                    obs[2 * (size_t)i + 1], cu, cv, fu, fv, &front);
-        mask[i] = (front && d < thresh) ? 1 : 0;
-    }
-    if (t == 0) { info[0] = hb >> 2; info[1] = hb & 3; info[2] = sc[0]; }
+    const PnpScore score = pnp_score(pts_w, obs, cam, thresh);
+    double d;
+    for (int i = t; i < num_pts; i += 256) mask[i] = pnp_point_inlier(score, sT, i, &d) ? 1 : 0;
+    if (t == 0) { info[0] = hb >> 2; info[1] = hb & 3; info[2] = w.count; }
 }
 
 #define PNP_SUMS 28        // 21 entries of H (upper triangle, row-major) | 6 of g | sum |r|^2
@@ -415,10 +394,11 @@ __global__ __launch_bounds__(256) void k_pnp_refine(
     const double* __restrict__ T_best, uint8_t* __restrict__ mask /* in: raw, out: final */, int32_t* __restrict__ info,
     double* __restrict__ result)
 {
-    __shared__ double sT[12], sred[4][PNP_SUMS], sH[36], sL[36], sg[6];
+    __shared__ double sT[12], sred[4 * PNP_SUMS], sH[36], sL[36], sg[6];
     __shared__ int sfail, s4[4];
     const int t = threadIdx.x;
-    const double cu = cam[0], cv = cam[1], fu = cam[2], fv = cam[3];
+    const PnpScore score = pnp_score(pts_w, obs, cam, thresh);
+    const double cu = score.cu, cv = score.cv, fu = score.fu, fv = score.fv;
     const int raw_count = info[2];
     double* hist = result + 16;
     double* sq_err = result + 16 + iters + 1;
@@ -450,18 +430,9 @@ __global__ __launch_bounds__(256) void k_pnp_refine(
             for (int r = 0; r < 6; ++r) acc[21 + r] += Ju[r] * ru + Jv[r] * rv;
             acc[27] += ru * ru + rv * rv;
         }
-#pragma unroll
-        for (int k = 0; k < PNP_SUMS; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
-        }
-        if ((t & 63) == 0) {
-#pragma unroll
-            for (int k = 0; k < PNP_SUMS; ++k) sred[t >> 6][k] = acc[k];
-        }
-        __syncthreads();
-        if (t < PNP_SUMS) {                                      // waves 0..3 in order
-            const double s = ((sred[0][t] + sred[1][t]) + sred[2][t]) + sred[3][t];
+        rc_block_partials(acc, sred);
+        if (t < PNP_SUMS) {
+            const double s = rc_block_total(sred, PNP_SUMS, t);
             if (t < 21) {
                 int r = 0, k = t;
                 while (k >= 6 - r) { k -= 6 - r; ++r; }
@@ -529,14 +500,12 @@ __global__ __launch_bounds__(256) void k_pnp_refine(
     int cnt = 0;
     double cost = 0.0;
     for (int i = t; i < num_pts; i += 256) {
-        bool front;
-        const double d = pnp_sq_err(sT, pts_w[3 * (size_t)i], pts_w[3 * (size_t)i + 1], pts_w[3 * (size_t)i + 2], obs[2 * (size_t)i],
-                                    obs[2 * (size_t)i + 1], cu, cv, fu, fv, &front);
-        cnt += (front && d < thresh) ? 1 : 0;
+        double d;
+        cnt += pnp_point_inlier(score, sT, i, &d) ? 1 : 0;
         if (mask[i]) cost += d;
     }
-    cnt = tv_block_count(cnt, s4);
-    cost = tv_block_sum(cost, sred[0]);
+    cnt = rc_block_sum(cnt, s4);
+    cost = rc_block_sum(cost, sred);
     bool fin = true;
 #pragma unroll
     for (int k = 0; k < 12; ++k) fin = fin && pnp_finite(sT[k]);
@@ -547,15 +516,13 @@ __global__ __launch_bounds__(256) void k_pnp_refine(
     __syncthreads();
     int fcnt = 0;
     for (int i = t; i < num_pts; i += 256) {
-        bool front;
-        const double d = pnp_sq_err(sT, pts_w[3 * (size_t)i], pts_w[3 * (size_t)i + 1], pts_w[3 * (size_t)i + 2], obs[2 * (size_t)i],
-                                    obs[2 * (size_t)i + 1], cu, cv, fu, fv, &front);
-        const bool in = front && d < thresh;
+        double d;
+        const bool in = pnp_point_inlier(score, sT, i, &d);
         sq_err[i] = d;
         mask[i] = in ? 1 : 0;
         fcnt += in ? 1 : 0;
     }
-    fcnt = tv_block_count(fcnt, s4);
+    fcnt = rc_block_sum(fcnt, s4);
     if (t < 12) result[t] = sT[t];
     if (t == 0) {
         result[12] = 0.0; result[13] = 0.0; result[14] = 0.0; result[15] = T_best[15];

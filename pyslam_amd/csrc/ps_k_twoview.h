@@ -1,5 +1,5 @@
 // ps_k_twoview.h -- monocular two-view initialisation: essential-matrix RANSAC on the device (gfx950, fp64).
-// Part of ps_core.hip (one translation unit; included after ps_ransac.h).  pyslam_amd/pipelines/epipolar.py is the same
+// Part of ps_core.hip (one translation unit; included after ps_ransac_core.h and ps_ransac.h).  pyslam_amd/pipelines/epipolar.py is the same
 // definition in numpy; this project has no reference counterpart for it (as for MonoCamera and the matcher).
 //
 // Input: N correspondences obs_1, obs_2 (pixels), a pinhole camera (cu, cv, fu, fv), H minimal sets of 8 point indices.
@@ -8,7 +8,7 @@
 //     itself (A^T A is never formed: that would square sigma_1 / sigma_8); F = f as 3 x 3, row-major, so that x_2^T F x_1 = 0.
 //     A sample with a repeated index, or with a pivot whose magnitude is not above 1e-12 of the first (largest) pivot, is
 //     DEGENERATE: flag 1, E = 0, count 0.  So is an F of rank < 2.
-//   projection: F = U S V^T by a one-sided Jacobi SVD of the 3 x 3 (as ransac_align's), E = u_1 v_1^T + u_2 v_2^T
+//   projection: F = U S V^T by a one-sided Jacobi SVD of the 3 x 3 (rc_jacobi3, ps_ransac_core.h), E = u_1 v_1^T + u_2 v_2^T
 //     (= U diag(1, 1, 0) V^T, Frobenius norm sqrt 2).
 //   SIGN RULE: the entry of E with the largest absolute value is positive; of equal magnitudes the one with the lowest row-major
 //     index decides.
@@ -27,11 +27,11 @@
 //     candidate's count is the number of inliers with det > 0, lambda > 0 and mu > 0.  Highest count wins, lowest index first.
 //     T_21 = [R | t], |t| = 1; parallax of an inlier = angle between R x_1 and x_2 in degrees.
 //
-// No atomics; every sum is reduced in a fixed order (lane tree, then waves 0..3, then workgroups in slot order), so two calls on the
+// No atomics; every sum is reduced in a fixed order (rc_block_sum: lane tree, then waves 0..3; then workgroups in slot order), so two calls on the
 // same input are bit-identical.  The small dense solves run in lane 0 on matrices kept in LDS (runtime-indexed pivoting on a
 // private array would go through scratch); the scoring pass is one coalesced 32 B read per point and hypothesis.
 #pragma once
-#include "ps_math.h"
+#include "ps_ransac_core.h"
 
 // ---- scalar building blocks (no thread indices: pointers may address LDS or private memory) ----------------------------------
 
@@ -45,52 +45,18 @@ PS_DEV void tv_fix_sign(double* __restrict__ E) {
     }
 }
 
-// The two leading singular pairs of the row-major 3 x 3 F (one-sided Jacobi on the columns of F, cf. ransac_align).
+// The two leading singular pairs of the row-major 3 x 3 F (rc_jacobi3 on the columns of F, sorted).
 // false: rank < 2 (sigma_2 <= 1e-12 sigma_1) or a non-finite entry.
 PS_DEV bool tv_svd2(const double* __restrict__ F, double* __restrict__ u1, double* __restrict__ u2, double* __restrict__ v1,
                     double* __restrict__ v2)
 {
-    double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};       // A[col][row], V[col][row]
+    double A[3][3], V[3][3], sg[3];                                    // A[col][row], V[col][row]
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int r = 0; r < 3; ++r) A[c][r] = F[3 * r + c];
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;
-#pragma unroll
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-            const double al = A[p][0] * A[p][0] + A[p][1] * A[p][1] + A[p][2] * A[p][2];
-            const double be = A[q][0] * A[q][0] + A[q][1] * A[q][1] + A[q][2] * A[q][2];
-            const double ga = A[p][0] * A[q][0] + A[p][1] * A[q][1] + A[p][2] * A[q][2];
-            if (ga == 0.0 || !(fabs(ga) > 1.2e-16 * sqrt(al * be))) continue;
-            rotated = true;
-            const double zeta = (be - al) / (2.0 * ga);
-            const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-            const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const double ap = A[p][r], aq = A[q][r], vp = V[p][r], vq = V[q][r];
-                A[p][r] = c * ap - s * aq; A[q][r] = s * ap + c * aq;
-                V[p][r] = c * vp - s * vq; V[q][r] = s * vp + c * vq;
-            }
-        }
-        if (!rotated) break;
-    }
-    double sg[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sg[k] = sqrt(A[k][0] * A[k][0] + A[k][1] * A[k][1] + A[k][2] * A[k][2]);
-    // columns by descending sigma (three compare-exchanges on static indices: no runtime-indexed private array)
-#define TV_CSWAP(i, j)                                                                      \
-    if (sg[j] > sg[i]) {                                                                    \
-        double w_ = sg[i]; sg[i] = sg[j]; sg[j] = w_;                                       \
-        _Pragma("unroll") for (int r = 0; r < 3; ++r) {                                     \
-            w_ = A[i][r]; A[i][r] = A[j][r]; A[j][r] = w_;                                  \
-            w_ = V[i][r]; V[i][r] = V[j][r]; V[j][r] = w_;                                  \
-        }                                                                                   \
-    }
-    TV_CSWAP(0, 1) TV_CSWAP(0, 2) TV_CSWAP(1, 2)
-#undef TV_CSWAP
+    rc_jacobi3<false>(A, V, sg);                                       // (a non-finite column pair is skipped)
+    rc_sort3(sg, A, V);
     if (!(sg[0] > 0.0) || !(sg[1] > 1e-12 * sg[0]) || !(sg[0] < 1e300)) return false;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -268,23 +234,17 @@ PS_DEV bool tv_in_front(const double* __restrict__ R, const double* __restrict__
 
 // ---- kernels -----------------------------------------------------------------------------------------------------------------
 
-// sum of `v` over the workgroup of 256 in a fixed order: xor tree inside a wave, then waves 0..3.  Every thread gets the total.
-PS_DEV double tv_block_sum(double v, double* __restrict__ s4 /* LDS, 4 */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();                                           // (s4 may still be read from the previous call)
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s4[0] + s4[1]) + s4[2]) + s4[3];
+// What a scoring pass needs beside the matrix: the normalised correspondences, 1 / fu^2, 1 / fv^2 and the threshold.
+struct TvScore { const double4* __restrict__ xn; double ifu2, ifv2, thresh; };
+
+PS_DEV TvScore tv_score(const double4* __restrict__ xn, const double* __restrict__ cam, double thresh) {
+    return TvScore{xn, 1.0 / (cam[2] * cam[2]), 1.0 / (cam[3] * cam[3]), thresh};
 }
 
-PS_DEV int tv_block_count(int v, int* __restrict__ s4 /* LDS, 4 */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s4[0] + s4[1] + s4[2] + s4[3];
+// is correspondence i an inlier of E
+PS_DEV bool tv_point_inlier(const TvScore& s, const double* __restrict__ E, int i) {
+    const double4 p = s.xn[i];
+    return tv_inlier(E, p.x, p.y, p.z, p.w, s.ifu2, s.ifv2, s.thresh);
 }
 
 __global__ __launch_bounds__(256) void k_tv_normalise(int num_pts, const double* __restrict__ obs_1, const double* __restrict__ obs_2,
@@ -341,15 +301,14 @@ __global__ __launch_bounds__(256) void k_tv_hypotheses(
     double E[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) E[k] = sE[k];
-    const double ifu2 = 1.0 / (cam[2] * cam[2]), ifv2 = 1.0 / (cam[3] * cam[3]);
+    const TvScore score = tv_score(xn, cam, thresh);
     int cnt = 0;
     for (int i = t; i < num_pts; i += 256) {
-        const double4 p = xn[i];
-        const bool in = tv_inlier(E, p.x, p.y, p.z, p.w, ifu2, ifv2, thresh);
+        const bool in = tv_point_inlier(score, E, i);
         if (masks) masks[(size_t)h * num_pts + i] = in ? 1 : 0;
         cnt += in ? 1 : 0;
     }
-    cnt = tv_block_count(cnt, scount);
+    cnt = rc_block_sum(cnt, scount);
     if (t == 0) counts[h] = cnt;
 }
 
@@ -361,31 +320,15 @@ __global__ __launch_bounds__(256) void k_tv_best(
 {
     __shared__ int32_t sc[256], si[256];
     const int t = threadIdx.x;
-    int bc = -1, bi = 0x7fffffff;
-    for (int h = t; h < H; h += 256) {
-        const int c = counts[h];
-        if (c > bc) { bc = c; bi = h; }
-    }
-    sc[t] = bc; si[t] = bi;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (t < off) {
-            const int c2 = sc[t + off], i2 = si[t + off];
-            if (c2 > sc[t] || (c2 == sc[t] && i2 < si[t])) { sc[t] = c2; si[t] = i2; }
-        }
-        __syncthreads();
-    }
-    const int hb = si[0];
-    if (t == 0) { info[0] = hb; info[1] = sc[0]; }
+    const RcBest w = rc_first_max(H, counts, sc, si);
+    const int hb = w.index;
+    if (t == 0) { info[0] = hb; info[1] = w.count; }
     double E[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) E[k] = E_all[(size_t)hb * 9 + k];
     if (t < 9) E_best[t] = E_all[(size_t)hb * 9 + t];
-    const double ifu2 = 1.0 / (cam[2] * cam[2]), ifv2 = 1.0 / (cam[3] * cam[3]);
-    for (int i = t; i < num_pts; i += 256) {
-        const double4 p = xn[i];
-        mask[i] = tv_inlier(E, p.x, p.y, p.z, p.w, ifu2, ifv2, thresh) ? 1 : 0;
-    }
+    const TvScore score = tv_score(xn, cam, thresh);
+    for (int i = t; i < num_pts; i += 256) mask[i] = tv_point_inlier(score, E, i) ? 1 : 0;
 }
 
 // Hartley statistics of the inliers from the per-workgroup partials, every thread for itself, in slot order:
@@ -423,7 +366,7 @@ __global__ __launch_bounds__(256) void k_tv_refit_pass(
         const double v[5] = {p.x, p.y, p.z, p.w, in ? 1.0 : 0.0};
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
-            const double s = tv_block_sum(v[k], s4);
+            const double s = rc_block_sum(v[k], s4);
             if (t == 0) partA[8 * (size_t)g + k] = s;
         }
         return;
@@ -432,8 +375,8 @@ __global__ __launch_bounds__(256) void k_tv_refit_pass(
     tv_hartley(G, partA, partB, stage == 2, hn);
     const double dx1 = p.x - hn[0], dy1 = p.y - hn[1], dx2 = p.z - hn[3], dy2 = p.w - hn[4];
     if (stage == 1) {
-        const double d1 = tv_block_sum(in ? sqrt(dx1 * dx1 + dy1 * dy1) : 0.0, s4);
-        const double d2 = tv_block_sum(in ? sqrt(dx2 * dx2 + dy2 * dy2) : 0.0, s4);
+        const double d1 = rc_block_sum(in ? sqrt(dx1 * dx1 + dy1 * dy1) : 0.0, s4);
+        const double d2 = rc_block_sum(in ? sqrt(dx2 * dx2 + dy2 * dy2) : 0.0, s4);
         if (t == 0) { partB[2 * (size_t)g] = d1; partB[2 * (size_t)g + 1] = d2; }
         return;
     }
@@ -448,7 +391,7 @@ __global__ __launch_bounds__(256) void k_tv_refit_pass(
     for (int pp = 0; pp < 9; ++pp)
 #pragma unroll
         for (int q = pp; q < 9; ++q) {
-            const double s = tv_block_sum(a[pp] * a[q], s4);
+            const double s = rc_block_sum(a[pp] * a[q], s4);
             if (t == 0) partC[45 * (size_t)g + k] = s;
             ++k;
         }
@@ -466,7 +409,7 @@ __global__ __launch_bounds__(256) void k_tv_finish(
     __shared__ double sM[81], sQ[81], sf[9], sE[9], sRa[9], sRb[9], st[3];
     __shared__ int sok, s4[4];
     const int t = threadIdx.x;
-    const double ifu2 = 1.0 / (cam[2] * cam[2]), ifv2 = 1.0 / (cam[3] * cam[3]);
+    const TvScore score = tv_score(xn, cam, thresh);
     const int raw_count = info[1];
     int final_count = raw_count, kept = 0;
     if (t < 9) sE[t] = E_best[t];
@@ -500,12 +443,11 @@ __global__ __launch_bounds__(256) void k_tv_finish(
             for (int k = 0; k < 9; ++k) E[k] = sf[k];
             int cnt = 0;
             for (int i = t; i < num_pts; i += 256) {
-                const double4 p = xn[i];
-                const bool in = tv_inlier(E, p.x, p.y, p.z, p.w, ifu2, ifv2, thresh);
+                const bool in = tv_point_inlier(score, E, i);
                 mask_refit[i] = in ? 1 : 0;
                 cnt += in ? 1 : 0;
             }
-            cnt = tv_block_count(cnt, s4);
+            cnt = rc_block_sum(cnt, s4);
             if (cnt >= raw_count) {
                 kept = 1; final_count = cnt;
                 for (int i = t; i < num_pts; i += 256) mask[i] = mask_refit[i];      // (this thread's own entries)
@@ -544,7 +486,7 @@ __global__ __launch_bounds__(256) void k_tv_finish(
             c[3] += tv_in_front(Rb, tt, -1.0, p.x, p.y, p.z, p.w, &cs) ? 1 : 0;
         }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) c[k] = tv_block_count(c[k], s4);
+    for (int k = 0; k < 4; ++k) c[k] = rc_block_sum(c[k], s4);
     int win = 0;
 #pragma unroll
     for (int k = 1; k < 4; ++k) if (c[k] > c[win]) win = k;

@@ -8,15 +8,15 @@
 // One workgroup per hypothesis: lane 0 aligns the minimal set, then all 256 threads score the
 // points (one coalesced pass over pts_1 / obs_2 per hypothesis, both L2-resident: 48 B per point).
 #pragma once
-#include "ps_math.h"
+#include "ps_ransac_core.h"
 
 // Rotation C and translation r of  p_2 ~ C p_1 + r  for n point pairs (reference :17-42):
 //   W = 1/n sum (p_2 - c_2)(p_1 - c_1)^T = U S V^T,  C = U diag(1, 1, det U det V) V^T,  r = c_2 - C c_1.
 // With (u_i, v_i) the singular pairs of the two largest singular values the reference's formula
 // equals  u_1 v_1^T + u_2 v_2^T + (u_1 x u_2)(v_1 x v_2)^T  whatever signs LAPACK picks for the
-// third pair, so only those two pairs are needed.  They come from a one-sided (Hestenes) Jacobi
-// SVD of the 3 x 3 matrix: columns of W V are rotated until orthogonal (relative accuracy
-// ~eps sigma_1 / sigma_2, no squaring of the condition number as with W^T W).
+// third pair, so only those two pairs are needed.  They come from the one-sided Jacobi SVD of the
+// 3 x 3 matrix (rc_jacobi3, ps_ransac_core.h); what follows the sweeps is this function's own: the two
+// largest by index, and LAPACK's users' completion of a rank-deficient set.
 PS_DEV void ransac_align(int n, const int32_t* __restrict__ idx /* or NULL: points 0..n-1 */,
                          const double* __restrict__ pts_1, const double* __restrict__ pts_2,
                          double* __restrict__ T /* 12: rows of [C | r] */)
@@ -44,32 +44,8 @@ PS_DEV void ransac_align(int n, const int32_t* __restrict__ idx /* or NULL: poin
     for (int col = 0; col < 3; ++col)
 #pragma unroll
         for (int row = 0; row < 3; ++row) A[col][row] *= inv_n;
-    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};      // V[col][row]
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;
-#pragma unroll
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-            const double al = A[p][0] * A[p][0] + A[p][1] * A[p][1] + A[p][2] * A[p][2];
-            const double be = A[q][0] * A[q][0] + A[q][1] * A[q][1] + A[q][2] * A[q][2];
-            const double ga = A[p][0] * A[q][0] + A[p][1] * A[q][1] + A[p][2] * A[q][2];
-            if (ga == 0.0 || fabs(ga) <= 1.2e-16 * sqrt(al * be)) continue;
-            rotated = true;
-            const double zeta = (be - al) / (2.0 * ga);
-            const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-            const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const double ap = A[p][r], aq = A[q][r], vp = V[p][r], vq = V[q][r];
-                A[p][r] = c * ap - s * aq; A[q][r] = s * ap + c * aq;
-                V[p][r] = c * vp - s * vq; V[q][r] = s * vp + c * vq;
-            }
-        }
-        if (!rotated) break;
-    }
-    double sg[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sg[k] = sqrt(A[k][0] * A[k][0] + A[k][1] * A[k][1] + A[k][2] * A[k][2]);
+    double V[3][3], sg[3];                                   // V[col][row]
+    rc_jacobi3<true>(A, V, sg);                              // (a non-finite column pair is rotated, as ever here)
     int i1 = 0;
     if (sg[1] > sg[i1]) i1 = 1;
     if (sg[2] > sg[i1]) i1 = 2;
@@ -162,7 +138,7 @@ __global__ __launch_bounds__(256) void k_ransac_hypotheses(
     uint8_t* __restrict__ masks /* [H][num_pts] */)
 {
     __shared__ double sT[12];
-    __shared__ int32_t scount[4];
+    __shared__ int scount[4];
     const int h = blockIdx.x, t = threadIdx.x;
     if (sample_idx) {
         if (t == 0) {
@@ -183,11 +159,8 @@ __global__ __launch_bounds__(256) void k_ransac_hypotheses(
         masks[(size_t)h * num_pts + i] = in ? 1 : 0;
         cnt += in ? 1 : 0;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if ((t & 63) == 0) scount[t >> 6] = cnt;
-    __syncthreads();
-    if (t == 0) counts[h] = scount[0] + scount[1] + scount[2] + scount[3];
+    cnt = rc_block_sum(cnt, scount);
+    if (t == 0) counts[h] = cnt;
 }
 
 // np.argmax(inlier_nums): the FIRST hypothesis with the maximal count; copies its transform and mask out
@@ -198,22 +171,9 @@ __global__ __launch_bounds__(256) void k_ransac_best(
 {
     __shared__ int32_t sc[256], si[256];
     const int t = threadIdx.x;
-    int bc = -1, bi = 0x7fffffff;
-    for (int h = t; h < H; h += 256) {
-        const int c = counts[h];
-        if (c > bc) { bc = c; bi = h; }            // ascending h: keeps the first maximum of this thread
-    }
-    sc[t] = bc; si[t] = bi;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (t < off) {
-            const int c2 = sc[t + off], i2 = si[t + off];
-            if (c2 > sc[t] || (c2 == sc[t] && i2 < si[t])) { sc[t] = c2; si[t] = i2; }
-        }
-        __syncthreads();
-    }
-    const int hb = si[0];
-    if (t == 0) { best[0] = hb; best[1] = sc[0]; }
+    const RcBest w = rc_first_max(H, counts, sc, si);
+    const int hb = w.index;
+    if (t == 0) { best[0] = hb; best[1] = w.count; }
     if (t < 16) T_best[t] = T_all[(size_t)hb * 16 + t];
     for (int i = t; i < num_pts; i += 256) best_mask[i] = masks[(size_t)hb * num_pts + i];
 }

@@ -153,6 +153,40 @@ def test_without_the_refinement_the_raw_slot_comes_back_bit_for_bit(seeded):
     assert res['cost_history'].shape == (1,) and np.isfinite(res['cost_history']).all()
 
 
+@pytest.fixture(scope='module')
+def tie_base():
+    """The N = 67 scene, its H = 64 table, and the restatement's winning row and the row with the lowest count."""
+    pts, obs, _, _ = sc.scene(67)
+    samples, ref = sc.oracle(67, 64)
+    per_row = ref['counts'].max(axis=1)
+    return pts, obs, samples, ref, ref['best'], int(np.argmin(per_row)), per_row
+
+
+# 4 H slots against the selection's stride of 256: exactly one stride; the only winner beyond it; a tie across it (the lower row
+# wins); two strides with the later row planted first
+@pytest.mark.parametrize('h,rows', [(64, (5, 63)), (65, (64,)), (65, (20, 64)), (129, (128, 3))])
+def test_pnp_ties_go_to_the_first_maximum(tie_base, h, rows):
+    import ransac_scenes
+    pts, obs, samples, base, w, l, per_row = tie_base
+    assert per_row[w] > per_row[l] and (per_row == per_row[w]).sum() == 1            # the base winner is unique
+    table = ransac_scenes.tie_table(samples, w, l, h, rows)
+    ref = ab.ransac(pts, obs, sc.CAM, table, THRESH, refine_winner=False, sensitivity=True)
+    cond = sc.conditions(ref)
+    assert cond['near'] == 0 and cond['near_final'] == 0                             # no squared error in the margin: nothing left out
+    rs = solver(pts, obs, refine=False)
+    res = rs._device_ransac(table)
+    T_all, counts, empty, degenerate = rs._device_hypotheses(table)
+    print('H = {} ({} slots), winner row {} (count {}) at {}, elsewhere row {} (count {}): device best {} slot {} count {}; '
+          'restatement {} / {} / {}'.format(h, 4 * h, w, per_row[w], rows, l, per_row[l], res['best'], res['best_slot'], res['raw_count'],
+                                            ref['best'], ref['best_slot'], ref['raw_count']))
+    assert (res['best'], res['best_slot']) == (ref['best'], ref['best_slot']) == (min(rows), base['best_slot'])
+    assert np.array_equal(counts, ref['counts']) and np.array_equal(empty, ref['empty'])
+    assert res['raw_count'] == res['count'] == ref['raw_count'] == per_row[w]
+    assert np.array_equal(res['mask'], ref['mask'])
+    assert np.array_equal(res['T_cw'], T_all[res['best'], res['best_slot']])        # bit for bit: the refinement is off
+    assert (T_all[list(rows)] == T_all[res['best']]).all()                          # every planted row is the same hypothesis
+
+
 def test_two_calls_are_bit_identical(seeded):
     pts, obs, _, _ = sc.scene(192)
     _, _, _, samples = seeded
