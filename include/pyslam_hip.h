@@ -647,6 +647,34 @@ int ps_pnp_ransac(const double* pts_w, const double* obs, int32_t num_pts, const
                   const double* cam5, double thresh, int32_t refine_iters, double* T_cw, uint8_t* mask, int32_t* info,
                   double* sq_err, double* cost_history);
 
+/* Similarity (Sim(3)) alignment: robust 7-DoF alignment of two matched 3-D point sets by RANSAC over Umeyama fits of three pairs --
+   a monocular map against a second map, a trajectory against ground truth, two keyframes that see the same landmarks
+   (pyslam_amd/pipelines/sim3.py; the definition, the degeneracy, tie and refit rules: pyslam_amd/csrc/ps_k_sim3.h, restated by
+   pyslam_amd/pipelines/similarity.py).  Stateless; host pointers in, host pointers out.  pts_1, pts_2: (num_pts, 3); the model is
+   p_2 = s R p_1 + t, stored row-major 4 x 4 as [s R | t; 0 0 0 1] with the scalar s beside it.  cam5 = cu cv fu fv b (b is not read)
+   selects the PIXEL mode: obs_1, obs_2 (num_pts, 2) are the pixels of the points in their own cameras, thresh is in pixels^2 on the
+   larger of the two squared reprojection errors, and both depths must be positive.  cam5 == NULL selects the METRIC mode: obs_1 and
+   obs_2 must be NULL, thresh is on |s R p_1 + t - p_2|^2 (+inf: every finite pair).  sample_idx: (num_hyp, 3) point indices, drawn by
+   the caller; fixed_scale: 1 holds s = 1 (maps with a metric scale), else 0; num_pts >= 3; thresh > 0.  Two calls on the same input
+   are bit-identical.
+   ps_sim3_hypotheses -- per sample S_all (num_hyp x 16), scales, counts, flags (num_hyp bytes; 1: the sample is degenerate --
+                         collinear or repeated points, a non-finite row, a scale that is not positive: S = 0, scale 0, count 0).
+   ps_sim3_score      -- inlier masks (num_S x num_pts bytes) and counts of given models S (num_S x 16).
+   ps_sim3_ransac     -- the whole chain with one synchronisation: hypotheses, the first one with the most inliers, its mask, up to
+                         refit_iters (0..1000) rounds of a fit over all current inliers and a rescoring.  S_21 (16), scale, mask
+                         (num_pts), sq_err (num_pts: the final model's errors; +inf when it is degenerate), info (8): best hypothesis,
+                         raw count, final count, rounds adopted, how the loop ended (0: every round ran, 1: a round with fewer inliers
+                         was discarded, 2: a round reproduced its mask, 3: a degenerate round was discarded), 1 when the result is
+                         degenerate, 0, 0. */
+int ps_sim3_hypotheses(const double* pts_1, const double* pts_2, const double* obs_1, const double* obs_2, int32_t num_pts,
+                       const int32_t* sample_idx, int32_t num_hyp, const double* cam5, double thresh, int32_t fixed_scale,
+                       double* S_all, double* scales, int32_t* counts, uint8_t* flags);
+int ps_sim3_score(const double* S, int32_t num_S, const double* pts_1, const double* pts_2, const double* obs_1, const double* obs_2,
+                  int32_t num_pts, const double* cam5, double thresh, uint8_t* masks, int32_t* counts);
+int ps_sim3_ransac(const double* pts_1, const double* pts_2, const double* obs_1, const double* obs_2, int32_t num_pts,
+                   const int32_t* sample_idx, int32_t num_hyp, const double* cam5, double thresh, int32_t fixed_scale,
+                   int32_t refit_iters, double* S_21, double* scale, uint8_t* mask, int32_t* info, double* sq_err);
+
 /* Dense photometric alignment: one SE(3) pose, one residual per reference pixel --
    PhotometricResidualSE3 (pyslam/residuals/photometric_residual.py:38-161) inside Problem's Gauss-Newton
    iteration with element-wise IRLS (pyslam/problem.py:279-360), as the dense VO pipeline runs it per pyramid

@@ -156,6 +156,11 @@ SIGNATURES = {
     'ps_pnp_score': (C.c_int, [c_f64p, C.c_int32, c_f64p, c_f64p, C.c_int32, c_f64p, C.c_double, c_u8p, c_i32p]),
     'ps_pnp_ransac': (C.c_int, [c_f64p, c_f64p, C.c_int32, c_i32p, C.c_int32, c_f64p, C.c_double, C.c_int32, c_f64p, c_u8p, c_i32p,
                                 c_f64p, c_f64p]),
+    'ps_sim3_hypotheses': (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p, C.c_int32, c_i32p, C.c_int32, c_f64p, C.c_double, C.c_int32,
+                                     c_f64p, c_f64p, c_i32p, c_u8p]),
+    'ps_sim3_score': (C.c_int, [c_f64p, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p, C.c_int32, c_f64p, C.c_double, c_u8p, c_i32p]),
+    'ps_sim3_ransac': (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p, C.c_int32, c_i32p, C.c_int32, c_f64p, C.c_double, C.c_int32, C.c_int32,
+                                 c_f64p, c_f64p, c_u8p, c_i32p, c_f64p]),
     'ps_photometric_create': (C.c_int, [C.POINTER(PhotoDesc), C.c_void_p, C.POINTER(H)]),
     'ps_photometric_destroy': (C.c_int, [H]),
     'ps_photometric_set_pose': (C.c_int, [H, c_f64p]),

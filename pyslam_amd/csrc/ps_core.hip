@@ -27,6 +27,7 @@
 #include "ps_ransac.h"
 #include "ps_k_twoview.h"
 #include "ps_k_pnp.h"
+#include "ps_k_sim3.h"
 #include "ps_photo.h"
 #include "ps_k_dense.h"
 #include "ps_k_feat.h"
@@ -690,6 +691,7 @@ extern "C" {
 #include "ps_abi_small.h"
 #include "ps_abi_twoview.h"
 #include "ps_abi_pnp.h"
+#include "ps_abi_sim3.h"
 #include "ps_abi_dense.h"
 #include "ps_abi_feat.h"
 

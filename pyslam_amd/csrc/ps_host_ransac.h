@@ -1,5 +1,5 @@
-// ps_host_ransac.h -- the host side of one RANSAC call, shared by the three front ends' C ABI (ps_abi_small.h: frame-to-frame,
-// ps_abi_twoview.h, ps_abi_pnp.h).  Part of ps_core.hip (inside its extern "C" block, before the three).
+// ps_host_ransac.h -- the host side of one RANSAC call, shared by the four front ends' C ABI (ps_abi_small.h: frame-to-frame,
+// ps_abi_twoview.h, ps_abi_pnp.h, ps_abi_sim3.h).  Part of ps_core.hip (inside its extern "C" block, before the four).
 //
 // Every call takes ONE device block (inputs | work space | results), one upload of the packed inputs and one download of the
 // packed results, which is its only synchronisation.  (The scoring exports keep their H x N masks in a block of their own and

@@ -1,5 +1,6 @@
 // ps_ransac_core.h -- what the RANSAC front ends on the device share (gfx950): frame-to-frame rigid alignment (ps_ransac.h),
-// two-view essential matrix (ps_k_twoview.h), absolute pose (ps_k_pnp.h).  Part of ps_core.hip, included before the three.
+// two-view essential matrix (ps_k_twoview.h), absolute pose (ps_k_pnp.h), similarity alignment (ps_k_sim3.h).  Part of ps_core.hip,
+// included before the four.
 //
 //   rc_first_max        np.argmax over int32 counts: the FIRST index with the maximal count.  Every front end's contract.
 //   rc_block_sum        sum over the workgroup of 256 in a fixed order; rc_block_partials / rc_block_total for several sums at once

@@ -671,3 +671,32 @@ def pnp_scene(num_pts=192, seed=11, outlier_fraction=0.3, pixel_noise=0.5, rotve
     if n_out:
         obs[num_pts - n_out:] = rng.uniform([0., 0.], [w, h], size=(n_out, 2))
     return pts, obs, T, outlier
+
+
+# ---------------------------------------------------------------------------
+# two monocular maps of two_view's scene whose scales are unrelated: 3-D - 3-D correspondences with outliers (pipelines/sim3.py)
+# ---------------------------------------------------------------------------
+def sim3_scene(num_pts=192, seed=11, scale=2.5, outlier_fraction=0.3, point_noise=0.005, pixel_noise=0.5,
+               rotvec=(0.04, -0.3, 0.06), t=(1.5, -0.2, 0.8)):
+    """The points of _two_view_scene(num_pts, seed) as two maps: pts_1 in the frame of camera 1 at the scene's own scale, pts_2 in
+    the frame of camera 2 (p = R p_1 + t, R = exp(rotvec)) in a map ``scale`` times as large, so p_2 = scale R p_1 + scale t.  Each
+    map's points carry relative depth noise along their ray (``point_noise``), each camera's pixels (TWO_VIEW_CAMERA) Gaussian noise.
+    The first ``outlier_fraction * num_pts`` rows of pts_2 and obs_2 are rotated by one place among themselves: wrong matches between
+    real points.  -> (pts_1 (N, 3), pts_2 (N, 3), obs_1 (N, 2), obs_2 (N, 2), scale, T_21 (4, 4) = [R | scale t], outlier mask (N,))."""
+    pts, T = _two_view_scene(num_pts, seed, rotvec, t)
+    cu, cv, fu, fv, w, h = TWO_VIEW_CAMERA
+    rng = np.random.default_rng([seed, 3])
+    q = pts @ T[:3, :3].T + T[:3, 3]
+    obs_1 = np.stack([fu * pts[:, 0] / pts[:, 2] + cu, fv * pts[:, 1] / pts[:, 2] + cv], axis=1)
+    obs_2 = np.stack([fu * q[:, 0] / q[:, 2] + cu, fv * q[:, 1] / q[:, 2] + cv], axis=1)
+    obs_1 = obs_1 + pixel_noise * rng.standard_normal(obs_1.shape)
+    obs_2 = obs_2 + pixel_noise * rng.standard_normal(obs_2.shape)
+    pts_1 = pts * (1. + point_noise * rng.standard_normal(num_pts))[:, None]
+    pts_2 = scale * q * (1. + point_noise * rng.standard_normal(num_pts))[:, None]
+    n_out = int(outlier_fraction * num_pts)
+    outlier = np.arange(num_pts) < n_out
+    if n_out:
+        pts_2[:n_out], obs_2[:n_out] = np.roll(pts_2[:n_out], 1, axis=0), np.roll(obs_2[:n_out], 1, axis=0)
+    T_21 = T.copy()
+    T_21[:3, 3] = scale * T[:3, 3]
+    return pts_1, pts_2, obs_1, obs_2, float(scale), T_21, outlier
