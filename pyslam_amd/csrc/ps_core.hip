@@ -161,6 +161,7 @@ PersistLedger& ps_persist_ledger() { static PersistLedger* p = new PersistLedger
 
 #include "ps_host_bandpart.h"
 #include "ps_options.h"
+#include "ps_structure.h"
 
 // ---- the handle by role -------------------------------------------------------------------------------------------------
 // ps_problem derives from three plain structs so that the struct itself says what a member is: a user option (PsOptions,
@@ -677,6 +678,7 @@ inline void relook_launch_gates(ps_problem* h) {
 #include "ps_host_ldi.h"
 #include "ps_host_iteration.h"
 #include "ps_host_build.h"
+#include "ps_host_structure.h"
 
 // ===========================================================================
 // C ABI

@@ -6,7 +6,7 @@
 // read it, never on the host).  What stays on the host: everything whose size is the number of blocks or tasks (block
 // pattern, work items, XCD lists, two-level structures: 10^4 .. 10^5 records).
 //
-// The lists are BIT-IDENTICAL to the host builder's (ps_abi_problem.h keeps it: PS_CREATE_DEVICE=0, and it is what problems
+// The lists are BIT-IDENTICAL to the host builder's (ps_host_structure.h keeps it: PS_CREATE_DEVICE=0, and it is what problems
 // below the size threshold use): pairs are generated in the host builder's order (landmark by landmark, row a < row b over
 // the rows of variable poses), keyed (tile, block row, block column) and sorted with a STABLE radix sort -- the order the
 // host's two stable counting passes per tile produce.  tests/test_gpu_create.py holds the two builds against each other
@@ -165,6 +165,37 @@ __global__ __launch_bounds__(256) void k_build_fill_i32(long n, int32_t* __restr
     if (i < n) p[i] = v;
 }
 
+// ---- the two builders of ps_problem_create (host: ps_host_structure.h; device: below) behind one interface each.  The stages
+// (ps_abi_problem.h) choose a builder once and call its phases in order; which tables exist on the host is the builder's business.
+struct PairTasks {                              // tasks = runs of equal (tile, block) in the pair list
+    std::vector<int32_t> start, tile;
+    std::vector<uint64_t> key;                  // (lower reduced pose << 32) | higher
+};
+struct PairBuilder {
+    long long total = 0;                        // pairs, known after prepare()
+    virtual ~PairBuilder() {}
+    virtual int max_tiles() const = 0;
+    virtual int prepare() = 0;
+    virtual int build(int ntiles) = 0;          // the two operations of ps_pair_list_build (ps_structure.h)
+    virtual PairListCounts counts() = 0;
+    virtual int tasks(PairTasks& out) = 0;      // of the last build (moved out)
+    virtual int place_pairs() = 0;              // the pair table into the handle, if the build has not left it there already
+};
+struct ObsBuilder {
+    // the result every later stage may read (+ the handle's h_vid_of_slot)
+    std::vector<int32_t> pcount;                // nr + 1: observations on variable poses before pose r (pose order)
+    long Nl = 0, Np = 0;
+    virtual ~ObsBuilder() {}
+    virtual int slots(const std::vector<int32_t>& point_of_vid) = 0;           // landmark slots; the device-side 'vid' table
+    virtual int landmark_order(const std::vector<int32_t>& point_of_vid, const std::vector<int32_t>& class_of_row) = 0;
+    virtual int pose_order() = 0;
+    virtual int place_sidx_p() = 0;             // (wide groups) the stiffness index per observation in pose order
+    virtual int place_pobs() = 0;
+    virtual std::unique_ptr<PairBuilder> pair_builder() = 0;
+    virtual int landmark_extent(int* most, int* fewest) = 0;                   // observations per variable landmark
+    virtual int place_run_starts(int W, int nw) = 0;                           // lmw_first of the packed landmark pass
+};
+
 // scratch of one device build: freed when the build ends
 struct DevScratch {
     std::vector<void*> ptrs;
@@ -183,10 +214,11 @@ struct DevScratch {
 // The observation tables on the device: landmark slots (by first observing pose, ties by vid), observations in landmark order
 // (lobs / lorig / lm_ptr), in pose order (pobs), the per-pose counts back on the host.  Every ordering is a STABLE radix sort of
 // indices by the key the host builder's counting sorts use, so every table is the host builder's, bit for bit.
-struct DevObsBuild {
+struct DevObsBuild : ObsBuilder {
+    ps_problem* h;
+    const ps_problem_desc *d, *src;
     DevScratch scratch;
-    std::vector<int32_t> pcount;                // nr + 1: observations on variable poses before pose r (pose order)
-    long Nl = 0, Np = 0;
+    DevObsBuild(ps_problem* h_, const ps_problem_desc* d_, const ps_problem_desc* src_) : h(h_), d(d_), src(src_) {}
     static int bits_for(uint64_t maxval) { int b = 1; while (b < 32 && (maxval >> b)) ++b; return b; }
     template <typename T>
     int input(ps_problem* h, const T* host_or_dev, bool resident, size_t n, const T** out) {
@@ -199,8 +231,9 @@ struct DevObsBuild {
     }
     // d: the descriptor with HOST tables (staged if the caller's were resident); src: the caller's own descriptor (its obs_* are
     // device pointers when PS_DESC_DEVICE_TABLES is set: used where they lie)
-    int run(ps_problem* h, const ps_problem_desc* d, const ps_problem_desc* src, int nr, int nv, const std::vector<int32_t>& point_of_vid,
-            std::vector<int32_t>& vid_of_slot) {
+    int run(const std::vector<int32_t>& point_of_vid) {
+        std::vector<int32_t>& vid_of_slot = h->h_vid_of_slot;
+        const int nr = h->nr, nv = h->nv;
         const long N = h->N;
         const int P = h->P, L = h->L;
         const bool res = (src->flags & PS_DESC_DEVICE_TABLES) != 0;
@@ -257,17 +290,40 @@ struct DevObsBuild {
         HIP_OK(hipStreamSynchronize(st));           // (the scratch is freed when this object goes)
         return 0;
     }
+    int slots(const std::vector<int32_t>&) override { return 0; }
+    int landmark_order(const std::vector<int32_t>& point_of_vid, const std::vector<int32_t>&) override {
+        return (h->arena_flush() || run(point_of_vid)) ? -1 : 0;
+    }
+    int pose_order() override { return 0; }
+    int place_sidx_p() override { return 0; }
+    int place_pobs() override { return 0; }
+    std::unique_ptr<PairBuilder> pair_builder() override;
+    int landmark_extent(int* most, int* fewest) override {
+        int32_t init[2] = {0, INT_MAX}, *d_mm = nullptr;
+        if (h->alloc(&d_mm, 2, true)) return -1;
+        HIP_OK(hipMemcpyAsync(d_mm, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(k_lmw_maxobs, dim3(cdiv(h->nv, 256)), dim3(256), 0, h->stream, h->nv, h->lm_ptr, d_mm);
+        HIP_OK(hipMemcpyAsync(init, d_mm, sizeof(init), hipMemcpyDeviceToHost, h->stream));
+        HIP_OK(hipStreamSynchronize(h->stream));
+        *most = init[0]; *fewest = init[1];
+        return 0;
+    }
+    int place_run_starts(int W, int nw) override {
+        if (h->alloc(&h->lmw_first, (size_t)nw + 1, true)) return -1;
+        hipLaunchKernelGGL(k_lmw_items, dim3(cdiv(nw + 1, 256)), dim3(256), 0, h->stream, h->nv, nw, W, h->lm_ptr, h->lmw_first);
+        return 0;
+    }
 };
 
-// The gather kernels' pair list on the device.  In: the handle's lobs / lm_ptr / pose_rid tables (on the device: the caller has
-// flushed the arena).  prepare(): row rids, pair counts, their scan -> total.  build(ntiles): keys + values, stable sort, values
+// The gather kernels' pair list on the device.  In: the handle's lobs / lm_ptr / pose_rid tables (on the device: prepare()
+// flushes the arena).  prepare(): row rids, pair counts, their scan -> total.  build(ntiles): keys + values, stable sort, values
 // into `pairs`, task starts and keys back on the host (task = run of equal (tile, block) keys).
-struct DevPairBuild {
-    ps_problem* h = nullptr;
+struct DevPairBuild : PairBuilder {
+    ps_problem* h;
     DevScratch scratch;
-    int nv = 0, nr = 0;
-    long nrows = 0;
-    long long total = 0;
+    int nv, nr;
+    long nrows;
+    uint64_t* pairs_out = nullptr;              // the handle's pair table (total pairs x 8 B), taken at the first build()
     int32_t* rid_row = nullptr;
     long long *cnt = nullptr, *before = nullptr;
     void* tmp = nullptr; size_t tmp_bytes = 0;
@@ -279,8 +335,12 @@ struct DevPairBuild {
     std::vector<int32_t> task_start, task_tile;
     std::vector<uint64_t> task_key;             // (lower reduced pose << 32) | higher
 
-    int prepare(ps_problem* h_, int nv_, int nr_, long nrows_) {
-        h = h_; nv = nv_; nr = nr_; nrows = nrows_;
+    DevPairBuild(ps_problem* h_, long nrows_) : h(h_), nv(h_->nv), nr(h_->nr), nrows(nrows_) {}
+    // (a device build leaves no observation tables on the host, so there is no host pair builder to fall back to: 65 536 tiles
+    //  = 590 GB of Z rows, not reachable)
+    int max_tiles() const override { return 65535; }
+    int prepare() override {
+        if (h->arena_flush()) return -1;
         if (scratch.get(&rid_row, (size_t)nrows) || scratch.get(&cnt, (size_t)nv + 1) || scratch.get(&before, (size_t)nv + 1)) return -1;
         tmp_bytes = ps_sort_tmp_bytes((size_t)nv + 1);
         void* t0 = nullptr;
@@ -298,8 +358,7 @@ struct DevPairBuild {
     static bool packed32(int ntiles, int nr) {
         return (uint64_t)ntiles * (uint64_t)nr * (uint64_t)nr <= 0xFFFFFFFFull && !ps_create_env("PS_CREATE_KEYS64");
     }
-    int reserve(uint64_t* pairs_out) {
-        (void)pairs_out;
+    int reserve() {
         if (keys) return 0;
         const size_t n = (size_t)total;
         tmp_bytes = ps_sort_tmp_bytes(n);
@@ -314,7 +373,7 @@ struct DevPairBuild {
         return 0;
     }
     template <typename K, bool PACKED>
-    int run(int ntiles, int bits, uint64_t* pairs_out) {
+    int run(int ntiles, int bits) {
         const long n = (long)total;
         K* k0 = (K*)keys; K* k1 = (K*)keys_sorted;
         hipLaunchKernelGGL((k_build_pairs<K, PACKED>), dim3(cdiv(nv, 256)), dim3(256), 0, h->stream, nv, h->lm_ptr, rid_row, before, ntiles, nr, k0, vals);
@@ -344,19 +403,34 @@ struct DevPairBuild {
         }
         return 0;
     }
-    // pairs_out: the handle's pair table (total pairs x 8 B)
-    int build(int ntiles, uint64_t* pairs_out) {
+    int build(int ntiles) override {
+        if (!pairs_out) {       // pairs generated, sorted and left in HBM; the host receives the task starts and keys only
+            if (h->alloc(&h->pairs, (size_t)total, true)) return -1;
+            pairs_out = reinterpret_cast<uint64_t*>(h->pairs);
+        }
         if (total == 0) { task_start.clear(); task_key.clear(); task_tile.clear(); return 0; }
-        if (reserve(pairs_out)) return -1;
+        if (reserve()) return -1;
         if (packed32(ntiles, nr)) {
             const uint64_t mx = (uint64_t)ntiles * (uint64_t)nr * (uint64_t)nr - 1;
             int bits = 1;
             while (bits < 32 && (mx >> bits)) ++bits;
-            return run<uint32_t, true>(ntiles, bits, pairs_out);
+            return run<uint32_t, true>(ntiles, bits);
         }
         int tb = 1;
         while ((ntiles - 1) >> tb) ++tb;
-        return run<uint64_t, false>(ntiles, 48 + tb, pairs_out);
+        return run<uint64_t, false>(ntiles, 48 + tb);
     }
+    PairListCounts counts() override {
+        if (task_tile.empty() || task_tile.back() == 0) return {(size_t)total, task_start.size(), task_start.size()};   // one tile: a task per block
+        std::vector<uint64_t> tk(task_key);
+        std::sort(tk.begin(), tk.end());
+        return {(size_t)total, task_start.size(), (size_t)(std::unique(tk.begin(), tk.end()) - tk.begin())};
+    }
+    int tasks(PairTasks& out) override {
+        out.start.swap(task_start); out.tile.swap(task_tile); out.key.swap(task_key);
+        return 0;
+    }
+    int place_pairs() override { return 0; }
 };
+std::unique_ptr<PairBuilder> DevObsBuild::pair_builder() { return std::unique_ptr<PairBuilder>(new DevPairBuild(h, Nl)); }
 }  // namespace

@@ -140,9 +140,6 @@ int read_scalars(ps_problem* h) {
     return sync(h);
 }
 
-// ---- structure building ---------------------------------------------------
-struct PairRec { uint64_t key; int32_t a, b, tile; };
-
 template <int D>
 int launch_factor_pass(ps_problem* h, double lambda, double* dbg = nullptr) {
     if (h->F == 0 && h->FH == 0) return 0;
@@ -219,14 +216,7 @@ int ensure_cg_buffers(ps_problem* h, int rows, int blocks) {
 // Coarse nodes (hat functions over the reduced-pose index) + the augmented BSR pattern
 // [[S^, K], [K^T, I]].  coarse_req = number of intervals G (ncb = G + 1 nodes).
 int build_coarse(ps_problem* h) {
-    const bool timing = ps_env("PS_CREATE_TIMING") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "build_coarse: %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
+    StageLap lap("build_coarse", ps_env("PS_CREATE_TIMING") != nullptr);
     const int nr = h->nr, D = h->D;
     {   // compute units the solver's stream may use (the one-launch solvers need their whole grid resident)
         const CuBudget cb = ps_stream_cus(h->stream);

@@ -136,6 +136,90 @@ def test_device_build_with_64_bit_pair_keys():
     assert _compare(lp2, PS_CREATE_KEYS64=1)[11] == 0
 
 
+# ---- the smallest shapes at which a boundary between two stages of ps_problem_create can go wrong.  Where the device build does
+# not apply (no variable landmark, no observation) mode 2 falls back to the host builder: _compare then holds two creates and
+# two iterations of the same builder against each other, i.e. asserts that they succeed and agree.
+def _keep_observations(lp, keep):
+    for name in ('obs_pose', 'obs_point', 'obs_grp', 'obs_uvd'):
+        setattr(lp, name, getattr(lp, name)[keep])
+
+
+def test_create_with_one_variable_pose():
+    """nr = 1: no Schur pair at all, a reduced system of one block."""
+    from pyslam_amd import synthetic
+    lp, _ = synthetic.stereo_ba(num_kf=6, num_lm=64, obs_per_lm=4, half_window=3, seed=21)
+    rid = np.full(6, -1, np.int32)
+    rid[3] = 0
+    lp.pose_rid = rid
+    _compare(lp)
+    host = _build(lp, 0)
+    try:
+        assert (host.info['num_pairs'], host.info['reduced_nnzb'], host.nr) == (0, 1, 1)
+    finally:
+        host.close()
+
+
+def test_create_with_every_landmark_constant():
+    """nv = 0, N > 0: no Z row, no landmark table; the poses are held by the constant landmarks alone."""
+    from pyslam_amd import synthetic
+    lp, _ = synthetic.stereo_ba(num_kf=6, num_lm=64, obs_per_lm=4, half_window=3, seed=22)
+    lp.point_vid = np.full(64, -1, np.int32)
+    _compare(lp)
+    host = _build(lp, 2)
+    try:
+        assert (host.nv, host.info['num_pairs'], host.nr) == (0, 0, 5)
+    finally:
+        host.close()
+
+
+def test_create_with_every_observed_pose_constant_but_one():
+    """Poses 1 .. 4 observe and are constant, pose 5 observes and is variable, poses 0 and 6 .. 9 are variable and held by pose
+    edges only: pose segments of length zero on either side of the one that has observations."""
+    from pyslam_amd import synthetic
+    lp, truth = synthetic.stereo_ba(num_kf=10, num_lm=120, obs_per_lm=4, half_window=3, seed=23, const_first_pose=False)
+    lp = synthetic.with_pose_edges(lp, 4, seed=5, truth_poses=truth['poses'])
+    _keep_observations(lp, (lp.obs_pose >= 1) & (lp.obs_pose <= 5))
+    const = np.zeros(10, bool)
+    const[1:5] = True
+    rid = np.full(10, -1)
+    rid[~const] = np.arange(6)
+    lp.pose_rid = rid.astype(np.int32)
+    seen = np.zeros(120, bool)                              # a landmark that lost every observation is held constant
+    seen[lp.obs_point] = True
+    lp.point_vid = np.where(seen, np.cumsum(seen) - 1, -1).astype(np.int32)
+    assert seen.any()
+    _compare(lp)
+    dev = _build(lp, 2)
+    try:
+        assert dev.nr == 6 and dev.info['num_pairs'] == 0
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize('most,kf', [(64, 64), (16, 17)])
+def test_create_with_one_observation_beside_the_packed_run_limit(most, kf):
+    """A landmark with a single observation next to landmarks with `most`: 64 is more than a packed run holds (PS_LMW_MAXOBS = 16:
+    no runs are built, the unpacked landmark pass runs), 16 is the most it holds (runs of 64 - 15 = 49 rows, the shortest).
+    (Every landmark is seen from nearly every keyframe, so that every pose is held by several.)"""
+    from pyslam_amd import synthetic
+    lp, _ = synthetic.stereo_ba(num_kf=kf, num_lm=12, obs_per_lm=most, half_window=kf, seed=24)
+    assert np.bincount(lp.obs_point).tolist() == [most] * 12
+    mine = np.nonzero((lp.obs_point == 1) & (lp.obs_pose > 0))[0]
+    keep = lp.obs_point != 1
+    keep[mine[0]] = True
+    _keep_observations(lp, keep)
+    assert sorted(np.bincount(lp.obs_point).tolist()) == [1] + [most] * 11
+    _compare(lp)
+
+
+@pytest.mark.parametrize('dof', [6, 3])
+def test_create_of_a_pose_graph(dof):
+    """N = 0: no observation table, no landmark, no pair; factor lists only."""
+    from pyslam_amd import synthetic
+    lp, _ = synthetic.pose_graph(num_poses=12, num_loops=6, dof=dof, seed=25)
+    _compare(lp)
+
+
 @pytest.mark.parametrize('kf,lm', [(200, 50000), (2000, 500000)])
 def test_device_build_at_the_baseline_sizes_is_the_host_builders(kf, lm):
     """C3 (untiled, 2.2 M pairs) and C4 (72 landmark tiles, 22.5 M pairs, 29-bit packed keys): every structure table of the default
