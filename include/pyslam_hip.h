@@ -574,6 +574,31 @@ int ps_sparse_normal_direct(int32_t m, int32_t n, const int32_t* j_row_ptr, cons
  * Stands in for the coarse-level part of scipy.sparse.linalg.spsolve (reference pyslam/problem.py:186); test and measurement entry. */
 int ps_debug_band_inverse(const double* a, int32_t ncb, int32_t dof, int32_t bw, int32_t chunk_nodes, float* ainv_out,
                           double* elapsed_us);
+/* The lagged dense inverse's kernels on their own (csrc/ps_k_ldi.h; option "lagged_inverse"): test entries that run the
+ * production kernels and change nothing in them; no production path calls them.
+ * ps_debug_ldi_gemm: C = alpha A B + beta Dm + gamma I by the fp32 MFMA product k_ldi_gemm, launched exactly as the Newton-Schulz
+ *   steps launch it.  Host arrays, row-major: A (M x lda), B (K x ldb), Dm (M x ldd, or NULL; may be the pointer A itself: the
+ *   device copies alias as well), C (M x ldc; its contents go in, tiles the kernel leaves alone come back unchanged).  krange (or
+ *   NULL): [k_lo, k_hi) per 32-row tile, 2 (M / 32) ints.  upper_only: tiles below the diagonal stay untouched.  dev_scale (or NULL):
+ *   one float that multiplies alpha and gamma on the device.  fro_part (or NULL): (M / 32) (N / 32) doubles, pre-filled with
+ *   fro_sentinel, the sum of squares of every tile written.  Refused before any launch: M or N not a multiple of 32, K or a
+ *   krange bound not a multiple of 16, a leading dimension below its extent or (lda, ldb) not a multiple of 4.
+ * ps_debug_ldi_ritz: the seed scale kernel k_ldi_ritz on rz[k] = r_k . z_k and alpha[k], k < m, of a CG of m iterations (the first
+ *   64 are used).  out3 = c, ritz_min, ritz_max; all zero when there is no usable estimate.
+ * ps_debug_ldi_read: one item of a live handle's inverse as doubles, after waiting for every stream that writes it; the state
+ *   machine does not move.  PS_LDI_READ_STATE (12 doubles: state [0 none, 1 seed in flight, 2 valid, 3 valid + refresh in flight],
+ *   buffer in use or -1, n, np, kp, direct seed 0 / 1, the residual bound the inverse in flight / in use was accepted under, CG
+ *   iterations of the last solve with it, "ldi_seed_steps", block rows, dof, buffers allocated 0 / 1) always answers; every other
+ *   item is an error until an inverse has been seeded: S32, X32, XU (the buffer in use), np x np; XT np x kp; LINV block rows x
+ *   dof x dof (the frozen factors); COEF 3; FRO 1 (||I - S^ X||_F^2 of the last step); R, Z: n (the residual the last k_ldi_init /
+ *   k_ldi_update stored and z = X_u r, valid straight after a call that solved with the inverse). */
+enum { PS_LDI_READ_STATE = 0, PS_LDI_READ_S32 = 1, PS_LDI_READ_X32 = 2, PS_LDI_READ_XU = 3, PS_LDI_READ_XT = 4, PS_LDI_READ_LINV = 5,
+       PS_LDI_READ_COEF = 6, PS_LDI_READ_FRO = 7, PS_LDI_READ_R = 8, PS_LDI_READ_Z = 9 };
+int ps_debug_ldi_gemm(int32_t M, int32_t N, int32_t K, float alpha, const float* A, int32_t lda, const float* B, int32_t ldb, float beta,
+                      const float* Dm, int32_t ldd, float gamma, float* C, int32_t ldc, const int32_t* krange, int32_t upper_only,
+                      const float* dev_scale, double fro_sentinel, double* fro_part);
+int ps_debug_ldi_ritz(const double* rz, const double* alpha, int32_t m, float* out3);
+int ps_debug_ldi_read(ps_problem* h, int32_t what, double* out, int64_t capacity);
 /* Stress entry behind DESIGN.md section 3 "side stream" (round 6; test and measurement infrastructure): the coarse level's
  * factorisation kernels run `launches` times on a stream of their own -- lowest priority if `lowprio` -- while, if `aggressor`,
  * streaming copy kernels keep an ordinary stream busy; every output is compared bit for bit with one produced on an idle device.

@@ -503,3 +503,84 @@ int ps_debug_band_inverse(const double* a, int32_t ncb, int32_t dof, int32_t bw,
     if (stw[ST_DIAG_FAIL]) return fail("band factorisation: the matrix is not positive definite");
     return 0;
 }
+
+// ---- the lagged dense inverse's kernels on their own (csrc/ps_k_ldi.h; tests/test_gpu_ldi_kernels.py) -----------------------------
+// C = alpha A B + beta Dm + gamma I by k_ldi_gemm, launched through ldi_gemm() like every production product.  Host arrays in
+// (A: M x lda, B: K x ldb, Dm: M x ldd or NULL, C: M x ldc with the caller's initial contents), C and the per-tile Frobenius
+// parts out (fro_part: (M / 32) (N / 32) doubles pre-filled with fro_sentinel, or NULL).  Dm may be the very pointer A (or B):
+// the device copies alias then too, as in ldi_ns_step.  krange: 2 (M / 32) ints or NULL; dev_scale: one float or NULL.
+int ps_debug_ldi_gemm(int32_t M, int32_t N, int32_t K, float alpha, const float* A, int32_t lda, const float* B, int32_t ldb, float beta,
+                      const float* Dm, int32_t ldd, float gamma, float* C, int32_t ldc, const int32_t* krange, int32_t upper_only,
+                      const float* dev_scale, double fro_sentinel, double* fro_part) {
+    if (!A || !B || !C) return fail("ps_debug_ldi_gemm: null argument");
+    if (M <= 0 || N <= 0 || K <= 0 || M % PS_GM_BM || N % PS_GM_BN) return fail("ps_debug_ldi_gemm: M and N must be positive multiples of 32");
+    if (K % PS_GM_BK) return fail("ps_debug_ldi_gemm: K must be a multiple of 16");
+    if (lda < K || ldb < N || ldc < N || (Dm && ldd < N)) return fail("ps_debug_ldi_gemm: a leading dimension is smaller than its extent");
+    if (lda % 4 || ldb % 4) return fail("ps_debug_ldi_gemm: lda and ldb must be multiples of 4 (16-byte loads)");
+    if (beta != 0.f && !Dm) return fail("ps_debug_ldi_gemm: beta != 0 needs Dm");
+    if (upper_only && M != N) return fail("ps_debug_ldi_gemm: upper_only needs a square C");
+    const int mt = M / PS_GM_BM, nt = N / PS_GM_BN;
+    if (krange)
+        for (int t = 0; t < mt; ++t) {
+            const int lo = krange[2 * t], hi = krange[2 * t + 1];
+            if (lo < 0 || hi > K || lo > hi || lo % PS_GM_BK || hi % PS_GM_BK) return fail("ps_debug_ldi_gemm: krange bounds must be multiples of 16 with 0 <= lo <= hi <= K");
+        }
+    if (need_device()) return -1;
+    DevBuf bA, bB, bD, bC, bF, bK, bS;
+    const size_t na = (size_t)M * lda, nb = (size_t)K * ldb, nd = (size_t)M * ldd, nc = (size_t)M * ldc;
+    if (bA.get(na * 4) || bB.get(nb * 4) || bC.get(nc * 4)) return -1;
+    HIP_OK(hipMemcpy(bA.p, A, na * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(bB.p, B, nb * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(bC.p, C, nc * 4, hipMemcpyHostToDevice));
+    const float* dD = nullptr;
+    if (Dm == A && ldd == lda) dD = bA.as<float>();
+    else if (Dm == B && ldd == ldb && M == K) dD = bB.as<float>();
+    else if (Dm) {
+        if (bD.get(nd * 4)) return -1;
+        HIP_OK(hipMemcpy(bD.p, Dm, nd * 4, hipMemcpyHostToDevice));
+        dD = bD.as<float>();
+    }
+    if (fro_part) {
+        std::vector<double> f((size_t)mt * nt, fro_sentinel);
+        if (bF.get(f.size() * 8)) return -1;
+        HIP_OK(hipMemcpy(bF.p, f.data(), f.size() * 8, hipMemcpyHostToDevice));
+    }
+    if (krange) {
+        if (bK.get((size_t)mt * sizeof(int2))) return -1;
+        HIP_OK(hipMemcpy(bK.p, krange, (size_t)mt * sizeof(int2), hipMemcpyHostToDevice));
+    }
+    if (dev_scale) {
+        if (bS.get(4)) return -1;
+        HIP_OK(hipMemcpy(bS.p, dev_scale, 4, hipMemcpyHostToDevice));
+    }
+    ldi_gemm(nullptr, 0, M, N, K, alpha, bA.as<float>(), lda, bB.as<float>(), ldb, beta, dD, ldd, gamma, bC.as<float>(), ldc,
+             fro_part ? bF.as<double>() : nullptr, krange ? bK.as<int2>() : nullptr, upper_only ? 1 : 0, dev_scale ? bS.as<float>() : nullptr);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(0));
+    HIP_OK(hipMemcpy(C, bC.p, nc * 4, hipMemcpyDeviceToHost));
+    if (fro_part) HIP_OK(hipMemcpy(fro_part, bF.p, (size_t)mt * nt * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// k_ldi_ritz once on the coefficients of a CG of m iterations: rz[k] = r_k . z_k and alpha[k], what the solver's CG leaves in
+// hist[k] and hist[cap + k].  out3: c = 1.9 / (ritz_min + ritz_max) and the two Ritz values (all zero: no usable estimate).
+int ps_debug_ldi_ritz(const double* rz, const double* alpha, int32_t m, float* out3) {
+    if (!out3 || m < 0 || (m > 0 && (!rz || !alpha))) return fail("ps_debug_ldi_ritz: bad argument");
+    if (need_device()) return -1;
+    const int cap = std::max(m, 1);
+    std::vector<double> hist(2 * (size_t)cap, 0.0);
+    for (int k = 0; k < m; ++k) { hist[k] = rz[k]; hist[cap + k] = alpha[k]; }
+    int32_t stw[ST_NWORDS] = {};
+    stw[ST_PCG_ITERS] = m;
+    const float before[3] = {-1.f, -1.f, -1.f};               // (the kernel writes all three words whatever it finds)
+    DevBuf bh, bs, bo;
+    if (bh.get(hist.size() * 8) || bs.get(sizeof(stw)) || bo.get(sizeof(before))) return -1;
+    HIP_OK(hipMemcpy(bh.p, hist.data(), hist.size() * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(bs.p, stw, sizeof(stw), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(bo.p, before, sizeof(before), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_ldi_ritz, dim3(1), dim3(64), 0, 0, (const double*)bh.as<double>(), cap, (const int32_t*)bs.as<int32_t>(), bo.as<float>());
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(0));
+    HIP_OK(hipMemcpy(out3, bo.p, sizeof(before), hipMemcpyDeviceToHost));
+    return 0;
+}

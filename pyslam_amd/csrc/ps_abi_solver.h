@@ -896,6 +896,52 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
     return 0;
 }
 
+// What the lagged dense inverse of a live handle holds (csrc/ps_host_ldi.h; tests/test_gpu_ldi_kernels.py), as doubles (the
+// fp32 matrices convert exactly).  Waits for the solver stream, the side stream and the direct seed's stream / ev_ldi, copies,
+// and touches nothing: the state machine, the counters and the schedule are where they were.
+int ps_debug_ldi_read(ps_problem* h, int32_t what, double* out, int64_t capacity) {
+    if (!h || !out) return fail("null argument");
+    if (what == PS_LDI_READ_STATE) {
+        if (capacity < 12) return fail("ps_debug_ldi_read: state record needs 12 doubles");
+        const double rec[12] = {(double)h->ldi_state, (double)h->ldi_cur, (double)h->ldi_n, (double)h->ldi_np, (double)h->ldi_kp,
+                                h->ldi_direct ? 1.0 : 0.0, h->ldi_fro_limit, (double)h->ldi_last_its, (double)h->ldi_seed_steps,
+                                (double)h->nr, (double)h->D, h->ldi_ready ? 1.0 : 0.0};
+        std::memcpy(out, rec, sizeof(rec));
+        return 0;
+    }
+    if (!h->ldi_ready || h->ldi_seeds < 1) return fail("ps_debug_ldi_read: the lagged inverse has never been set up on this handle");
+    HIP_OK(hipStreamSynchronize(h->stream));
+    if (h->side) HIP_OK(hipStreamSynchronize(h->side));
+    if (h->ldi_stream) HIP_OK(hipStreamSynchronize(h->ldi_stream));
+    if (h->ev_ldi) HIP_OK(hipEventSynchronize(h->ev_ldi));
+    const size_t n = (size_t)h->ldi_n, np = (size_t)h->ldi_np, kp = (size_t)h->ldi_kp;
+    const void* src = nullptr; size_t count = 0; bool f32 = true;
+    const bool seed_item = what == PS_LDI_READ_S32 || what == PS_LDI_READ_X32 || what == PS_LDI_READ_XT || what == PS_LDI_READ_LINV ||
+                           what == PS_LDI_READ_COEF;
+    if (seed_item && h->ldi_direct) return fail("ps_debug_ldi_read: the direct seed keeps no Newton-Schulz operands");
+    const bool use_item = what == PS_LDI_READ_XU || what == PS_LDI_READ_R || what == PS_LDI_READ_Z;
+    if (use_item && h->ldi_cur < 0) return fail("ps_debug_ldi_read: no inverse is in use");
+    switch (what) {
+        case PS_LDI_READ_S32: src = h->ldi_S32; count = np * np; break;
+        case PS_LDI_READ_X32: src = h->ldi_X32; count = np * np; break;
+        case PS_LDI_READ_XU: src = h->ldi_Xu[h->ldi_cur]; count = np * np; break;
+        case PS_LDI_READ_XT: src = h->ldi_Xt; count = np * kp; break;
+        case PS_LDI_READ_LINV: src = h->ldi_Linv; count = (size_t)h->nr * h->D * h->D; f32 = false; break;
+        case PS_LDI_READ_COEF: src = h->ldi_coef; count = 3; break;
+        case PS_LDI_READ_FRO: if (capacity < 1) return fail("ps_debug_ldi_read: capacity"); out[0] = *h->h_ldi_fro; return 0;
+        // the residual the last k_ldi_init (no iteration) / k_ldi_update (iteration m - 1 writes buffer m & 1) stored, and z = X_u r
+        case PS_LDI_READ_R: src = h->ldi_r[h->ldi_last_its & 1]; count = n; f32 = false; break;
+        case PS_LDI_READ_Z: src = h->z; count = n; f32 = false; break;
+        default: return fail("ps_debug_ldi_read: unknown item");
+    }
+    if ((size_t)capacity < count) return fail("ps_debug_ldi_read: capacity too small");
+    if (!f32) { HIP_OK(hipMemcpy(out, src, count * 8, hipMemcpyDeviceToHost)); return 0; }
+    std::vector<float> tmp(count);
+    HIP_OK(hipMemcpy(tmp.data(), src, count * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < count; ++i) out[i] = (double)tmp[i];
+    return 0;
+}
+
 // the folded / explicit crossover depends on whether the lagged dense inverse can apply (ps_host_cg.h: build_coarse): an
 // option that changes that answer has the coarse level rebuilt by the next solve
 static void relook_path(ps_problem* h) {

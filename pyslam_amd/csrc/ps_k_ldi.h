@@ -235,6 +235,9 @@ __global__ __launch_bounds__(256) void k_ldi_seed_prep(int n, int nc, int np, in
 
 // X32 <- sym(T) on the real blocks (+ the padding diagonal), and Xu <- L_i^-T X_ij L_j^-1: the unscaled fp32 inverse the
 // solver stream applies.  One wave per block (bi, bj).
+// X32 comes out exactly symmetric (tests/test_gpu_ldi_kernels.py holds it to that).  Xu is NOT promised to be: block (bi, bj)
+// and block (bj, bi) are two fp64 triple products summed in different orders and rounded to fp32 separately, so
+// |Xu - Xu^T| <= 2^-23 |Xu| per entry -- one fp32 unit, far below what the preconditioned CG notices.
 template <int D>
 __global__ __launch_bounds__(64) void k_ldi_sym_unscale(
     int nr, int np, const float* __restrict__ T, const double* __restrict__ Linv, float* __restrict__ X32,

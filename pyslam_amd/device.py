@@ -451,6 +451,24 @@ class DeviceProblem:
         nat.check(self._lib.ps_debug_factor_blocks(self._h, nat.f64p(r), nat.f64p(j1), nat.f64p(j2)))
         return r, j1, j2
 
+    def debug_ldi_state(self):
+        """State record of the lagged dense inverse (include/pyslam_hip.h: ps_debug_ldi_read, PS_LDI_READ_STATE)."""
+        rec = np.zeros(12)
+        nat.check(self._lib.ps_debug_ldi_read(self._h, 0, nat.f64p(rec), rec.size))
+        keys = ('state', 'cur', 'n', 'np', 'kp', 'direct', 'fro_limit', 'last_its', 'seed_steps', 'nr', 'dof', 'ready')
+        return {k: (float(v) if k == 'fro_limit' else int(v)) for k, v in zip(keys, rec)}
+
+    def debug_ldi_read(self, what):
+        """One item of the lagged dense inverse as float64 (the fp32 matrices convert exactly): 'S32', 'X32', 'Xu', 'Xt',
+        'Linv', 'coef', 'fro', 'r', 'z' (ps_debug_ldi_read).  Raises until an inverse has been seeded."""
+        s = self.debug_ldi_state()
+        n, npad, kp, nr, d = s['n'], s['np'], s['kp'], s['nr'], s['dof']
+        code, shape = {'S32': (1, (npad, npad)), 'X32': (2, (npad, npad)), 'Xu': (3, (npad, npad)), 'Xt': (4, (npad, kp)),
+                       'Linv': (5, (nr, d, d)), 'coef': (6, (3,)), 'fro': (7, (1,)), 'r': (8, (n,)), 'z': (9, (n,))}[what]
+        out = np.zeros(max(int(np.prod(shape)), 1))
+        nat.check(self._lib.ps_debug_ldi_read(self._h, code, nat.f64p(out), out.size))
+        return out[:int(np.prod(shape))].reshape(shape)
+
     def get_info(self):
         """ps_problem_info as a dict, read now (sizes, and the solver counters: restarts, launches, lagged-inverse and
         one-launch-PCG statistics)."""
@@ -524,6 +542,41 @@ def band_inverse(A, ncb, dof, bw, chunk_nodes=0):
     nat.check(lib.ps_debug_band_inverse(nat.f64p(A), ncb, dof, bw, chunk_nodes, out.ctypes.data_as(C.POINTER(C.c_float)),
                                         C.cast(C.byref(us), nat.c_f64p)))
     return out, us.value
+
+
+def ldi_gemm(A, B, C0, M, N, K, alpha=1.0, beta=0.0, Dm=None, gamma=0.0, lda=None, ldb=None, ldd=None, ldc=None, krange=None,
+             upper_only=False, dev_scale=None, fro_sentinel=None, need_gpu=True):
+    """C = alpha A B + beta Dm + gamma I by the lagged inverse's fp32 MFMA product (include/pyslam_hip.h: ps_debug_ldi_gemm).
+    A, B, C0 (and Dm): contiguous float32 arrays of M x lda, K x ldb, M x ldc (M x ldd); Dm may be the object A itself (the device
+    copies alias then).  -> (C, fro_part or None); fro_part is asked for by giving fro_sentinel."""
+    lib = nat.require_gpu() if need_gpu else nat.load()
+    f32p = C.POINTER(C.c_float)
+    lda, ldb, ldc = lda or K, ldb or N, ldc or N
+    ldd = ldd or (lda if Dm is A else N)
+    for a in (A, B, C0) + (() if Dm is None else (Dm,)):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+    out = C0.copy()
+    mt, nt = max(M // 32, 1), max(N // 32, 1)
+    fro = None if fro_sentinel is None else np.zeros((mt, nt))
+    kr = None if krange is None else np.ascontiguousarray(krange, dtype=np.int32).reshape(-1)
+    sc = None if dev_scale is None else np.array([dev_scale], dtype=np.float32)
+    nat.check(lib.ps_debug_ldi_gemm(M, N, K, alpha, A.ctypes.data_as(f32p), lda, B.ctypes.data_as(f32p), ldb, beta,
+                                    None if Dm is None else Dm.ctypes.data_as(f32p), ldd, gamma, out.ctypes.data_as(f32p), ldc,
+                                    nat.i32p(kr), int(bool(upper_only)), None if sc is None else sc.ctypes.data_as(f32p),
+                                    0.0 if fro_sentinel is None else float(fro_sentinel), nat.f64p(fro)))
+    return out, fro
+
+
+def ldi_ritz(rz, alpha, m=None):
+    """(c, ritz_min, ritz_max) as float32 from the seed-scale kernel k_ldi_ritz on a CG's coefficients (ps_debug_ldi_ritz)."""
+    lib = nat.require_gpu()
+    rz = np.ascontiguousarray(rz, dtype=np.float64)
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+    m = min(rz.size, alpha.size) if m is None else m
+    assert m <= rz.size and m <= alpha.size
+    out = np.full(3, -1.0, dtype=np.float32)
+    nat.check(lib.ps_debug_ldi_ritz(nat.f64p(rz), nat.f64p(alpha), m, out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
 
 
 class NotConverged(nat.NativeError):
