@@ -835,6 +835,23 @@ int ps_feat_read_map_matches(ps_feat* h, int32_t num_points, int32_t* feature, i
    ps_feat_read_map_second fails unless the last map match was a global one. */
 int ps_feat_match_map_global(ps_feat* h, int32_t ratio_num, int32_t ratio_den, const ps_feat_params* params, int32_t* num_matched);
 int ps_feat_read_map_second(ps_feat* h, int32_t num_points, int32_t* second);
+/* The keyframe database (step 10 of the definition): an ordered list of entries, each num >= 0 descriptors of 32 bytes as
+   ps_feat_read_features returns them.  ps_feat_db_add appends one entry and returns its index (num = 0 is allowed, descriptors may
+   then be null; the caller's array is free on return); entries are never edited, ps_feat_db_clear empties the list and keeps the
+   buffers.  At most 65536 entries and 2^22 descriptors.  Nothing is allocated before the first ps_feat_db_add; the buffers grow by
+   doubling and are counted in ps_feat_device_bytes.
+   ps_feat_db_query computes the features of the current frame's left image if it has none under `params` and writes
+   scores[e - first], first <= e < last: the number of descriptors of entry e whose best cost over all features is at most
+   match_cost_max and, where the frame has a second feature, satisfies ratio_den * best < ratio_num * second-best (what
+   ps_feat_match_map_global gives status 0 or 3).  It counts descriptors of the entry, not distinct features of the frame.  One
+   memset, one launch, one copy of last - first ints, one wait; two calls give the same bits.  first == last is a query of
+   nothing.  Fails on a range outside 0 <= first <= last <= entries, on a ratio outside 0 < num <= den <= 32768, and without a
+   pushed frame. */
+int ps_feat_db_add(ps_feat* h, int32_t num, const uint8_t* descriptors, int32_t* entry);
+int ps_feat_db_clear(ps_feat* h);
+int ps_feat_db_size(ps_feat* h, int32_t* entries, int64_t* descriptors);
+int ps_feat_db_query(ps_feat* h, int32_t first, int32_t last, int32_t ratio_num, int32_t ratio_den, const ps_feat_params* params,
+                     int32_t* scores);
 /* number of images whose features were computed since create (a recognised frame adds none) */
 int ps_feat_feature_passes(ps_feat* h, int64_t* passes);
 int ps_feat_device_bytes(ps_feat* h, int64_t* bytes);

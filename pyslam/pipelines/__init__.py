@@ -7,3 +7,4 @@ from pyslam_amd.pipelines.keyframes import (Keyframe, DenseKeyframe, DenseRGBDKe
                                             SparseStereoKeyframe, SparseRGBDKeyframe)
 from pyslam_amd.pipelines.sparse import SparseVOPipeline, SparseStereoPipeline, SparseRGBDPipeline  # noqa: F401
 from pyslam_amd.pipelines.mono import track_frame, relocalise_frame, SparseMonoPipeline, SparseMonoKeyframe  # noqa: F401
+from pyslam_amd.pipelines.loop import loop_candidates, verify_loop, detect_loop  # noqa: F401

@@ -190,6 +190,10 @@ SIGNATURES = {
     'ps_feat_read_map_matches': (C.c_int, [H, C.c_int32, c_i32p, c_i32p, c_i32p, c_f64p]),
     'ps_feat_match_map_global': (C.c_int, [H, C.c_int32, C.c_int32, C.POINTER(FeatParams), c_i32p]),
     'ps_feat_read_map_second': (C.c_int, [H, C.c_int32, c_i32p]),
+    'ps_feat_db_add': (C.c_int, [H, C.c_int32, c_u8p, c_i32p]),
+    'ps_feat_db_clear': (C.c_int, [H]),
+    'ps_feat_db_size': (C.c_int, [H, c_i32p, C.POINTER(C.c_int64)]),
+    'ps_feat_db_query': (C.c_int, [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(FeatParams), c_i32p]),
     'ps_feat_feature_passes': (C.c_int, [H, C.POINTER(C.c_int64)]),
     'ps_feat_device_bytes': (C.c_int, [H, C.POINTER(C.c_int64)]),
     'ps_dense_normal_solve': (C.c_int, [c_f64p, c_f64p, C.c_int32, C.c_int32, c_f64p, c_f64p]),

@@ -8,7 +8,12 @@
 // stream with one synchronisation at its end.  The one exception is the map of matching by projection (ps_feat_set_map,
 // step 8 of the definition): its buffers are allocated at the first ps_feat_set_map and grow with the map, so a handle
 // that never sets one holds exactly what it was created with.  Likewise the second-best costs of matching without a prior
-// (ps_feat_match_map_global, step 9): the map's result block has room for them from the first such match on.
+// (ps_feat_match_map_global, step 9): the map's result block has room for them from the first such match on.  And the keyframe
+// database (ps_feat_db_*, step 10; kernel in csrc/ps_k_feat_db.h): nothing of it exists before the first ps_feat_db_add, and its
+// buffers grow by doubling.
+
+#define PS_FEAT_DB_MAX_ENTRIES 65536
+#define PS_FEAT_DB_MAX_DESC (1 << 22)
 
 extern "C++" {
 struct PsFeatImage {
@@ -60,6 +65,33 @@ struct ps_feat {
     unsigned long long* map_claim = nullptr;
     std::vector<void*> map_allocs;          // the buffers that grow with the map
     int64_t map_bytes = 0;
+    // the keyframe database (step 10): entries are appended, never edited; nothing of it exists before the first ps_feat_db_add
+    std::vector<int> db_start, db_len, db_block;   // per entry: first descriptor, length, first workgroup (db_block has K + 1 values)
+    int64_t db_n = 0, db_desc_cap = 0, db_bytes = 0;       // descriptors held, room for
+    int db_block_cap = 0, db_entry_cap = 0;
+    uint32_t* db_desc = nullptr;
+    FeatDbBlock* db_blocks = nullptr;
+    int *db_estart = nullptr, *db_elen = nullptr, *db_score = nullptr;
+    std::vector<void*> db_allocs;
+    // room for n values where there was room for `cap` (doubling), the first `used` kept: the stream is idle when this is called
+    template <typename T> int grow_db(T** p, int64_t used, int64_t cap, int64_t n, int64_t first_cap, int64_t* new_cap) {
+        int64_t c = cap ? cap : first_cap;
+        while (c < n) c *= 2;
+        *new_cap = c;
+        if (c == cap) return 0;
+        T* q = nullptr;
+        if (hipMalloc((void**)&q, (size_t)c * sizeof(T)) != hipSuccess) return fail("hipMalloc failed");
+        if (used && hipMemcpy(q, *p, (size_t)used * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) { hipFree(q); return fail("hipMemcpy failed"); }
+        if (*p) {
+            hipFree(*p);
+            db_allocs.erase(std::find(db_allocs.begin(), db_allocs.end(), (void*)*p));
+        }
+        db_allocs.push_back((void*)q);
+        const int64_t d = (c - cap) * (int64_t)sizeof(T);
+        db_bytes += d; bytes += d;
+        *p = q;
+        return 0;
+    }
     int alloc_bytes(void** p, size_t b) {
         if (hipMalloc(p, std::max<size_t>(b, 16)) != hipSuccess) return fail("hipMalloc failed");
         allocs.push_back(*p);
@@ -92,7 +124,7 @@ struct ps_feat {
         }
         return 0;
     }
-    ~ps_feat() { for (void* p : map_allocs) hipFree(p); for (void* p : allocs) hipFree(p); }
+    ~ps_feat() { for (void* p : db_allocs) hipFree(p); for (void* p : map_allocs) hipFree(p); for (void* p : allocs) hipFree(p); }
 };
 }  // extern "C++"
 
@@ -396,6 +428,83 @@ int ps_feat_read_map_second(ps_feat* f, int32_t num_points, int32_t* second) {
     if (num_points < 0 || num_points > f->map_matched_n) return fail("more points asked for than the map that was matched holds");
     const size_t n = num_points, N = f->map_matched_n;
     if (n && second) memcpy(second, f->h_map_out.data() + 16 + 28 * N, n * sizeof(int));
+    return 0;
+}
+
+int ps_feat_db_add(ps_feat* f, int32_t num, const uint8_t* descriptors, int32_t* entry) {
+    if (!f || !entry) return fail("null argument");
+    *entry = -1;
+    if (num < 0) return fail("num must not be negative");
+    if (num > 0 && !descriptors) return fail("null argument");
+    const int K = (int)f->db_start.size();
+    if (K >= PS_FEAT_DB_MAX_ENTRIES) return fail("the database holds at most 65536 entries");
+    if (f->db_n + num > PS_FEAT_DB_MAX_DESC) return fail("the database holds at most 2^22 descriptors");
+    hipStream_t s = f->stream;
+    const int nb0 = K ? f->db_block.back() : 0, nb = cdiv(num, PS_FEAT_DB_BLOCK);
+    int64_t dc = f->db_desc_cap, bc = f->db_block_cap, ec = f->db_entry_cap;
+    if (f->db_n + num > dc || nb0 + nb > bc || K + 1 > ec) {
+        HIP_OK(hipStreamSynchronize(s));                   // a query may still read the buffers that are replaced
+        int64_t ec2 = ec;
+        if (f->grow_db(&f->db_desc, 8 * f->db_n, 8 * dc, 8 * (f->db_n + num), 8 * 1024, &dc) ||
+            f->grow_db(&f->db_blocks, nb0, bc, nb0 + nb, 64, &bc) || f->grow_db(&f->db_estart, K, ec, K + 1, 64, &ec2) ||
+            f->grow_db(&f->db_elen, K, ec, K + 1, 64, &ec2) || f->grow_db(&f->db_score, 0, ec, K + 1, 64, &ec2)) return -1;
+        f->db_desc_cap = dc / 8; f->db_block_cap = (int)bc; f->db_entry_cap = (int)ec2;
+    }
+    const int start = (int)f->db_n;
+    std::vector<FeatDbBlock> blocks(nb);
+    for (int b = 0; b < nb; ++b) blocks[b] = FeatDbBlock{K, start + PS_FEAT_DB_BLOCK * b};
+    const int se[2] = {start, (int)num};
+    if (num > 0) {
+        HIP_OK(hipMemcpyAsync(f->db_desc + 8 * (size_t)start, descriptors, (size_t)num * 32, hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(f->db_blocks + nb0, blocks.data(), (size_t)nb * sizeof(FeatDbBlock), hipMemcpyHostToDevice, s));
+    }
+    HIP_OK(hipMemcpyAsync(f->db_estart + K, &se[0], sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(f->db_elen + K, &se[1], sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));                       // the caller's array is free on return
+    if (!K) f->db_block.assign(1, 0);
+    f->db_start.push_back(start); f->db_len.push_back(num); f->db_block.push_back(nb0 + nb);
+    f->db_n += num;
+    *entry = K;
+    return 0;
+}
+
+int ps_feat_db_clear(ps_feat* f) {
+    if (!f) return fail("null handle");
+    f->db_start.clear(); f->db_len.clear(); f->db_block.clear();
+    f->db_n = 0;
+    return 0;
+}
+
+int ps_feat_db_size(ps_feat* f, int32_t* entries, int64_t* descriptors) {
+    if (!f || !entries || !descriptors) return fail("null argument");
+    *entries = (int32_t)f->db_start.size();
+    *descriptors = f->db_n;
+    return 0;
+}
+
+int ps_feat_db_query(ps_feat* f, int32_t first, int32_t last, int32_t ratio_num, int32_t ratio_den, const ps_feat_params* params,
+                     int32_t* scores) {
+    if (!f || !params || !scores) return fail("null argument");
+    const ps_feat_params& p = *params;
+    const int K = (int)f->db_start.size();
+    if (first < 0 || first > last || last > K) return fail("the entry range must satisfy 0 <= first <= last <= entries");
+    if (ratio_num < 1 || ratio_num > ratio_den || ratio_den > 32768) return fail("the ratio must satisfy 0 < num <= den <= 32768");
+    if (p.nms_n < 1 || p.nms_n > 3) return fail("nms_n must be 1..3");
+    if (p.max_features < 1 || p.max_features > f->max_features) return fail("max_features outside the handle's capacity");
+    if (f->cur < 0) return fail("push a frame before querying the database");
+    PsFeatFrame& Cf = f->frame[f->cur];
+    if (feat_frame_features(f, Cf, p)) return -1;
+    if (first == last) return 0;                           // a query of nothing (the feature pass waits for whoever needs it)
+    hipStream_t s = f->stream;
+    const int n = last - first, b0 = f->db_block[first], nb = f->db_block[last] - b0;
+    HIP_OK(hipMemsetAsync(f->db_score, 0, (size_t)n * sizeof(int), s));
+    if (nb > 0)
+        hipLaunchKernelGGL(k_feat_db_search, dim3(nb), dim3(256), 0, s, (const FeatDbBlock*)(f->db_blocks + b0), (const int*)f->db_estart,
+                           (const int*)f->db_elen, (int)first, (const uint32_t*)f->db_desc, Cf.im[0].list(), (int)p.max_features,
+                           (int)p.match_cost_max, (int)ratio_num, (int)ratio_den, f->db_score);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(scores, f->db_score, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
     return 0;
 }
 

@@ -32,6 +32,7 @@
 #include "ps_k_dense.h"
 #include "ps_k_feat.h"
 #include "ps_k_feat_global.h"
+#include "ps_k_feat_db.h"
 #include "ps_sparse.h"
 #include "ps_k_covmarg.h"
 #include "ps_k_triang.h"

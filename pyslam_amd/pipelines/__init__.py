@@ -9,6 +9,8 @@ sim3: similarity (Sim(3)) alignment RANSAC of two matched 3-D point sets -- a mo
 map or another keyframe (similarity: its host restatement).
 mono: matching by projection composed into ``track_frame``, matching without a prior composed into ``relocalise_frame``, and the
 monocular pipeline ``SparseMonoPipeline``.
+loop: the matcher's keyframe database composed with matching without a prior and the Sim(3) RANSAC into ``detect_loop`` (place
+recognition and its geometric verification; nothing corrects the map).
 The stereo dense pipeline (cv2.StereoBM) is not in scope (out of scope)."""
 from .ransac import FrameToFrameRANSAC, compute_transform_fast  # noqa: F401
 from .twoview import EssentialRANSAC, bootstrap  # noqa: F401
@@ -19,3 +21,4 @@ from .keyframes import Keyframe, DenseKeyframe, DenseRGBDKeyframe, SparseStereoK
 from .sparse import SparseVOPipeline, SparseStereoPipeline, SparseRGBDPipeline  # noqa: F401
 from .matcher import Matcher, Matcher_parameters  # noqa: F401
 from .mono import track_frame, relocalise_frame, SparseMonoPipeline, SparseMonoKeyframe  # noqa: F401
+from .loop import loop_candidates, verify_loop, detect_loop  # noqa: F401

@@ -45,7 +45,7 @@ integer up to the one division of the sub-pixel step:
 """
 import numpy as np
 
-__all__ = ['Params', 'OFFSETS', 'BORDER', 'R_NONE', 'gradients', 'response', 'features', 'match_leg', 'match', 'match_map', 'match_map_global', 'Frame']
+__all__ = ['Params', 'OFFSETS', 'BORDER', 'R_NONE', 'gradients', 'response', 'features', 'match_leg', 'match', 'match_map', 'match_map_global', 'db_query', 'Frame']
 
 BORDER = 5
 R_NONE = np.iinfo(np.int64).min
@@ -365,6 +365,39 @@ def match_map_global(frame, descriptors, ratio=(4, 5), params=None):
         feature[i], status[i] = j, 0
     _claim_and_refine(frame, desc, feature, status, cost, uv, p)
     return feature, status, cost, second, uv
+
+
+def db_query(entries, frame, ratio=(4, 5), params=None, first=0, last=None):
+    """The keyframe database query (step 10) -> scores (last - first,) int32: for every entry e of ``entries[first:last]`` -- a list
+    of (n_e, 32) uint8 descriptor arrays -- the number of its descriptors whose best cost over all features of ``frame`` is at most
+    ``match_cost_max`` and, where the frame has a second feature, satisfies ``den * best < num * second-best``.  A count of the
+    entry's descriptors, not of distinct features.  Written on its own, without match_map_global."""
+    p = params or Params()
+    num, den = int(ratio[0]), int(ratio[1])
+    if not 0 < num <= den <= 32768:
+        raise ValueError('db_query: the ratio must satisfy 0 < num <= den <= 32768, got {}'.format(tuple(ratio)))
+    K = len(entries)
+    last = K if last is None else int(last)
+    first = int(first)
+    if not 0 <= first <= last <= K:
+        raise ValueError('db_query: the entry range must satisfy 0 <= first <= last <= {}, got [{}, {})'.format(K, first, last))
+    F, cmax = len(frame), int(p.match_cost_max)
+    scores = np.zeros(last - first, dtype=np.int32)
+    if F == 0:
+        return scores
+    fd = frame.desc.astype(np.int32)
+    for e in range(first, last):
+        d = np.asarray(entries[e], dtype=np.uint8).reshape(-1, 32).astype(np.int32)
+        for row in d:
+            c = np.abs(fd - row).sum(axis=1)
+            order = np.argsort(c, kind='stable')               # ties: the lower feature index first
+            c1 = int(c[order[0]])
+            if c1 > cmax:
+                continue
+            if F >= 2 and den * c1 >= num * int(c[order[1]]):
+                continue
+            scores[e - first] += 1
+    return scores
 
 
 class _Descriptors:

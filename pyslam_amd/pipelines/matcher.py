@@ -15,6 +15,8 @@ them -- is not processed again: the pipelines push the active keyframe in front 
 ``setMap`` / ``matchMap`` are matching by projection (step 8 of the definition): the map's points, each with the
 descriptor it was created with, against the features of the current frame around their projections under a pose prior.
 ``matchMapGlobal`` is matching without a prior (step 9): every map point against every feature, with a second-best ratio test.
+``dbAdd`` / ``dbQuery`` are the keyframe database (step 10): per stored entry, the number of its descriptors that pass step 9's test
+against the current frame, all entries in one launch.
 """
 import ctypes as C
 
@@ -68,6 +70,8 @@ class Matcher:
         self._passes_before = 0
         self._map = None            # (points_w, descriptors) of setMap, kept so that a rebuilt handle gets the map again
         self._map_on = None         # the handle the map was uploaded to
+        self._db = []               # the entries of dbAdd, kept so that a rebuilt handle gets the database again
+        self._db_on = None          # the handle the database was uploaded to
 
     def setIntrinsics(self, *args):
         """Accepted and ignored (libviso2 uses the calibration for its 3-D outlier checks; RANSAC follows here)."""
@@ -93,6 +97,7 @@ class Matcher:
             shape = (max(h, self._shape[0]) if self._shape else h, max(w, self._shape[1]) if self._shape else w, cap)
             nat.check(self._lib.ps_feat_create(shape[0], shape[1], shape[2], C.c_void_p(self._stream or 0), C.byref(hh)))
             self._h, self._shape, self._n = hh, shape, 0
+            self._db_on = self._h if not self._db else None     # an empty database is on every handle
         return self._h
 
     def pushBack(self, left, right=None):
@@ -204,6 +209,62 @@ class Matcher:
             nat.check(self._lib.ps_feat_read_map_matches(self._h, N, nat.i32p(feature), nat.i32p(status), nat.i32p(cost), nat.f64p(uv)))
             nat.check(self._lib.ps_feat_read_map_second(self._h, N, nat.i32p(second)))
         return feature, status, cost, second, uv
+
+    def _desc(self, descriptors):
+        desc = np.asarray(descriptors)
+        if desc.dtype != np.uint8:
+            raise TypeError('Matcher: descriptors must be uint8, got {}'.format(desc.dtype))
+        return np.ascontiguousarray(desc.reshape(-1, 32))
+
+    def _upload_db(self):
+        if self._db_on is not None:
+            return
+        for desc in self._db:
+            e = C.c_int32()
+            nat.check(self._lib.ps_feat_db_add(self._h, desc.shape[0], desc.ctypes.data_as(nat.c_u8p) if desc.shape[0] else None,
+                                               C.byref(e)))
+        self._db_on = self._h
+
+    def dbAdd(self, descriptors):
+        """Appends one entry -- (n, 32) uint8 descriptors as ``features`` returns them, n >= 0 -- to the keyframe database and
+        returns its index.  Entries are never edited; ``dbClear`` empties the database."""
+        desc = self._desc(descriptors)
+        if self._h is not None and self._db_on is self._h:
+            e = C.c_int32()
+            nat.check(self._lib.ps_feat_db_add(self._h, desc.shape[0], desc.ctypes.data_as(nat.c_u8p) if desc.shape[0] else None,
+                                               C.byref(e)))
+            assert e.value == len(self._db)
+        elif len(self._db) >= 65536 or sum(d.shape[0] for d in self._db) + desc.shape[0] > 1 << 22:
+            raise nat.NativeError('Matcher: the database holds at most 65536 entries and 2^22 descriptors')
+        self._db.append(desc)
+        return len(self._db) - 1
+
+    def dbClear(self):
+        self._db = []
+        if self._h is not None and self._db_on is self._h:
+            nat.check(self._lib.ps_feat_db_clear(self._h))
+
+    def dbSize(self):
+        """(entries, descriptors) of the keyframe database."""
+        if self._h is not None and self._db_on is self._h:
+            k, n = C.c_int32(), C.c_int64()
+            nat.check(self._lib.ps_feat_db_size(self._h, C.byref(k), C.byref(n)))
+            return k.value, n.value
+        return len(self._db), sum(d.shape[0] for d in self._db)
+
+    def dbQuery(self, ratio=(4, 5), first=0, last=None):
+        """Scores (last - first,) int32 of the database's entries ``first .. last - 1`` (default: all) against the current frame's
+        (left) image: per entry, the number of its descriptors whose best cost over all features is at most ``match_cost_max`` and
+        satisfies ``ratio[1] * cost < ratio[0] * second-best cost`` -- what ``matchMapGlobal`` gives status 0 or 3 with the entry
+        as the map.  One launch for the whole range."""
+        if self._h is None:
+            raise nat.NativeError('Matcher: push a frame before querying the database')
+        self._upload_db()
+        last = len(self._db) if last is None else int(last)
+        scores = np.zeros(max(last - int(first), 1), dtype=np.int32)
+        p = self.params._native()
+        nat.check(self._lib.ps_feat_db_query(self._h, int(first), last, int(ratio[0]), int(ratio[1]), C.byref(p), nat.i32p(scores)))
+        return scores[:max(last - int(first), 0)]
 
     @property
     def feature_passes(self):

@@ -27,6 +27,10 @@ The map lives on the host as arrays -- ``points_w`` (L, 3), ``descriptors`` (L, 
 ``obs_kf`` / ``obs_lm`` / ``obs_uv`` -- and is uploaded to the matcher when the landmarks tracked against change.  Its scale is
 that of the initialisation; nothing corrects its drift (no loop closure, no scale prior: DESIGN.md section 7, limits).
 
+Loop detection (``loop_detection``, off by default): every keyframe's descriptors join the matcher's keyframe database, and after a
+new keyframe k and its bundle adjustment ``loop.detect_loop`` runs over the entries ``[0, k - loop_gap)``.  A hit is recorded in
+``loop_closures``; it corrects nothing, and poses and map are those of the same run with the switch off.
+
 Tracking loss (``relocalise``): a frame on which ``register_frame`` raises ValueError is relocalised against all live landmarks.
 Where that fails too the frame's pose is ``None`` and the pipeline is ``lost``: every further frame is relocalised until one
 succeeds (its index joins ``relocalised``), after which tracking goes on as before."""
@@ -223,6 +227,16 @@ class SparseMonoPipeline:
         """The last frame could be neither tracked nor relocalised"""
         self.relocalised = []
         """Indices into ``T_c_w`` of the frames whose pose comes from a relocalisation"""
+        self.loop_detection = False
+        """Keep every keyframe in the matcher's database and look for a loop at every new keyframe"""
+        self.loop_gap = 10
+        """Number of newest keyframes that are never queried"""
+        self.loop_ratio = (4, 5)
+        """(num, den) of the ratio test of the database query and of the verification's matching without a prior"""
+        self.loop_closures = []
+        """One dict per detected loop: keyframe, entry, scale, T_21 (p_keyframe = scale R p_entry + t), pairs, connected"""
+        self.loop_queries = []
+        """One dict per query: keyframe, scores, candidates, verified ((entry, counts) per verification)"""
 
     def set_mode(self, mode):
         """Set the localization mode to ['map'|'track']"""
@@ -293,6 +307,8 @@ class SparseMonoPipeline:
         self._add_observations(1, lm, m[ok, 4:6])
         self.keyframes.append(kf)
         self.landmark_counts.append(int(self.alive.sum()))
+        if self.loop_detection:
+            self._db_sync()
         return T_2w
 
     def _features(self, which):
@@ -345,7 +361,53 @@ class SparseMonoPipeline:
             self._bundle_adjust()
         self._drop_behind()
         self.landmark_counts.append(int(self.alive.sum()))
+        if self.loop_detection:
+            self._detect_loop(k)
         return kf.T_c_w
+
+    # ---- loop detection ----
+    def loop_entry(self, k):
+        """Keyframe k as an entry of ``loop.verify_loop``: its features, their landmarks in its camera frame (NaN: none, or not
+        alive) and the landmarks' indices."""
+        kf = self.keyframes[k]
+        T = kf.T_c_w.as_matrix()
+        bound = kf.landmark >= 0
+        bound[bound] = self.alive[kf.landmark[bound]]
+        pts = np.full((kf.uv.shape[0], 3), np.nan)
+        pts[bound] = self.points_w[kf.landmark[bound]] @ T[:3, :3].T + T[:3, 3]
+        return dict(desc=kf.desc, points_c=pts, uv=kf.uv, ids=np.where(bound, kf.landmark, -1))
+
+    def _detect_loop(self, k):
+        self._db_sync()
+        last = k - int(self.loop_gap)
+        if last <= 0:
+            return
+        state = np.random.get_state()                          # the verification's samples leave the tracking's draws where they were
+        try:
+            self._query_loop(k, last)
+        finally:
+            np.random.set_state(state)
+
+    def _db_sync(self):
+        while self.matcher.dbSize()[0] < len(self.keyframes):  # entry index = keyframe index
+            self.matcher.dbAdd(self.keyframes[self.matcher.dbSize()[0]].desc)
+
+    def _query_loop(self, k, last):
+        from pyslam_amd.pipelines.loop import detect_loop
+        pipe = self
+
+        class Entries:
+            def __getitem__(self, e):
+                return pipe.loop_entry(e)
+        q = self.loop_entry(k)
+        hit = detect_loop(self.camera, self.matcher, self.keyframes[k].image, q['points_c'], Entries(), 0, last, ids_q=q['ids'],
+                          ratio=self.loop_ratio)
+        query = dict(self.matcher.loop_query_, keyframe=k)
+        self.loop_queries.append(query)
+        if hit is not None:
+            e, scale, T_21, pairs = hit
+            self.loop_closures.append(dict(keyframe=k, entry=e, scale=scale, T_21=T_21, pairs=pairs,
+                                           connected=query['verified'][-1][1]['connected']))
 
     def _new_landmarks(self, prev, kf, k):
         """Flow matches between the previous keyframe and the new one whose features are bound to no landmark: those that agree
