@@ -511,6 +511,11 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
                               the lagged set-up applies, the exact set-up's block scaling and coarse row sums are one launch of the rows
                               kernel.  0: one wave per block through LDS, the two launches.  Speed only, same bits.  Handled ahead of
                               the option table
+     "cg_persist_recover" [1; 0 / 1] the one-launch folded CG ("cg_persist") recovers x = L^-T (x^_f + P y) inside the launch, every workgroup
+                              its own slice of poses from operands it copied into LDS at kernel entry, when the largest slice's
+                              operands fit "cg_persist_recover_lds" [146432; 0 .. 146432 bytes of dynamic LDS: what one workgroup per
+                              compute unit leaves free]; else, and with 0, the gated k_coarse_recover runs behind the launch.  Speed
+                              only, same bits.  Both handled ahead of the option table
      "schur_pipeline"     [1; 0 / 1] the Schur pair kernel with two chunks per wave in flight (k_schur_pairs_db); 0: k_schur_pairs
      "lm_packed" [1; 0 / 1], "band_part" [1; 0 / 1], "band_part_chunk" [0 auto; 0 .. 4096 nodes], "sync_refactor" [1; 0 / 1],
      "hold_across_steps" [1; 0 / 1]: round-5 kernels and schedules against their predecessors (DESIGN.md sections 0 and 3)
@@ -534,7 +539,11 @@ int ps_set_option(ps_problem* h, const char* name, double value);
    those among them that found ridden factors made for another set-up plan (lagged / exact, coarse buffer) than their own.
    "rows_regs": the option; "rows_setups": lagged set-ups launched so far (k_rows_setup); "exact_row_setups": exact set-ups so far
    whose block scaling and row sums were the rows kernel's one launch; "rows_lci_in_lds": 1 if the rows kernel holds the lagged
-   coarse factor in LDS on this handle (0 before the coarse level is built, and where the lagged set-up does not apply). */
+   coarse factor in LDS on this handle (0 before the coarse level is built, and where the lagged set-up does not apply).
+   "cg_persist_recover", "cg_persist_recover_lds": the options; "cg_persist_recover_need": bytes of LDS the largest slice's operands
+   take on this handle (0 before the coarse level is built, and where the one-launch folded CG does not apply);
+   "cg_persist_recovered" / "cg_persist_recover_fallbacks": one-launch solves so far (ps_problem_info.cg_persist_solves) that recover
+   x inside the launch / that leave it to k_coarse_recover behind the launch. */
 int ps_get_option(ps_problem* h, const char* name, double* value);
 
 /* hipEvent stage timers on the handle's stream (the reference has no tracing). */

@@ -67,12 +67,12 @@ int ps_warm_up(void) {
 int ps_problem_destroy(ps_problem* h) {
     if (!h) return 0;
     if (h->cp_dbg) {
-        long long c[8]; hipMemcpy(c, h->cp_dbg, 64, hipMemcpyDeviceToHost);
+        long long c[PS_CP_NCLK]; hipMemcpy(c, h->cp_dbg, sizeof c, hipMemcpyDeviceToHost);
         int khz = 100000; hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, 0);
         fprintf(stderr, "k_cg_persist, workgroup 0, %ld launches, us per launch: recurrences %.2f | sync %.2f | products + publish %.2f | gather + sums %.2f "
-                "(%.1f failed passes) | dots + sync %.2f | exchanges %lld = %.2f per launch\n", h->cp_launches, c[0] * 1e3 / khz / h->cp_launches,
+                "(%.1f failed passes) | dots + sync %.2f | exchanges %lld = %.2f per launch | prologue %.2f | recovery %.2f\n", h->cp_launches, c[0] * 1e3 / khz / h->cp_launches,
                 c[1] * 1e3 / khz / h->cp_launches, c[2] * 1e3 / khz / h->cp_launches, c[3] * 1e3 / khz / h->cp_launches, (double)c[7] / h->cp_launches,
-                c[5] * 1e3 / khz / h->cp_launches, c[6], (double)c[6] / h->cp_launches);
+                c[5] * 1e3 / khz / h->cp_launches, c[6], (double)c[6] / h->cp_launches, c[8] * 1e3 / khz / h->cp_launches, c[4] * 1e3 / khz / h->cp_launches);
         hipFree(h->cp_dbg);
     }
     if (h->xp_dbg) {                                      // (PS_XP_CLOCKS: the LAST launch's time stamps, averaged over its passes)

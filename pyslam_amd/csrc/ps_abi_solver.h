@@ -968,6 +968,19 @@ int ps_set_option(ps_problem* h, const char* name, double value) {
         h->prelin_valid = h->prelm_valid = h->ride_valid = false;
         return 0;
     }
+    // the one-launch folded CG's recovery of x inside the launch (csrc/ps_core.hip: cg_persist_recover); 0: k_coarse_recover behind it.
+    // "cg_persist_recover_lds": the most dynamic LDS a workgroup's slice of the recovery's operands may take
+    if (!std::strcmp(name, "cg_persist_recover")) {
+        h->cg_persist_recover = value != 0 ? 1 : 0;
+        h->prelin_valid = h->prelm_valid = h->ride_valid = false;
+        return 0;
+    }
+    if (!std::strcmp(name, "cg_persist_recover_lds")) {
+        if (!(value >= 0 && value <= PS_CP_RECOVER_LDS_CAP)) return fail("cg_persist_recover_lds out of range (0 .. 146432 bytes)");
+        h->cg_persist_recover_lds = (int)value;
+        h->prelin_valid = h->prelm_valid = h->ride_valid = false;
+        return 0;
+    }
     h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     const char* refusal = nullptr;
     const int fx = ps_option_apply(*h, name, value, &refusal);
@@ -997,6 +1010,11 @@ int ps_get_option(ps_problem* h, const char* name, double* value) {
     else if (n == "rows_setups") *value = (double)h->rows_setups;
     else if (n == "exact_row_setups") *value = (double)h->exact_row_setups;
     else if (n == "rows_lci_in_lds") *value = h->coarse_built && h->lagx_ok && h->rows_lci_lds ? 1.0 : 0.0;
+    else if (n == "cg_persist_recover") *value = (double)h->cg_persist_recover;
+    else if (n == "cg_persist_recover_lds") *value = (double)h->cg_persist_recover_lds;
+    else if (n == "cg_persist_recover_need") *value = h->coarse_built && h->cp_ok ? (double)h->cp_rec_lds : 0.0;
+    else if (n == "cg_persist_recovered") *value = (double)h->cp_rec_inside;
+    else if (n == "cg_persist_recover_fallbacks") *value = (double)h->cp_rec_behind;
     else return fail("ps_get_option: no read-back for option: " + n);
     return 0;
 }

@@ -395,6 +395,14 @@ struct ps_problem : PsOptions, PsCostHistory, PsCarried {
     unsigned long long* cp_exch = nullptr;
     unsigned cp_salt = 0;
     long cp_launches = 0, cp_failures = 0;
+    // options "cg_persist_recover" / "cg_persist_recover_lds" (ps_set_option, ahead of the table): the recovery x = L^-T (x^_f + P y)
+    // inside the launch, every workgroup its own slice of poses with the operands prefetched into LDS (ps_k_cg_persist.h), when
+    // the largest slice's operands fit the cap; else, and with 0, the gated k_coarse_recover behind the launch.  Same bits either way.
+    int cg_persist_recover = 1;
+    int cg_persist_recover_lds = PS_CP_RECOVER_LDS_CAP;
+    int cp_rec_pp = 0, cp_rec_cols = 0;         // poses per workgroup's slice; most columns of L_c^-1 a slice's nodes select
+    size_t cp_rec_lds = 0;                      // dynamic LDS the largest slice needs (0: no slices -- pnode is not ascending)
+    long cp_rec_inside = 0, cp_rec_behind = 0;  // launches that recover in the launch / that leave it to k_coarse_recover
     // co-residency (ps_stream_cus / PersistLedger above): what build_coarse found, what a solve in flight holds
     int persist_dev = 0, persist_cus = 0;       // device of the handle; compute units its stream may use (0: unknown -> no one-launch form)
     bool persist_masked = false;                // ... fewer than the device has (a CU mask)

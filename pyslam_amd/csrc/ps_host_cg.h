@@ -426,10 +426,25 @@ int build_coarse(ps_problem* h) {
         // all workgroups must be resident at once: what the DEVICE says this stream can hold (occupancy of the instantiation x
         // the compute units the stream may use, ps_core.hip: ps_stream_cus), not a literal; at most PS_CP_MAXEX exchanged sums
         const int cp_nwg = cdiv((int)tasks.size(), PS_CP_NT / 64);
+        // the recovery inside the launch: workgroup b owns poses [b pp, (b + 1) pp) and prefetches the columns of L_c^-1 that its
+        // poses' nodes q, q + 1 select -- nodes pnode[first] .. pnode[last] + 1, pnode ascending (else: no slices, cp_rec_lds = 0)
+        h->cp_rec_pp = cdiv(nr, cp_nwg); h->cp_rec_cols = 0; h->cp_rec_lds = 0;
+        {
+            bool ascending = true;
+            for (int i = 1; i < nr; ++i) ascending = ascending && pnode[i] >= pnode[i - 1];
+            for (int p0 = 0; p0 < nr && ascending; p0 += h->cp_rec_pp) {
+                const int last = std::min(nr, p0 + h->cp_rec_pp) - 1;
+                h->cp_rec_cols = std::max(h->cp_rec_cols, (std::min(ncb - 1, pnode[last] + 1) - pnode[p0] + 1) * D);
+            }
+            if (ascending && h->cp_rec_pp <= PS_CP_NT) h->cp_rec_lds = cp_recover_lds(D, ncb * D, h->cp_rec_pp, h->cp_rec_cols);
+        }
         int cp_per_cu = 0;
         {
+            // (occupancy with the LDS of the recovery's slices where a launch may ask for it: never fewer units than it will need)
             const void* kfn = D == 6 ? (const void*)k_cg_persist<6> : (const void*)k_cg_persist<3>;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&cp_per_cu, kfn, PS_CP_NT, 0) != hipSuccess) { (void)hipGetLastError(); cp_per_cu = 0; }
+            const size_t dyn = h->cp_rec_lds <= (size_t)PS_CP_RECOVER_LDS_CAP ? h->cp_rec_lds : 0;
+            if (dyn && ensure_dynamic_lds(kfn, dyn)) return -1;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&cp_per_cu, kfn, PS_CP_NT, dyn) != hipSuccess) { (void)hipGetLastError(); cp_per_cu = 0; }
         }
         h->cp_cus_needed = cp_per_cu > 0 ? cdiv(cp_nwg, cp_per_cu) : 0;
         if ((long)tasks.size() * D <= (long)PS_CP_MAXEX && h->cp_cus_needed > 0 && h->cp_cus_needed <= h->persist_capacity()) {
@@ -891,7 +906,7 @@ void cg_fused_launch(ps_problem* h, double tol, int count) {
     // the whole solve in ONE launch (ps_k_cg_persist.h) when the system fits its layout: every launch the budget still allows
     // (it stops at convergence by itself), from a fresh set-up only
 #ifdef PS_MEASURE
-    if (ps_env("PS_CP_CLOCKS") && !h->cp_dbg) { hipMalloc(&h->cp_dbg, 64); hipMemset(h->cp_dbg, 0, 64); }
+    if (ps_env("PS_CP_CLOCKS") && !h->cp_dbg) { hipMalloc(&h->cp_dbg, PS_CP_NCLK * 8); hipMemset(h->cp_dbg, 0, PS_CP_NCLK * 8); }
 #endif
     if (h->cg_persist && h->cp_ok && h->G > 0 && h->cg_lds && !h->cg_split && !h->cg_two_level_reduce &&
         !h->cg_ablate && h->cg_launched == 0 && h->cg_max_launches > 0 && h->cg_max_launches <= 4090 && !h->no_repeat &&
@@ -901,12 +916,18 @@ void cg_fused_launch(ps_problem* h, double tol, int count) {
             hipMemsetAsync(h->cp_exch, 0, (size_t)4 * h->cp_ntasks * D * sizeof(unsigned long long), h->stream);
             h->cp_salt = 1;
         }
-        hipLaunchKernelGGL((k_cg_persist<D>), dim3(cdiv(h->cp_ntasks, PS_CP_NT / 64)), dim3(PS_CP_NT), 0, h->stream, h->nr_aug * D,
+        // the recovery inside the launch (option "cg_persist_recover") when the largest slice's operands fit the cap (which is at most
+        // PS_CP_RECOVER_LDS_CAP: build_coarse has asked for that much dynamic LDS); else rec.x == NULL, and the gated
+        // k_coarse_recover runs behind the launch (cg_fused_recover)
+        const bool inside = h->cg_persist_recover && h->cp_rec_lds > 0 && h->cp_rec_lds <= (size_t)h->cg_persist_recover_lds;
+        hipLaunchKernelGGL((k_cg_persist<D>), dim3(cdiv(h->cp_ntasks, PS_CP_NT / 64)), dim3(PS_CP_NT), inside ? h->cp_rec_lds : 0, h->stream, h->nr_aug * D,
                            h->cp_ntasks, (const CpTask*)h->cp_tasks, h->cp_row_task0, h->acol_idx, h->Saug, h->cg_r[0], h->cg_w[0], h->cg_s[0], h->cg_p,
                            h->cg_xh, h->hist, cap, nl, tol2, h->status, h->scalars, h->cp_exch, h->cp_salt, h->cp_spin, h->cp_dbg,
-                           CpRecover{h->nr, h->ncb, h->pnode, h->pw0, h->pw1, h->Linv, h->Lci2[h->lci_cur], h->Bmat, h->x});
+                           CpRecover{h->nr, h->ncb, h->pnode, h->pw0, h->pw1, h->Linv, h->Lci2[h->lci_cur], h->Bmat, inside ? h->x : nullptr,
+                                     h->cp_rec_pp, h->cp_rec_cols});
         h->cg_launched = nl; h->cg_kernel_launches += 1; ++h->cp_launches;
-        h->cp_recovered = true;                               // (a converged solve leaves x behind: the gated k_coarse_recover is not needed)
+        ++(inside ? h->cp_rec_inside : h->cp_rec_behind);
+        h->cp_recovered = inside;                             // (a converged solve leaves x behind: the gated k_coarse_recover is not needed)
         return;
     }
     h->cg_kernel_launches += count;

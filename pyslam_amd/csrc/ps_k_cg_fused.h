@@ -854,3 +854,34 @@ __global__ __launch_bounds__(256) void k_bsr_residual(
     }
     g[t] = v;
 }
+
+// x^_i = x~_f,i + pw0_i y[node_i] + pw1_i y[node_i + 1] with y = Lci^T x~_c ;  x_i = Linv_i^T x^_i  (the two-level recovery)
+// The arithmetic of the recovery, ONE source for its two callers (k_coarse_recover, ps_k_coarse.h: operands from memory; k_cg_persist: a
+// workgroup's slice of them from LDS).  Every product is an explicit fma() -- as scaled_block_row's -- so that the two callers
+// cannot be contracted differently: the sums are the same to the last bit wherever the operands live.
+//   coarse_recover_ylane   one lane's share of y_k = sum_{m >= k} Lci[m][k] x~_c[m]: m = k + sub, k + sub + 8, ... ascending (8 lanes
+//                          per column; the caller adds the lanes with the xor-1/2/4 butterfly).  Entry m of column k is col[m * stride]
+//   coarse_recover_entry   component c of x_i: z = w0 y[q] + w1 y[q + 1] (y1 == NULL: no right node), x^_a += sum_m B[a][m] z[m] in m
+//                          order, sum_a Linv[a][c] x^_a in a order
+PS_DEV double coarse_recover_ylane(const double* col, int stride, const double* xc, int k, int sub, int nc) {
+    double v = 0.0;
+#pragma unroll 4
+    for (int m = k + sub; m < nc; m += 8) v = fma(col[(size_t)m * stride], xc[m], v);
+    return v;
+}
+template <int D>
+PS_DEV double coarse_recover_entry(const double* y0, const double* y1, double w0, double w1, const double* xh /* x~_f,i */,
+                                   const double* B /* B_i */, const double* Li /* Linv_i */, int c) {
+    double z[D];                                         // interpolated coarse unknown at pose i
+#pragma unroll
+    for (int m = 0; m < D; ++m) { const double right = y1 ? w1 * y1[m] : 0.0; z[m] = fma(w0, y0[m], right); }
+    double v = 0.0;
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        double xhat = xh[a];
+#pragma unroll
+        for (int m = 0; m < D; ++m) xhat = fma(B[a * D + m], z[m], xhat);
+        v = fma(Li[a * D + c], xhat, v);
+    }
+    return v;
+}

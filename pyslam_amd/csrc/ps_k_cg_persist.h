@@ -37,6 +37,7 @@
 #define PS_CP_MAXEX (12 * PS_CP_NT)     // exchanged sums per iteration: tasks * D <= PS_CP_MAXEX (1 024 tasks of SE(3) rows)
 #define PS_CP_MAXN (PS_CP_NV * PS_CP_NT)
 #define PS_CP_LONG 4                    // tasks of a long row (more than two tasks) gathered at a time
+#define PS_CP_NCLK 16                   // words of the measurement build's phase clocks (PS_CP_CLOCKS): 0-7 the loop, 4 the recovery, 8 the prologue
 // Wall-clock bound of a spin (wall_clock64: 100 MHz), beside the bound in passes: ONE SECOND.  Round 6 first took the 20 ms
 // k_xcg_persist had: with two PROCESSES on one device (tests/test_gpu_sharded.py: two ranks on one GPU) the scheduler suspends a
 // process's queues for whole time slices, a spin that straddles a slice sees the clock jump by more than that, and one solve in
@@ -48,9 +49,22 @@
 #endif
 
 struct CpTask { int32_t row, b0, b1, pad; };
-// what k_coarse_recover needs: x = L^-T (x^_f + P y), y = L_c^-T x^_c -- done by the kernel's first workgroup once the solve has
-// converged (x == NULL: not done here)
-struct CpRecover { int nr, ncb; const int32_t* pnode; const double *pw0, *pw1, *Linv, *Lci, *Bmat; double* x; };
+// what k_coarse_recover needs: x = L^-T (x^_f + P y), y = L_c^-T x^_c -- done inside the launch once the solve has converged
+// (x == NULL: not done here).  Workgroup b recovers poses [b pp, (b + 1) pp), pp = ceil(nr / workgroups) (C3: 58 workgroups, 4
+// poses each), from operands it copied into LDS at kernel entry: every operand is final before the launch, every workgroup holds
+// all of x^ with the same bits -- so nothing of the recovery is a dependent trip to memory behind the solve, and no workgroup
+// waits for another.  (Rounds 5-6: the first workgroup alone, out of memory, while the others had left: ~20 serialised round trips.)
+// maxcols: the most columns of L_c^-1 a slice's nodes select (the host's plan: build_coarse), which fixes the LDS layout.
+struct CpRecover { int nr, ncb; const int32_t* pnode; const double *pw0, *pw1, *Linv, *Lci, *Bmat; double* x; int pp, maxcols; };
+// The most dynamic LDS a slice's operands may take.  At 256 VGPRs the kernel's 8 waves fill a compute unit's registers (2 waves per
+// SIMD): one workgroup per unit, which has the unit's 160 KB of LDS to itself -- less the static 16.3 KB (rn with the time-out flag, red), rounded to
+// 17 KB: 143 KB.  (C3 needs 13.4 KB.)  A larger need: rec.x == NULL and k_coarse_recover behind the launch.
+#define PS_CP_RECOVER_LDS_CAP ((160 - 17) * 1024)
+// dynamic LDS of a launch whose slices are `pp` poses and select at most `maxcols` columns of L_c^-1 (nc rows each):
+// columns | B, Linv, pw0, pw1 of the slice | y of the columns | pnode of the slice, its first node and number of columns
+inline size_t cp_recover_lds(int D, int nc, int pp, int maxcols) {
+    return ((size_t)maxcols * nc + (size_t)pp * (2 * D * D + 2) + maxcols) * sizeof(double) + (size_t)(pp + 2) * sizeof(int32_t);
+}
 
 typedef unsigned long long ps_u64;
 typedef __attribute__((address_space(1))) ps_u64 ps_gu64;
@@ -86,18 +100,60 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
     double* __restrict__ hist, int cap, int nlaunch /* iterations k = -1 .. nlaunch - 2 at most */, double tol2,
     int32_t* __restrict__ status, double* __restrict__ scalars,
     ps_u64* __restrict__ exch /* 2 x (ntasks * D) doubles as two granules each */, unsigned salt, unsigned spin_limit,
-    long long* __restrict__ dbg /* measurement build: phase clocks of workgroup 0 (8 words), else NULL */, CpRecover rec)
+    long long* __restrict__ dbg /* measurement build: phase clocks of workgroup 0 (PS_CP_NCLK words), else NULL */, CpRecover rec)
 {
     constexpr int DD = D * D;
-    __shared__ double rn[PS_CP_MAXN];
-    __shared__ double yc[PS_CP_MAXN];                  // the recovery's y (the exchanged sums go from the granules straight to registers)
+    // (static LDS a multiple of 16 bytes, 16 656: the dynamic region behind it starts aligned.  rn[PS_CP_MAXN] is the time-out flag)
+    __shared__ double rn[PS_CP_MAXN + 2];
     __shared__ double red[2][2][PS_CP_NT / 64];
-    __shared__ int bad;
+    extern __shared__ __attribute__((aligned(16))) double cp_rec[];   // the recovery's operands of this workgroup's slice (rec.x != NULL)
+    int& bad = *reinterpret_cast<int*>(&rn[PS_CP_MAXN]);
     const int t = threadIdx.x, wv = t >> 6, lane = t & 63, kk = lane >> 3, r = lane & 7;
     const int task = blockIdx.x * (PS_CP_NT / 64) + wv;
     const bool chief = blockIdx.x == 0 && t == 0;
     const size_t nex = (size_t)ntasks * D;                   // exchanged doubles per iteration
+    const long long t_entry = dbg ? wall_clock64() : 0;      // (measurement build: the prologue's clock, dbg[8])
     if (t == 0) bad = 0;
+    // ---- the recovery's operands of this workgroup's slice of poses [p0, p0 + np): loaded HERE, stored to LDS behind the loads below
+    // (everything is final before the launch and independent of the solve: one round trip beside the prologue's own).  A flat
+    // list: entries [0, ncols * nc) are the columns qa D .. of L_c^-1 that the slice's nodes select, rows m >= k of column k only
+    // (sLc[j * nc + m]); behind them B, Linv, pw0, pw1 of the slice, in this order.  Nothing of this is carried over the solve loop
+    // in a register (the kernel has none to spare): the recovery works its layout out again, and reads the slice's first node
+    // and number of columns back from LDS.
+    constexpr int PF = 4;                                    // list entries per thread in flight (C3: 1 404 + 296 entries, one trip)
+    const int nc = rec.ncb * D, p0 = blockIdx.x * rec.pp;
+    const int np = rec.x ? max(0, min(rec.nr, p0 + rec.pp) - p0) : 0;
+    int qa = 0, ncols = 0, nlist = 0;
+    if (np > 0) {
+        int32_t* const spn = reinterpret_cast<int32_t*>(cp_rec + rec.maxcols * nc + rec.pp * (2 * DD + 2) + rec.maxcols);
+        qa = rec.pnode[p0];
+        ncols = min((min(rec.ncb - 1, rec.pnode[p0 + np - 1] + 1) - qa + 1) * D, rec.maxcols);
+        nlist = ncols * nc + np * (2 * DD + 2);
+        if (t < np) spn[t] = rec.pnode[p0 + t];
+        if (t == 0) { spn[rec.pp] = qa; spn[rec.pp + 1] = ncols; }
+    }
+    auto rec_src = [&](int idx, int& dst) -> const double* { // list entry idx: where it comes from (NULL: nothing) and goes to
+        const int nl = ncols * nc;
+        if (idx < nl) {
+            const int m = idx / ncols, j = idx - m * ncols, k = qa * D + j;
+            dst = j * nc + m;
+            return m >= k ? rec.Lci + (size_t)m * nc + k : nullptr;
+        }
+        const int e = idx - nl, nb = np * DD;
+        dst = rec.maxcols * nc + e;
+        if (e < nb) return rec.Bmat + (size_t)p0 * DD + e;
+        if (e < 2 * nb) return rec.Linv + (size_t)p0 * DD + (e - nb);
+        if (e < 2 * nb + np) return rec.pw0 + p0 + (e - 2 * nb);
+        return rec.pw1 + p0 + (e - 2 * nb - np);
+    };
+    double pfv[PF];
+    int pfd[PF];
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+        const int idx = t + u * PS_CP_NT;
+        pfd[u] = -1; pfv[u] = 0.0;
+        if (idx < nlist) { int d = 0; const double* src = rec_src(idx, d); if (src) { pfv[u] = *src; pfd[u] = d; } }
+    }
     // ---- the task's blocks into registers (once), the vectors' entries of this thread
     int b0 = 0, b1 = 0;
     if (task < ntasks) { const CpTask tk = tasks[task]; b0 = tk.b0; b1 = tk.b1; }
@@ -131,6 +187,14 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
     int lv = -1, le0 = 0, len = 0;                           // the thread's first entry of a row of more than two tasks
 #pragma unroll
     for (int v = PS_CP_NV - 1; v >= 0; --v) if (en[v] > 2) { lv = v; le0 = e0[v]; len = en[v]; }
+#pragma unroll
+    for (int u = 0; u < PF; ++u) if (pfd[u] >= 0) cp_rec[pfd[u]] = pfv[u];
+    for (int base = PF * PS_CP_NT; base < nlist; base += PS_CP_NT) {     // (a longer list: what is left, one entry at a time)
+        const int idx = base + t;
+        int d = 0;
+        const double* src = idx < nlist ? rec_src(idx, d) : nullptr;
+        if (src) cp_rec[d] = *src;
+    }
     if (status[ST_PCG_DONE]) return;                         // (as every launch of the per-iteration form)
     // (1 / gamma_prev and 1 / alpha_prev are formed while the exchange is in flight: ONE division between an iteration's dot
     //  products and its recurrences -- the per-launch kernels do three, which changes the last bits of alpha and beta, not more)
@@ -139,12 +203,13 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
     long long ck[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define PS_CP_CLK(i) do { if (dbg) { const long long now_ = wall_clock64(); ck[i] += now_ - last_; last_ = now_; } } while (0)
     long long last_ = dbg ? wall_clock64() : 0;
+    if (dbg && chief) dbg[8] += last_ - t_entry;             // (the prologue: kernel entry to the first pass)
     for (int k = -1; k < nlaunch - 1; ++k) {
         double alpha = 0.0, beta = 0.0;
         if (k >= 0) {
             if (k == 0) thresh = tol2 * gamma;
             if (!(gamma > thresh)) {                         // converged (gamma == 0 too); NaN = breakdown
-                if (chief) { status[ST_PCG_DONE] = (gamma != gamma) ? 2 : 1; scalars[SC_RRFINAL] = gamma; if (k == 0) scalars[SC_RR0] = gamma; }
+                if (chief) { atomicMax(&status[ST_PCG_DONE], (gamma != gamma) ? 2 : 1); scalars[SC_RRFINAL] = gamma; if (k == 0) scalars[SC_RR0] = gamma; }
                 converged = !(gamma != gamma);
                 break;
             }
@@ -152,7 +217,7 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
             const double denom = (k == 0) ? delta : delta - beta * gamma * inv_aprev;
             alpha = gamma / denom;
             if (!(denom > 0.0)) {                            // breakdown: stop, the host reports it
-                if (chief) { status[ST_PCG_DONE] = 2; scalars[SC_RRFINAL] = gamma; }
+                if (chief) { atomicMax(&status[ST_PCG_DONE], 2); scalars[SC_RRFINAL] = gamma; }
                 break;
             }
             if (chief) {
@@ -187,7 +252,7 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
         // The decision may depend ONLY on what every workgroup holds with the same bits -- gamma_next, thresh, k, nlaunch -- and
         // never on what one workgroup knows alone (`bad`): a workgroup that stays would wait for granules nobody publishes.
         if (k >= 0 && k + 1 < nlaunch - 1 && !(gamma_next > thresh)) {
-            if (chief) { status[ST_PCG_DONE] = (gamma_next != gamma_next) ? 2 : 1; scalars[SC_RRFINAL] = gamma_next; }
+            if (chief) { atomicMax(&status[ST_PCG_DONE], (gamma_next != gamma_next) ? 2 : 1); scalars[SC_RRFINAL] = gamma_next; }
             converged = !(gamma_next != gamma_next);
             break;
         }
@@ -288,47 +353,56 @@ __global__ __launch_bounds__(PS_CP_NT) void k_cg_persist(
         __syncthreads();
         PS_CP_CLK(5);
         if (bad) {                                           // an exchange timed out: a breakdown the host answers with the other kernels
-            if (t == 0) { status[ST_PCG_DONE] = 2; status[ST_PERSIST_FAIL] = 1; }
+            if (t == 0) { atomicMax(&status[ST_PCG_DONE], 2); status[ST_PERSIST_FAIL] = 1; }
             break;
         }
         gamma = gamma_next; delta = 0.0;
 #pragma unroll
         for (int w2 = 0; w2 < PS_CP_NT / 64; ++w2) delta += rd[1][w2];
     }
-    if (dbg && chief) for (int i = 0; i < 8; ++i) dbg[i] += ck[i];
 #undef PS_CP_CLK
-    // ---- what the recovery reads (x^) and what a caller that looks at the state finds: written by the first workgroup
-    if (blockIdx.x == 0) {
-        if (converged && rec.x) {                            // the recovery of k_coarse_recover, on x^ as this workgroup holds it
-            const int nc = rec.ncb * D, nf = rec.nr * D;
-            __syncthreads();                                 // (every wave has left the loop: rn is free)
+    const long long t_left = dbg ? wall_clock64() : 0;       // (ck[4]: from here to the last store of rec.x)
+    // ---- the recovery of k_coarse_recover, on x^ as this workgroup holds it (every workgroup holds the same bits): y for the
+    // columns of the slice's nodes, then the slice's entries, all operands from LDS; the arithmetic is k_coarse_recover's own
+    // (coarse_recover_ylane / coarse_recover_entry, ps_k_cg_fused.h), sum for sum.  A workgroup whose exchange timed out is not
+    // here (converged is false): ST_PCG_DONE is then 2 whoever wrote last (atomicMax), and nothing downstream applies x.
+    if (converged && rec.x) {
+        __syncthreads();                                     // (every wave has left the loop: rn is free)
 #pragma unroll
-            for (int v = 0; v < PS_CP_NV; ++v) { const int i = t + v * PS_CP_NT; if (i < n) rn[i] = vx[v]; }
-            __syncthreads();
-            const double* xc = rn + nf;
-            for (int base = 0; base < nc; base += PS_CP_NT / 8) {
-                const int kq = base + t / 8, sub = t & 7;
+        for (int v = 0; v < PS_CP_NV; ++v) { const int i = t + v * PS_CP_NT; if (i < n) rn[i] = vx[v]; }
+        __syncthreads();
+        const int nc = rec.ncb * D, p0 = blockIdx.x * rec.pp, np = max(0, min(rec.nr, p0 + rec.pp) - p0);
+        if (np > 0) {                                        // (np, ncols, qa are the same in every thread of the workgroup)
+            const double* sLc = cp_rec;                      // maxcols x nc
+            const double* sOp = sLc + rec.maxcols * nc;      // B | Linv | pw0 | pw1 of np poses
+            double* sy = cp_rec + rec.maxcols * nc + rec.pp * (2 * DD + 2);    // maxcols: y of the slice's columns
+            const int32_t* spn = reinterpret_cast<const int32_t*>(sy + rec.maxcols);   // pp: pnode of the slice; then qa, ncols
+            const int qa = spn[rec.pp], ncols = spn[rec.pp + 1];
+            const double* xc = rn + rec.nr * D;
+            for (int base = 0; base < ncols; base += PS_CP_NT / 8) {
+                const int j = base + t / 8, sub = t & 7;
                 double v = 0.0;
-                if (kq < nc) for (int m = kq + sub; m < nc; m += 8) v += rec.Lci[(size_t)m * nc + kq] * xc[m];
+                if (j < ncols) v = coarse_recover_ylane(sLc + j * nc, 1, xc, qa * D + j, sub, nc);
                 v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-                if (kq < nc && sub == 0) yc[kq] = v;
+                if (j < ncols && sub == 0) sy[j] = v;
             }
             __syncthreads();
-            for (int e = t; e < nf; e += PS_CP_NT) {
-                const int i = e / D, c = e - i * D, q = rec.pnode[i];
-                const double w0 = rec.pw0[i], w1 = rec.pw1[i];
-                double z[D];
-#pragma unroll
-                for (int m = 0; m < D; ++m) z[m] = w0 * yc[q * D + m] + ((q + 1 < rec.ncb) ? w1 * yc[(q + 1) * D + m] : 0.0);
-                double v = 0.0;
-#pragma unroll
-                for (int a = 0; a < D; ++a) {
-                    double xhat = rn[i * D + a];
-#pragma unroll
-                    for (int m = 0; m < D; ++m) xhat += rec.Bmat[(size_t)i * DD + a * D + m] * z[m];
-                    v += rec.Linv[(size_t)i * DD + a * D + c] * xhat;
-                }
-                rec.x[e] = v;
+            const double *sB = sOp, *sLi = sOp + np * DD, *sw0 = sOp + 2 * np * DD, *sw1 = sw0 + np;
+            for (int e = t; e < np * D; e += PS_CP_NT) {
+                const int il = e / D, c = e - il * D, q = spn[il];
+                // (a node beyond the slice's columns cannot be: the columns span pnode[first] .. pnode[last] + 1, pnode ascending)
+                rec.x[(size_t)p0 * D + e] = coarse_recover_entry<D>(sy + (q - qa) * D, (q + 1 < rec.ncb) ? sy + (q + 1 - qa) * D : nullptr,
+                                                                    sw0[il], sw1[il], rn + (p0 + il) * D, sB + il * DD, sLi + il * DD, c);
+            }
+        }
+    }
+    // ---- what a caller that looks at the state finds: written by the first workgroup
+    if (blockIdx.x == 0) {
+        if (dbg) {                                           // (measurement build; dbg is the same in every thread)
+            __syncthreads();
+            if (t == 0) {
+                ck[4] = wall_clock64() - t_left;
+                for (int i = 0; i < 8; ++i) dbg[i] += ck[i];
             }
         }
 #pragma unroll

@@ -709,7 +709,8 @@ __global__ __launch_bounds__(1024) void k_coarse_rhs(
 }
 
 // x^_i = x~_f,i + pw0_i y[node_i] + pw1_i y[node_i + 1] with y = Lci^T x~_c ;  x_i = Linv_i^T x^_i
-// every workgroup first forms y (nc values) in LDS: y_k = sum_{m>=k} Lci[m][k] x~_c[m]
+// The arithmetic is coarse_recover_ylane / coarse_recover_entry (ps_k_cg_fused.h): one source for this kernel and k_cg_persist.
+// every workgroup first forms y (nc values) in LDS
 template <int D>
 __global__ __launch_bounds__(256) void k_coarse_recover(
     int nr, int ncb, const int32_t* __restrict__ pnode, const double* __restrict__ pw0,
@@ -724,10 +725,7 @@ __global__ __launch_bounds__(256) void k_coarse_recover(
     for (int base = 0; base < nc; base += blockDim.x / 8) {
         const int k = base + threadIdx.x / 8, sub = threadIdx.x & 7;
         double v = 0.0;
-        if (k < nc) {
-#pragma unroll 4
-            for (int m = k + sub; m < nc; m += 8) v += Lci[(size_t)m * nc + k] * xc[m];
-        }
+        if (k < nc) v = coarse_recover_ylane(Lci + k, nc, xc, k, sub, nc);
         v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
         if (k < nc && sub == 0) sy[k] = v;
     }
@@ -735,19 +733,8 @@ __global__ __launch_bounds__(256) void k_coarse_recover(
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nr * D) return;
     const int i = t / D, c = t % D, q = pnode[i];
-    const double w0 = pw0[i], w1 = pw1[i];
-    double z[D];                                         // interpolated coarse unknown at pose i
-#pragma unroll
-    for (int m = 0; m < D; ++m) z[m] = w0 * sy[q * D + m] + ((q + 1 < ncb) ? w1 * sy[(q + 1) * D + m] : 0.0);
-    double v = 0.0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        double xhat = xh[(size_t)i * D + a];
-#pragma unroll
-        for (int m = 0; m < D; ++m) xhat += Bmat[(size_t)i * D * D + a * D + m] * z[m];
-        v += Linv[(size_t)i * D * D + a * D + c] * xhat;
-    }
-    x[t] = v;
+    x[t] = coarse_recover_entry<D>(sy + q * D, (q + 1 < ncb) ? sy + (q + 1) * D : nullptr, pw0[i], pw1[i], xh + (size_t)i * D,
+                                   Bmat + (size_t)i * D * D, Linv + (size_t)i * D * D, c);
 }
 
 // ---------------------------------------------------------------------------
@@ -994,6 +981,8 @@ __global__ __launch_bounds__(256) void k_coarse_mreduce(
     const int a = live ? o / ncol : 0, c = live ? o % ncol : 0;
     double v = 0.0;
     if (live) {
+        // (all of a lane's loads issued before the first is added, 32 at a time, measured 5.85 -> 5.64 us per launch at C3: less than
+        //  the kernel's own launch-to-launch spread, 5.4-6.4, and not kept -- HISTORY.md, "One-launch CG: recover x in every workgroup")
         const int iend = shi[a / D];
 #pragma unroll 4
         for (int i = sub; i < iend; i += 8) v += Mpart[((size_t)i * nc + a) * ncol + c];

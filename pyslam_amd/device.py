@@ -495,6 +495,11 @@ class DeviceProblem:
         nat.check(self._lib.ps_get_info(self._h, C.byref(info)))
         return int(info.cg_persist_solves), int(info.cg_persist_failures)
 
+    def cg_persist_recover_counts(self):
+        """(one-launch folded CG launches that recover x inside the launch, launches that leave it to the gated k_coarse_recover
+        behind them) -- ps_get_option "cg_persist_recovered" / "cg_persist_recover_fallbacks" (option "cg_persist_recover")."""
+        return int(self.get_option('cg_persist_recovered')), int(self.get_option('cg_persist_recover_fallbacks'))
+
     def set_option(self, name, value):
         nat.check(self._lib.ps_set_option(self._h, name.encode(), float(value)))
 
