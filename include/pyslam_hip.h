@@ -426,6 +426,14 @@ int ps_debug_factor_blocks(ps_problem* h, double* r, double* j1, double* j2);
    tasks, row_ptr, col_idx, diag_slot (16 words; 0 for a table the problem does not have).  What holds the device
    structure build against the host builder bit for bit (tests/test_gpu_create.py); no reference counterpart. */
 int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* count);
+/* The run tables of the packed observation passes (csrc/ps_k_packed.h), device -> host.  *nwaves: runs on this handle (0: it keeps
+   the 16-lane kernels); run (nwaves, 4): {first landmark, one past the last, first row, rows} per wave -- the record the kernels
+   read under "packed_prefetch"; first (nwaves + 1): the run starts the record is made from; lm_ptr (variable landmarks + 1): first
+   row of every landmark slot; sq_part (ceil(nwaves / 4)): the partial sums of ||dx_point||^2, one per workgroup, as the last packed
+   back-substitution left them.  run / first / lm_ptr / sq_part may be NULL; capacity_waves: runs the caller's run / first /
+   sq_part have room for (refused when too few: call with NULLs first).  No reference counterpart. */
+int ps_debug_packed_runs(ps_problem* h, int32_t* nwaves, int32_t capacity_waves, int32_t* run, int32_t* first, int32_t* lm_ptr,
+                         double* sq_part);
 
 /* Tuning knobs.  [default; accepted values]: "0 / 1" is stored as value != 0; a range is refused outside it and truncated to
    an integer inside it; "any" is truncated and never refused.  One table holds every name with its parse rule, bounds, refusal
@@ -516,6 +524,12 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
                               operands fit "cg_persist_recover_lds" [146432; 0 .. 146432 bytes of dynamic LDS: what one workgroup per
                               compute unit leaves free]; else, and with 0, the gated k_coarse_recover runs behind the launch.  Speed
                               only, same bits.  Both handled ahead of the option table
+     "packed_prefetch"    [1; 0 / 1] the packed landmark pass, cost pass and back-substitution ("lm_packed") read their wave's run from one
+                              16-byte record (built beside the run starts at create time) and request their operands in four
+                              dependent trips to memory -- record + gate word; the lane's row + the run's landmark starts; the gathers
+                              the row names (x of its pose, pose, point, the whole observation-group record) + the head lane's point
+                              index; the point with the head lane's C^-1 and c -- instead of seven.  0: the load order they had
+                              before.  Speed only, same bits.  Handled ahead of the option table
      "schur_pipeline"     [1; 0 / 1] the Schur pair kernel with two chunks per wave in flight (k_schur_pairs_db); 0: k_schur_pairs
      "lm_packed" [1; 0 / 1], "band_part" [1; 0 / 1], "band_part_chunk" [0 auto; 0 .. 4096 nodes], "sync_refactor" [1; 0 / 1],
      "hold_across_steps" [1; 0 / 1]: round-5 kernels and schedules against their predecessors (DESIGN.md sections 0 and 3)
@@ -543,7 +557,8 @@ int ps_set_option(ps_problem* h, const char* name, double value);
    "cg_persist_recover", "cg_persist_recover_lds": the options; "cg_persist_recover_need": bytes of LDS the largest slice's operands
    take on this handle (0 before the coarse level is built, and where the one-launch folded CG does not apply);
    "cg_persist_recovered" / "cg_persist_recover_fallbacks": one-launch solves so far (ps_problem_info.cg_persist_solves) that recover
-   x inside the launch / that leave it to k_coarse_recover behind the launch. */
+   x inside the launch / that leave it to k_coarse_recover behind the launch.
+   "packed_prefetch": the option. */
 int ps_get_option(ps_problem* h, const char* name, double* value);
 
 /* hipEvent stage timers on the handle's stream (the reference has no tracing). */

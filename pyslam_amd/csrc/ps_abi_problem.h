@@ -37,8 +37,8 @@ int ps_warm_up(void) {
         // when it loads).  Asking for the attributes of the kernels of the whole-iteration paths resolves them here.
         hipFuncAttributes a;
 #define PS_TOUCH(...) (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&__VA_ARGS__))
-        PS_TOUCH(k_landmark_pass<false>); PS_TOUCH(k_landmark_pass_packed<false, false>); PS_TOUCH(k_landmark_pass_packed<false, true>); PS_TOUCH(k_backsub_packed<false>); PS_TOUCH(k_pose_pass<false>); PS_TOUCH(k_pose_finalize); PS_TOUCH(k_schur_pairs_db<0>);
-        PS_TOUCH(k_schur_combine); PS_TOUCH(k_backsub<false>); PS_TOUCH(k_cost_reproj<false>); PS_TOUCH(k_cost_packed<false>); PS_TOUCH(k_reduce3); PS_TOUCH(k_reduce_partials);
+        PS_TOUCH(k_landmark_pass<false>); PS_TOUCH(k_landmark_pass_packed<false, false, true>); PS_TOUCH(k_landmark_pass_packed<false, true, true>); PS_TOUCH(k_backsub_packed<false, true>); PS_TOUCH(k_pose_pass<false>); PS_TOUCH(k_pose_finalize); PS_TOUCH(k_schur_pairs_db<0>);
+        PS_TOUCH(k_schur_combine); PS_TOUCH(k_backsub<false>); PS_TOUCH(k_cost_reproj<false>); PS_TOUCH(k_cost_packed<false, true>); PS_TOUCH(k_reduce3); PS_TOUCH(k_reduce_partials);
         PS_TOUCH(k_copy2); PS_TOUCH(k_zero4); PS_TOUCH(k_lag_status_check);
         PS_TOUCH(k_block_jacobi_factor<6>); PS_TOUCH(k_scale_blocks<6>); PS_TOUCH(k_scale_blocks_p<6>); PS_TOUCH(k_rows_setup<6, PS_RS_REGS>); PS_TOUCH(k_rows_setup<6, PS_RS_EXACT>);
         PS_TOUCH(k_coarse_rowsums<6>); PS_TOUCH(k_coarse_matrix<6>); PS_TOUCH(k_coarse_chol<6, true>); PS_TOUCH(k_coarse_border<6>);

@@ -896,6 +896,20 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
     return 0;
 }
 
+// The run tables of the packed observation passes as the handle holds them (tests/test_gpu_packed_prefetch.py)
+int ps_debug_packed_runs(ps_problem* h, int32_t* nwaves, int32_t capacity_waves, int32_t* run, int32_t* first, int32_t* lm_ptr, double* sq_part) {
+    if (!h || !nwaves) return fail("null argument");
+    if (sync(h)) return -1;
+    const int nw = h->lmw_nwaves;
+    *nwaves = nw;
+    if ((run || first || sq_part) && capacity_waves < nw) return fail("ps_debug_packed_runs: capacity too small");
+    if (sq_part && nw) HIP_OK(hipMemcpy(sq_part, h->sq_part_l, (size_t)cdiv(nw, 4) * 8, hipMemcpyDeviceToHost));
+    if (run && nw) HIP_OK(hipMemcpy(run, h->lmw_run, (size_t)nw * sizeof(LmwRun), hipMemcpyDeviceToHost));
+    if (first && nw) HIP_OK(hipMemcpy(first, h->lmw_first, ((size_t)nw + 1) * 4, hipMemcpyDeviceToHost));
+    if (lm_ptr && h->nv > 0) HIP_OK(hipMemcpy(lm_ptr, h->lm_ptr, ((size_t)h->nv + 1) * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // What the lagged dense inverse of a live handle holds (csrc/ps_host_ldi.h; tests/test_gpu_ldi_kernels.py), as doubles (the
 // fp32 matrices convert exactly).  Waits for the solver stream, the side stream and the direct seed's stream / ev_ldi, copies,
 // and touches nothing: the state machine, the counters and the schedule are where they were.
@@ -981,6 +995,12 @@ int ps_set_option(ps_problem* h, const char* name, double value) {
         h->prelin_valid = h->prelm_valid = h->ride_valid = false;
         return 0;
     }
+    // the packed observation passes' operands in four dependent trips (csrc/ps_core.hip: packed_prefetch); 0: the load order before
+    if (!std::strcmp(name, "packed_prefetch")) {
+        h->packed_prefetch = value != 0 ? 1 : 0;
+        h->prelin_valid = h->prelm_valid = h->ride_valid = false;
+        return 0;
+    }
     h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     const char* refusal = nullptr;
     const int fx = ps_option_apply(*h, name, value, &refusal);
@@ -1010,6 +1030,7 @@ int ps_get_option(ps_problem* h, const char* name, double* value) {
     else if (n == "rows_setups") *value = (double)h->rows_setups;
     else if (n == "exact_row_setups") *value = (double)h->exact_row_setups;
     else if (n == "rows_lci_in_lds") *value = h->coarse_built && h->lagx_ok && h->rows_lci_lds ? 1.0 : 0.0;
+    else if (n == "packed_prefetch") *value = (double)h->packed_prefetch;
     else if (n == "cg_persist_recover") *value = (double)h->cg_persist_recover;
     else if (n == "cg_persist_recover_lds") *value = (double)h->cg_persist_recover_lds;
     else if (n == "cg_persist_recover_need") *value = h->coarse_built && h->cp_ok ? (double)h->cp_rec_lds : 0.0;

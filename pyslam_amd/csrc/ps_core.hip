@@ -495,6 +495,11 @@ struct ps_problem : PsOptions, PsCostHistory, PsCarried {
     // (lmw_nwaves + 1 entries; 0 waves: the 16-lane kernels -- a track longer than 16 observations, or an unobserved landmark)
     int32_t* lmw_first = nullptr;
     int lmw_nwaves = 0;
+    // option "packed_prefetch" (ps_set_option, ahead of the table): the packed kernels read their run from ONE 16-byte record per
+    // wave (lmw_run: lmw_nwaves records, built beside lmw_first) and ask for their operands in four dependent trips instead of
+    // seven (ps_k_packed.h: PF).  0: the load order they had before.  Every value is the same either way.
+    LmwRun* lmw_run = nullptr;
+    int packed_prefetch = 1;
     // lagged dense inverse of the reduced system as the CG preconditioner (ps_k_ldi.h / ps_host_ldi.h)
     bool ldi_ready = false;         // buffers allocated
     int ldi_n = 0, ldi_np = 0, ldi_kp = 0;

@@ -193,7 +193,7 @@ struct ObsBuilder {
     virtual int place_pobs() = 0;
     virtual std::unique_ptr<PairBuilder> pair_builder() = 0;
     virtual int landmark_extent(int* most, int* fewest) = 0;                   // observations per variable landmark
-    virtual int place_run_starts(int W, int nw) = 0;                           // lmw_first of the packed landmark pass
+    virtual int place_run_starts(int W, int nw) = 0;                           // lmw_first / lmw_run of the packed landmark pass
 };
 
 // scratch of one device build: freed when the build ends
@@ -309,8 +309,8 @@ struct DevObsBuild : ObsBuilder {
         return 0;
     }
     int place_run_starts(int W, int nw) override {
-        if (h->alloc(&h->lmw_first, (size_t)nw + 1, true)) return -1;
-        hipLaunchKernelGGL(k_lmw_items, dim3(cdiv(nw + 1, 256)), dim3(256), 0, h->stream, h->nv, nw, W, h->lm_ptr, h->lmw_first);
+        if (h->alloc(&h->lmw_first, (size_t)nw + 1, true) || h->alloc(&h->lmw_run, (size_t)nw, true)) return -1;
+        hipLaunchKernelGGL(k_lmw_items, dim3(cdiv(nw + 1, 256)), dim3(256), 0, h->stream, h->nv, nw, W, h->lm_ptr, h->lmw_first, h->lmw_run);
         return 0;
     }
 };

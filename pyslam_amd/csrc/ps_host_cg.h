@@ -1130,10 +1130,13 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
 #define PS_LM_LAUNCH(W) hipLaunchKernelGGL(k_landmark_pass<W>, dim3(cdiv(h->nv, 256 / PS_LM_GROUP)), dim3(256), 0, h->stream, h->nv, h->lm_ptr, \
                            h->lm_point, h->lobs, h->poses, h->points, h->pose_rid, h->ogroups, lambda, h->Z,                       \
                            h->Cinv, h->cvec, h->status, h->lm_ablate, wl)
-#define PS_LMP_LAUNCH(W) hipLaunchKernelGGL((k_landmark_pass_packed<W, false>), dim3(cdiv(h->lmw_nwaves, 4)), dim3(256), 0, h->stream, h->lmw_nwaves, \
-                           h->lmw_first, h->lm_ptr, h->lm_point, h->lobs, h->poses, h->points, h->pose_rid, h->ogroups, lambda, h->Z,      \
+#define PS_LMP_LAUNCH(W, PF) hipLaunchKernelGGL((k_landmark_pass_packed<W, false, PF>), dim3(cdiv(h->lmw_nwaves, 4)), dim3(256), 0, h->stream, h->lmw_nwaves, \
+                           h->lmw_first, h->lmw_run, h->lm_ptr, h->lm_point, h->lobs, h->poses, h->points, h->pose_rid, h->ogroups, lambda, h->Z,      \
                            h->Cinv, h->cvec, h->status, wl, (const int32_t*)nullptr, (double*)nullptr, (long long*)nullptr, 0LL)
-        if (h->lm_packed && h->lmw_nwaves > 0 && !h->lm_ablate) { if (h->wide_obs) PS_LMP_LAUNCH(true); else PS_LMP_LAUNCH(false); }
+        if (h->lm_packed && h->lmw_nwaves > 0 && !h->lm_ablate) {
+            if (h->packed_prefetch) { if (h->wide_obs) PS_LMP_LAUNCH(true, true); else PS_LMP_LAUNCH(false, true); }
+            else if (h->wide_obs) PS_LMP_LAUNCH(true, false); else PS_LMP_LAUNCH(false, false);
+        }
         else if (h->wide_obs) PS_LM_LAUNCH(true); else PS_LM_LAUNCH(false);
 #undef PS_LMP_LAUNCH
 #undef PS_LM_LAUNCH
@@ -1223,12 +1226,11 @@ int cost_partials_pass(ps_problem* h, int include_all, const int32_t* gate) {
         // summed it on its way (the tail of an iteration that expects a successor, the start cost) or this one did
         const ObsWide wl{h->sidx_l, h->stiff_tab};
         const int nbl = cdiv(h->lmw_nwaves, 4);
-        if (h->wide_obs)
-            hipLaunchKernelGGL(k_cost_packed<true>, dim3(nbl), dim3(256), 0, h->stream, h->lmw_nwaves, h->lmw_first, h->lm_ptr, h->lm_point,
-                               h->lobs, h->poses, h->points, h->ogroups, h->cost_partials, gate, wl);
-        else
-            hipLaunchKernelGGL(k_cost_packed<false>, dim3(nbl), dim3(256), 0, h->stream, h->lmw_nwaves, h->lmw_first, h->lm_ptr, h->lm_point,
-                               h->lobs, h->poses, h->points, h->ogroups, h->cost_partials, gate, wl);
+#define PS_CSP_LAUNCH(W, PF) hipLaunchKernelGGL((k_cost_packed<W, PF>), dim3(nbl), dim3(256), 0, h->stream, h->lmw_nwaves, h->lmw_first, h->lmw_run, \
+                           h->lm_ptr, h->lm_point, h->lobs, h->poses, h->points, h->ogroups, h->cost_partials, gate, wl)
+        if (h->packed_prefetch) { if (h->wide_obs) PS_CSP_LAUNCH(true, true); else PS_CSP_LAUNCH(false, true); }
+        else if (h->wide_obs) PS_CSP_LAUNCH(true, false); else PS_CSP_LAUNCH(false, false);
+#undef PS_CSP_LAUNCH
         n += nbl;
     } else if (h->N > 0) {
         const ObsWide wl{h->sidx_l, h->stiff_tab};
@@ -1279,8 +1281,9 @@ int backsub(ps_problem* h, const int32_t* gate = nullptr, bool fuse_update = fal
     const double lam_ratio = h->lin_lambda / (1.0 + h->lin_lambda);
     if (h->lm_packed && h->lmw_nwaves > 0) {                // lanes packed by observation (ps_k_packed.h)
         const int nbl = cdiv(h->lmw_nwaves, 4);               // (= nsq_l_now(h): the partials of ||dx_l||^2 k_reduce3 sums)
-#define PS_BSP_LAUNCH(MD, ...) hipLaunchKernelGGL(k_backsub_packed<MD>, dim3(nbl + (fuse_update ? h->nsq_p : 0)), dim3(256), 0, h->stream, h->lmw_nwaves, \
-                               h->lmw_first, h->lm_ptr, h->Z, h->Cinv, h->cvec, h->x, h->dxl, h->sq_part_l, gate, nbl, __VA_ARGS__)
+#define PS_BSP_LAUNCH1(MD, PF, ...) hipLaunchKernelGGL((k_backsub_packed<MD, PF>), dim3(nbl + (fuse_update ? h->nsq_p : 0)), dim3(256), 0, h->stream, h->lmw_nwaves, \
+                               h->lmw_first, h->lmw_run, h->lm_ptr, h->Z, h->Cinv, h->cvec, h->x, h->dxl, h->sq_part_l, gate, nbl, __VA_ARGS__)
+#define PS_BSP_LAUNCH(MD, ...) do { if (h->packed_prefetch) PS_BSP_LAUNCH1(MD, true, __VA_ARGS__); else PS_BSP_LAUNCH1(MD, false, __VA_ARGS__); } while (0)
         if (h->lm_md) {
             if (fuse_update) PS_BSP_LAUNCH(true, h->lm_point, h->points, h->P, h->pose_rid, h->poses, h->sq_part_p, hearly, eseq, h->md_part_l, lam_ratio);
             else PS_BSP_LAUNCH(true, (const int32_t*)nullptr, (double*)nullptr, 0, (const int32_t*)nullptr, (double*)nullptr, (double*)nullptr, hearly, eseq,
@@ -1290,6 +1293,7 @@ int backsub(ps_problem* h, const int32_t* gate = nullptr, bool fuse_update = fal
         else
             PS_BSP_LAUNCH(false, (const int32_t*)nullptr, (double*)nullptr, 0, (const int32_t*)nullptr, (double*)nullptr, (double*)nullptr, hearly, eseq);
 #undef PS_BSP_LAUNCH
+#undef PS_BSP_LAUNCH1
         return 0;
     }
 #define PS_BS_LAUNCH(MD, ...) hipLaunchKernelGGL(k_backsub<MD>, dim3(h->nsq_l16 + (fuse_update ? h->nsq_p : 0)), dim3(256), 0, h->stream, h->nv, h->lm_ptr, \
@@ -1371,10 +1375,11 @@ int lm_cost_enqueue(ps_problem* h, double lambda, const int32_t* gate) {
     {
         StageTimer t(h, PS_ST_LANDMARK);
         const ObsWide wl{h->sidx_l, h->stiff_tab};
-#define PS_LMC_LAUNCH(W) hipLaunchKernelGGL((k_landmark_pass_packed<W, true>), dim3(nbl), dim3(256), 0, h->stream, h->lmw_nwaves, h->lmw_first,    \
-                           h->lm_ptr, h->lm_point, h->lobs, h->poses, h->points, h->pose_rid, h->ogroups, lambda, h->Z, h->Cinv, h->cvec,        \
+#define PS_LMC_LAUNCH(W, PF) hipLaunchKernelGGL((k_landmark_pass_packed<W, true, PF>), dim3(nbl), dim3(256), 0, h->stream, h->lmw_nwaves, h->lmw_first,    \
+                           h->lmw_run, h->lm_ptr, h->lm_point, h->lobs, h->poses, h->points, h->pose_rid, h->ogroups, lambda, h->Z, h->Cinv, h->cvec,        \
                            h->status, wl, gate, h->cost_partials, h->h_lmfail_dev + (h->prelm_tag & 1), h->prelm_tag)
-        if (h->wide_obs) PS_LMC_LAUNCH(true); else PS_LMC_LAUNCH(false);
+        if (h->packed_prefetch) { if (h->wide_obs) PS_LMC_LAUNCH(true, true); else PS_LMC_LAUNCH(false, true); }
+        else if (h->wide_obs) PS_LMC_LAUNCH(true, false); else PS_LMC_LAUNCH(false, false);
 #undef PS_LMC_LAUNCH
     }
     int n = nbl;

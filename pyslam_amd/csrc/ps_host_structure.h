@@ -140,7 +140,9 @@ struct HostObsBuild : ObsBuilder {
         const int nv = h->nv;
         std::vector<int32_t> first((size_t)nw + 1, nv);
         for (int w = 0, v = 0; w < nw; ++w) { while (v < nv && lm_ptr[v] < W * w) ++v; first[w] = v; }
-        return h->upload(&h->lmw_first, first);
+        std::vector<LmwRun> run((size_t)nw);
+        for (int w = 0; w < nw; ++w) run[w] = LmwRun{first[w], first[w + 1], lm_ptr[first[w]], lm_ptr[first[w + 1]] - lm_ptr[first[w]]};
+        return (h->upload(&h->lmw_first, first) || h->upload(&h->lmw_run, run)) ? -1 : 0;
     }
 };
 

@@ -27,25 +27,37 @@ __global__ __launch_bounds__(256) void k_lmw_maxobs(int nv, const int32_t* __res
     if ((threadIdx.x & 63) == 0 && mx >= 0) { atomicMax(out, mx); atomicMin(out + 1, mn); }
 }
 
-// first[w] = the first landmark whose first row is >= W w  (first[nwaves] = nv)
-__global__ __launch_bounds__(256) void k_lmw_items(int nv, int nwaves, int W, const int32_t* __restrict__ lm_ptr, int32_t* __restrict__ first) {
+// The run of wave w as ONE 16-byte record (option "packed_prefetch"): what lmw_first[w], lmw_first[w + 1] and the two lm_ptr
+// entries behind them say, so that a wave knows its landmarks and its rows after one load instead of two dependent ones.
+struct __attribute__((aligned(16))) LmwRun { int32_t v0, v1, row0, nrows; };
+
+// the first landmark whose first row is >= target
+PS_DEV int lmw_first_landmark(int nv, int target, const int32_t* __restrict__ lm_ptr) {
+    int lo = 0, hi = nv;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (lm_ptr[mid] < target) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+// first[w] = the first landmark whose first row is >= W w  (first[nwaves] = nv); run[w] = the record of first[w], first[w + 1]
+__global__ __launch_bounds__(256) void k_lmw_items(int nv, int nwaves, int W, const int32_t* __restrict__ lm_ptr, int32_t* __restrict__ first,
+                                                   LmwRun* __restrict__ run) {
     const int w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w > nwaves) return;
     if (w == nwaves) { first[w] = nv; return; }
-    const int target = W * w;
-    int lo = 0, hi = nv;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (lm_ptr[mid] < target) lo = mid + 1; else hi = mid; }
-    first[w] = lo;
+    const int v0 = lmw_first_landmark(nv, W * w, lm_ptr);
+    const int v1 = w + 1 == nwaves ? nv : lmw_first_landmark(nv, W * (w + 1), lm_ptr);
+    first[w] = v0;
+    const int row0 = lm_ptr[v0];
+    run[w] = LmwRun{v0, v1, row0, lm_ptr[v1] - row0};
 }
 
 // the run's segment structure for this lane: landmark v, its first lane, one past its last lane; `nrows` rows in the run
 struct LmwSeg { int v, lane0, lane1, nrows, row0; bool valid, head; };
-PS_DEV LmwSeg lmw_segment(int v0, int v1, const int32_t* __restrict__ lm_ptr, int lane, volatile int32_t* flags /* LDS, 64 */) {
+// `start`: lane k < nlm holds the first row of landmark v0 + k
+PS_DEV LmwSeg lmw_segment_of(int v0, int nlm, int row0, int nrows, int start, int lane, volatile int32_t* flags /* LDS, 64 */) {
     LmwSeg s;
-    const int nlm = v1 - v0;                                 // (<= 64: every landmark of a run has at least one row, a run at most 64)
-    const int start = (lane < nlm) ? lm_ptr[v0 + lane] : 0;  // lane k: first row of landmark v0 + k
-    s.row0 = lm_ptr[v0];
-    s.nrows = lm_ptr[v1] - s.row0;
+    s.row0 = row0;
+    s.nrows = nrows;
     flags[lane] = 0;
     __builtin_amdgcn_wave_barrier();
     if (lane < nlm) flags[start - s.row0] = 1;               // (a run has at most 64 rows, so at most 64 landmarks)
@@ -61,6 +73,36 @@ PS_DEV LmwSeg lmw_segment(int v0, int v1, const int32_t* __restrict__ lm_ptr, in
     s.head = s.valid && lane == s.lane0;
     return s;
 }
+PS_DEV LmwSeg lmw_segment(int v0, int v1, const int32_t* __restrict__ lm_ptr, int lane, volatile int32_t* flags /* LDS, 64 */) {
+    const int nlm = v1 - v0;                                 // (<= 64: every landmark of a run has at least one row, a run at most 64)
+    const int start = (lane < nlm) ? lm_ptr[v0 + lane] : 0;  // lane k: first row of landmark v0 + k
+    const int row0 = lm_ptr[v0];
+    return lmw_segment_of(v0, nlm, row0, lm_ptr[v1] - row0, start, lane, flags);
+}
+
+// PF (option "packed_prefetch", default): the three packed kernels ask for their operands in as few dependent trips to memory
+// as the data allow.  A wave of these kernels does one run and leaves -- nearly all of them are resident at once, and a launch
+// lasts about as long as ONE wave's chain of dependent loads -- so what counts is how many times a wave waits, not what it moves:
+//   trip A  the run record (LmwRun: one scalar load through the wave-uniform index) and the gate word together;
+//   trip B  what the static structure addresses: the lane's row (Z row / observation record) and lm_ptr[v0 + lane] for the head mask;
+//   trip C  what the row's contents address: x[rid], pose, point, pose_rid, the whole ObsGroup record (obs_group_fetch, ps_math.h),
+//           and the head lane's lm_point;
+//   trip D  (back-substitution) points[lm_point[v]] with the head lane's C^-1 and c, in front of the LDS sums.
+// Every sum, its order and every fma chain are those of the PF = false form, which keeps the load order the kernels had before
+// (lmw_first -> lm_ptr -> rows -> ...): the results are the same bits.  Gathers indexed by table CONTENTS stay behind the gate test.
+//
+// The run record of this wave (zeros past the last run) and the gate word (1 without a gate), requested together and both
+// waited for here: the empty statement keeps the record's load in front of the gate test instead of behind it.
+PS_DEV LmwRun lmw_run_and_gate(const LmwRun* __restrict__ lmw_run, int nwaves, int gw /* wave-uniform */, const int32_t* __restrict__ gate,
+                               int& gate_word) {
+    int4 r = make_int4(0, 0, 0, 0);
+    if (gw < nwaves) r = reinterpret_cast<const int4*>(lmw_run)[gw];
+    int g = 1;
+    if (gate) g = gate[ST_PCG_DONE];
+    asm volatile("" : "+s"(r.x), "+s"(r.y), "+s"(r.z), "+s"(r.w), "+s"(g));
+    gate_word = g;
+    return LmwRun{r.x, r.y, r.z, r.w};
+}
 
 // COST (round 5): the pass ALSO sums the robust cost of its observations at this linearisation point (ReprojEval::cost, which
 // the evaluation forms anyway) into one partial per workgroup -- the "cost after the step" of an iteration IS the cost at the
@@ -69,9 +111,10 @@ PS_DEV LmwSeg lmw_segment(int v0, int v1, const int32_t* __restrict__ lm_ptr, in
 // gated like the rest of the tail (`gate`: a no-op until the reduced solve has converged), and a landmark block that is not
 // positive definite is reported through `fail_word` (pinned host memory, stamped with `fail_tag`) instead of the status words:
 // it belongs to the NEXT call's linearisation, whose status the host folds it into (wait_published).
-template <bool WIDE, bool COST>
+template <bool WIDE, bool COST, bool PF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PS_LM_WAVES, 8))) void k_landmark_pass_packed(
-    int nwaves, const int32_t* __restrict__ lmw_first, const int32_t* __restrict__ lm_ptr, const int32_t* __restrict__ lm_point,
+    int nwaves, const int32_t* __restrict__ lmw_first, const LmwRun* __restrict__ lmw_run, const int32_t* __restrict__ lm_ptr,
+    const int32_t* __restrict__ lm_point,
     const LObs* __restrict__ lobs, const double* __restrict__ poses,
     const double* __restrict__ points, const int32_t* __restrict__ pose_rid,
     const ObsGroup* __restrict__ groups, double lambda,
@@ -83,27 +126,66 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PS_LM_WAVES
     __shared__ __attribute__((aligned(16))) double zst[4][64 * PS_ZROW];    // sums (64 x 9), then C^-1 per segment, then the Z rows
     __shared__ int32_t flags[4][64];
     __shared__ double csum[16];
-    if (COST && gate && gate[ST_PCG_DONE] != 1) return;      // (2 = CG breakdown: the host falls back, nothing is applied)
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, gw = blockIdx.x * 4 + wv;
+    const int lane = threadIdx.x & 63;
+    int wv, v0, v1;
+    LmwRun rn = {0, 0, 0, 0};
+    if (PF) {                                                 // trip A
+        wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        int gate_word;
+        rn = lmw_run_and_gate(lmw_run, nwaves, blockIdx.x * 4 + wv, COST ? gate : nullptr, gate_word);
+        if (COST && gate_word != 1) return;
+        v0 = rn.v0; v1 = rn.v1;
+    } else {
+        if (COST && gate && gate[ST_PCG_DONE] != 1) return;  // (2 = CG breakdown: the host falls back, nothing is applied)
+        wv = threadIdx.x >> 6;
+        const int gw = blockIdx.x * 4 + wv;
+        v0 = gw < nwaves ? lmw_first[gw] : 0; v1 = gw < nwaves ? lmw_first[gw + 1] : 0;
+    }
     double obs_cost = 0.0;
-    const int v0 = gw < nwaves ? lmw_first[gw] : 0, v1 = gw < nwaves ? lmw_first[gw + 1] : 0;
     if (v1 > v0) {                                            // (wave-uniform)
-    const LmwSeg sg = lmw_segment(v0, v1, lm_ptr, lane, flags[wv]);
     double* sm = zst[wv];
-    const int i = sg.row0 + lane;
     ReprojEval ev;
     bool variable_pose = false;
     int rid_of_obs = -1;
     double hb[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    LmwSeg sg;
+    if (PF) {
+        const int nlm = v1 - v0, i = rn.row0 + lane;
+        const int start = (lane < nlm) ? lm_ptr[v0 + lane] : 0;                  // trip B (with the row below)
+        if (lane < rn.nrows) {
+            const LObs o = lobs[i];
+            const int si = WIDE ? wide.sidx[i] : 0;
+            const int pose = PS_POSE_OF(o), grp = PS_GRP_OF(o);                   // trip C
+            const Se3 T = se3_load(poses + 12 * pose);
+            // (a row of the run belongs to a variable landmark: its point is lm_point[v] of its segment, known before the mask)
+            const double pw[3] = {points[3 * (size_t)o.point], points[3 * (size_t)o.point + 1], points[3 * (size_t)o.point + 2]};
+            rid_of_obs = pose_rid[pose];
+            double Sl[9];
+            if (WIDE) {
+                const double* sp = wide.stiff + 9 * (size_t)si;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) Sl[k] = sp[k];
+            }
+            const int g0 = __builtin_amdgcn_readfirstlane(grp);
+            const ObsGroup g = obs_group_fetch(groups, g0);
+            reproj_eval_obs_fetched<true, true, WIDE>(T, pw, &o.u, groups, grp, g0, g, Sl, ev);
+        }
+        sg = lmw_segment_of(v0, nlm, rn.row0, rn.nrows, start, lane, flags[wv]);
+    } else {
+        sg = lmw_segment(v0, v1, lm_ptr, lane, flags[wv]);
+        const int i = sg.row0 + lane;
+        if (sg.valid) {
+            const int pt = lm_point[sg.v];
+            const double pw[3] = {points[3 * (size_t)pt], points[3 * (size_t)pt + 1], points[3 * (size_t)pt + 2]};
+            const LObs o = lobs[i];
+            const int pose = PS_POSE_OF(o);
+            const Se3 T = se3_load(poses + 12 * pose);
+            rid_of_obs = pose_rid[pose];
+            reproj_eval_obs<true, true, WIDE>(T, pw, &o.u, groups, PS_GRP_OF(o), wide, i, ev);
+        }
+    }
     if (sg.valid) {
-        const int pt = lm_point[sg.v];
-        const double pw[3] = {points[3 * (size_t)pt], points[3 * (size_t)pt + 1], points[3 * (size_t)pt + 2]};
-        const LObs o = lobs[i];
-        const int pose = PS_POSE_OF(o);
-        const Se3 T = se3_load(poses + 12 * pose);
-        rid_of_obs = pose_rid[pose];
         variable_pose = rid_of_obs >= 0;
-        reproj_eval_obs<true, true, WIDE>(T, pw, &o.u, groups, PS_GRP_OF(o), wide, i, ev);
         if (COST) obs_cost = ev.cost;
         const double* J = ev.Jl;
 #pragma unroll
@@ -212,13 +294,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PS_LM_WAVES
 // The robust cost alone, in the landmark pass's structure: wave w evaluates the rows of run w, one per lane, a workgroup writes
 // one partial -- the SAME partial sums, bit for bit, as k_landmark_pass_packed<.., true> forms (the cost of an observation is
 // a function of its inputs alone: ps_math.h), so a cost is the same number whichever of the two produced it.
-template <bool WIDE>
+template <bool WIDE, bool PF>
 __global__ __launch_bounds__(256) void k_cost_packed(
-    int nwaves, const int32_t* __restrict__ lmw_first, const int32_t* __restrict__ lm_ptr, const int32_t* __restrict__ lm_point,
+    int nwaves, const int32_t* __restrict__ lmw_first, const LmwRun* __restrict__ lmw_run, const int32_t* __restrict__ lm_ptr,
+    const int32_t* __restrict__ lm_point,
     const LObs* __restrict__ lobs, const double* __restrict__ poses, const double* __restrict__ points,
     const ObsGroup* __restrict__ groups, double* __restrict__ cost_part, const int32_t* __restrict__ gate, ObsWide wide)
 {
     __shared__ double csum[16];
+    if (PF) {
+        const int lane = threadIdx.x & 63, gw = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        int gate_word;
+        const LmwRun rn = lmw_run_and_gate(lmw_run, nwaves, gw, gate, gate_word);           // trip A
+        if (gate_word != 1) return;
+        double c = 0.0;
+        if (lane < rn.nrows) {
+            const int i = rn.row0 + lane;
+            const LObs o = lobs[i];                                                           // trip B
+            const int si = WIDE ? wide.sidx[i] : 0;
+            const int grp = PS_GRP_OF(o);                                                     // trip C
+            const Se3 T = se3_load(poses + 12 * PS_POSE_OF(o));
+            const double pw[3] = {points[3 * (size_t)o.point], points[3 * (size_t)o.point + 1], points[3 * (size_t)o.point + 2]};
+            double Sl[9];
+            if (WIDE) {
+                const double* sp = wide.stiff + 9 * (size_t)si;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) Sl[k] = sp[k];
+            }
+            const int g0 = __builtin_amdgcn_readfirstlane(grp);
+            const ObsGroup g = obs_group_fetch(groups, g0);
+            ReprojEval ev;
+            reproj_eval_obs_fetched<false, false, WIDE>(T, pw, &o.u, groups, grp, g0, g, Sl, ev);
+            c = ev.cost;
+        }
+        c = block_sum(c, csum);
+        if (threadIdx.x == 0) cost_part[blockIdx.x] = c;
+        return;
+    }
     if (gate && gate[ST_PCG_DONE] != 1) return;      // (2 = CG breakdown: the host falls back, nothing is applied)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, gw = blockIdx.x * 4 + wv;
     double c = 0.0;
@@ -242,9 +354,9 @@ __global__ __launch_bounds__(256) void k_cost_packed(
 // back-substitution, the same packing: one Z row per lane, the landmark's three sums by its head lane
 // MD (adaptive LM, ps_lm_iteration): the head lane also forms its landmark's terms of the model decrease (lm_landmark_terms,
 // ps_k_lm.h), one partial per workgroup into md_part; false: the kernel as it was, the two last arguments unused
-template <bool MD>
+template <bool MD, bool PF>
 __global__ __launch_bounds__(256) void k_backsub_packed(
-    int nwaves, const int32_t* __restrict__ lmw_first, const int32_t* __restrict__ lm_ptr,
+    int nwaves, const int32_t* __restrict__ lmw_first, const LmwRun* __restrict__ lmw_run, const int32_t* __restrict__ lm_ptr,
     const double* __restrict__ Z, const double* __restrict__ Cinv, const double* __restrict__ cvec,
     const double* __restrict__ xp, double* __restrict__ dxl,
     double* __restrict__ sq_part /* one partial of ||dx_l||^2 per workgroup */,
@@ -257,7 +369,14 @@ __global__ __launch_bounds__(256) void k_backsub_packed(
     __shared__ double lds[16];
     __shared__ double sm3[4][64 * 3];
     __shared__ int32_t flags[4][64];
-    const bool closed = gate && gate[ST_PCG_DONE] != 1;
+    LmwRun rn = {0, 0, 0, 0};
+    bool closed;
+    if (PF) {                                        // trip A (a retracting workgroup's waves lie past the last run: zeros)
+        int gate_word;
+        rn = lmw_run_and_gate(lmw_run, nwaves, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), gate, gate_word);
+        closed = gate_word != 1;
+    } else
+        closed = gate && gate[ST_PCG_DONE] != 1;
     if (hearly && blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<volatile long long*>(hearly) = closed ? -eseq : eseq;
     if (closed) return;                              // (2 = CG breakdown: the host falls back, nothing is applied)
     if ((int)blockIdx.x >= nblk_l) {
@@ -277,6 +396,73 @@ __global__ __launch_bounds__(256) void k_backsub_packed(
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, gw = blockIdx.x * 4 + wv;
     double sq = 0.0, md = 0.0;
+    if (PF) {
+        if (rn.nrows > 0) {                                   // (wave-uniform)
+            const int nlm = rn.v1 - rn.v0;
+            // trip B: the lane's row, the word that names its pose among it, and the first rows of the run's landmarks
+            const int start = (lane < nlm) ? lm_ptr[rn.v0 + lane] : 0;
+            double z[12];
+            int rid = -1;
+            if (lane < rn.nrows) {
+                const double* zr = Z + PS_ZROW * (size_t)(rn.row0 + lane);
+                const double2* zq = reinterpret_cast<const double2*>(zr);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) { const double2 t = zq[k]; z[2 * k] = t.x; z[2 * k + 1] = t.y; }
+                rid = (int)zr[12];
+            }
+            const LmwSeg sg = lmw_segment_of(rn.v0, nlm, rn.row0, rn.nrows, start, lane, flags[wv]);
+            // trip C: x of the row's pose by every lane, the point's index by the head lane
+            const size_t v = (size_t)sg.v;
+            double x[6], m[6], cv[3], p[3];
+            int pt = 0;
+            if (rid >= 0) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) x[k] = xp[6 * (size_t)rid + k];
+            }
+            if (sg.head && points) pt = lm_point[v];
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+            if (rid >= 0) {
+                // Z^T x = M^T (x_rho - pc x x_phi)
+                const double y0 = x[0] - (z[10] * x[5] - z[11] * x[4]);
+                const double y1 = x[1] - (z[11] * x[3] - z[9] * x[5]);
+                const double y2 = x[2] - (z[9] * x[4] - z[10] * x[3]);
+                a0 = -(z[0] * y0 + z[3] * y1 + z[6] * y2);
+                a1 = -(z[1] * y0 + z[4] * y1 + z[7] * y2);
+                a2 = -(z[2] * y0 + z[5] * y1 + z[8] * y2);
+            }
+            // trip D, in front of the LDS sums: the head lane's C^-1, c and point.  (Their addresses are known since the head
+            // mask; asked for here, when the row and x have been consumed, they cost no trip more and the kernel keeps its
+            // 64 registers: eight waves per SIMD, all runs of a C3-sized problem resident at once.)
+            if (sg.head) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) m[k] = Cinv[6 * v + k];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) cv[k] = cvec[3 * v + k];
+                if (points) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) p[k] = points[3 * (size_t)pt + k];
+                }
+            }
+            double* sm = sm3[wv];
+            sm[3 * lane] = a0; sm[3 * lane + 1] = a1; sm[3 * lane + 2] = a2;
+            __builtin_amdgcn_wave_barrier();
+            if (sg.head) {
+                double b0 = 0.0, b1 = 0.0, b2 = 0.0;
+                for (int l = lane; l < sg.lane1; ++l) { b0 += sm[3 * l]; b1 += sm[3 * l + 1]; b2 += sm[3 * l + 2]; }
+                b0 += cv[0]; b1 += cv[1]; b2 += cv[2];       // dx = M^T a
+                const double d0 = m[0] * b0 + m[1] * b1 + m[3] * b2;
+                const double d1 = m[2] * b1 + m[4] * b2;
+                const double d2 = m[5] * b2;
+                dxl[3 * v] = d0; dxl[3 * v + 1] = d1; dxl[3 * v + 2] = d2;
+                sq = d0 * d0 + d1 * d1 + d2 * d2;
+                if (MD) md = lm_landmark_terms(m, cv, d0, d1, d2, lam_ratio);
+                if (points) {
+                    double* po = points + 3 * (size_t)pt;
+                    po[0] = p[0] + d0; po[1] = p[1] + d1; po[2] = p[2] + d2;
+                }
+            }
+        }
+    } else {
     const int v0 = gw < nwaves ? lmw_first[gw] : 0, v1 = gw < nwaves ? lmw_first[gw + 1] : 0;
     if (v1 > v0) {                                            // (wave-uniform)
         const LmwSeg sg = lmw_segment(v0, v1, lm_ptr, lane, flags[wv]);
@@ -318,6 +504,7 @@ __global__ __launch_bounds__(256) void k_backsub_packed(
                 pt[0] += d0; pt[1] += d1; pt[2] += d2;
             }
         }
+    }
     }
     sq = block_sum(sq, lds);
     if (threadIdx.x == 0) sq_part[blockIdx.x] = sq;

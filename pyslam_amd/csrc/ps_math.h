@@ -429,3 +429,32 @@ PS_DEV void reproj_eval_obs(const Se3& T, const double* __restrict__ pw, const d
         if (grp == g0) { reproj_eval_s<WITH_JP, WITH_JL>(T, pw, uvd, groups[g0], Sl, o); break; }
     }
 }
+
+// The WHOLE group record of the first active lane's group, requested at once (option "packed_prefetch", ps_k_packed.h).
+// reproj_eval_grp leaves it to the compiler when a field is fetched, and the fields arrive in three dependent pieces -- the loss
+// and camera ids the branches test first, the rest inside them.  Here every field is asked for in front of the evaluation, in
+// the same trip as the caller's pose and point gathers; the empty statement below is what keeps the compiler from moving a
+// field's load back down to its first use.  The evaluation itself is reproj_eval_s, untouched: the same bits.
+PS_DEV ObsGroup obs_group_fetch(const ObsGroup* __restrict__ groups, int g0 /* wave-uniform */) {
+    ObsGroup g = groups[g0];
+    asm volatile("" : "+s"(g.cu), "+s"(g.cv), "+s"(g.fu), "+s"(g.fv), "+s"(g.b), "+s"(g.loss_k), "+s"(g.loss_id), "+s"(g.cam_type));
+    asm volatile("" : "+s"(g.S[0]), "+s"(g.S[1]), "+s"(g.S[2]), "+s"(g.S[3]), "+s"(g.S[4]), "+s"(g.S[5]), "+s"(g.S[6]), "+s"(g.S[7]), "+s"(g.S[8]));
+    return g;
+}
+
+// reproj_eval_obs with the record of the first group in hand (`gfirst` = obs_group_fetch(groups, readfirstlane(grp)) by the
+// lanes that call this): the waterfall over mixed waves is the same, its first pass finds its record loaded.  `Sl`: WIDE only.
+template <bool WITH_JP, bool WITH_JL, bool WIDE>
+PS_DEV void reproj_eval_obs_fetched(const Se3& T, const double* __restrict__ pw, const double* __restrict__ uvd,
+                                    const ObsGroup* __restrict__ groups, int grp, int gfirst_id, const ObsGroup& gfirst,
+                                    const double* __restrict__ Sl, ReprojEval& o) {
+    for (;;) {                          // (one copy of the evaluation, as in reproj_eval_grp)
+        const int g0 = __builtin_amdgcn_readfirstlane(grp);
+        if (grp == g0) {
+            ObsGroup g = gfirst;        // (a wave-uniform choice: the first pass finds g0 == gfirst_id)
+            if (g0 != gfirst_id) g = groups[g0];
+            reproj_eval_s<WITH_JP, WITH_JL>(T, pw, uvd, g, WIDE ? Sl : g.S, o);
+            break;
+        }
+    }
+}

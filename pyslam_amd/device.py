@@ -438,6 +438,19 @@ class DeviceProblem:
         nat.check(self._lib.ps_get_landmark_factors(self._h, nat.f64p(cinv), nat.f64p(c)))
         return cinv, c
 
+    def packed_runs(self):
+        """(run (nwaves, 4) = {v0, v1, row0, nrows}, first (nwaves + 1), lm_ptr (nv + 1), the back-substitution's partials of
+        ||dx_point||^2 (ceil(nwaves / 4))) of the packed observation passes as the handle holds them (include/pyslam_hip.h:
+        ps_debug_packed_runs); nwaves = 0: the handle keeps the 16-lane kernels."""
+        nw = C.c_int32(0)
+        nat.check(self._lib.ps_debug_packed_runs(self._h, C.byref(nw), 0, None, None, None, None))
+        n = nw.value
+        run, first, lm_ptr = np.zeros((n, 4), dtype=np.int32), np.zeros(n + 1, dtype=np.int32), np.zeros(self.nv + 1, dtype=np.int32)
+        sq = np.zeros((n + 3) // 4)
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        nat.check(self._lib.ps_debug_packed_runs(self._h, C.byref(nw), n, i32(run), i32(first), i32(lm_ptr), nat.f64p(sq)))
+        return run, first, lm_ptr, sq
+
     def debug_reproj_blocks(self):
         n = self.lp.num_obs
         r, jp, jl = np.zeros((n, 3)), np.zeros((n, 3, 6)), np.zeros((n, 3, 3))
