@@ -434,6 +434,12 @@ int ps_debug_table_checksums(ps_problem* h, uint64_t* out, int capacity, int* co
    sq_part have room for (refused when too few: call with NULLs first).  No reference counterpart. */
 int ps_debug_packed_runs(ps_problem* h, int32_t* nwaves, int32_t capacity_waves, int32_t* run, int32_t* first, int32_t* lm_ptr,
                          double* sq_part);
+/* The work items of the pose pass (csrc/ps_k_linearize.h) and the partial sums its last launch left, device -> host.  *nitems: items
+   on this handle (one workgroup each: a chunk of one variable pose's observations); items (nitems, 3): {reduced pose, first row,
+   one past the last row} in the pose-ordered observation table; partial (nitems, 33): upper triangle of the 6 x 6 block (21) |
+   gradient (6) | damping sums (6; zero after a linearisation with lambda = 0).  items / partial may be NULL; capacity_items: items
+   the caller's tables have room for (refused when too few: call with NULLs first).  No reference counterpart. */
+int ps_debug_pose_items(ps_problem* h, int32_t* nitems, int32_t capacity_items, int32_t* items, double* partial);
 
 /* Tuning knobs.  [default; accepted values]: "0 / 1" is stored as value != 0; a range is refused outside it and truncated to
    an integer inside it; "any" is truncated and never refused.  One table holds every name with its parse rule, bounds, refusal
@@ -530,7 +536,13 @@ int ps_debug_packed_runs(ps_problem* h, int32_t* nwaves, int32_t capacity_waves,
                               the row names (x of its pose, pose, point, the whole observation-group record) + the head lane's point
                               index; the point with the head lane's C^-1 and c -- instead of seven.  0: the load order they had
                               before.  Speed only, same bits.  Handled ahead of the option table
-     "schur_pipeline"     [1; 0 / 1] the Schur pair kernel with two chunks per wave in flight (k_schur_pairs_db); 0: k_schur_pairs
+     "pose_prefetch"      [1; 0 / 1] the pose pass (items of at most 512 observations: every handle of the product library) requests both
+                              observations of a thread, then their point / C^-1 / c gathers with the whole observation-group record,
+                              evaluates each down to twelve numbers and forms its 33 sums only at the end; the six damping sums are
+                              compiled out of the launches with lambda = 0.  Under 128 registers there: four waves per SIMD instead of
+                              three.  0: k_pose_pass, one observation after the other.  Speed only, same bits.  Handled ahead of the
+                              option table
+     "schur_pipeline"    [1; 0 / 1] the Schur pair kernel with two chunks per wave in flight (k_schur_pairs_db); 0: k_schur_pairs
      "lm_packed" [1; 0 / 1], "band_part" [1; 0 / 1], "band_part_chunk" [0 auto; 0 .. 4096 nodes], "sync_refactor" [1; 0 / 1],
      "hold_across_steps" [1; 0 / 1]: round-5 kernels and schedules against their predecessors (DESIGN.md sections 0 and 3)
      "cg_force_restart"   [0; 0 / 1] tests: end the first pass of a synchronous reduced solve at 1e-4 and restart from the true residual
@@ -558,7 +570,7 @@ int ps_set_option(ps_problem* h, const char* name, double value);
    take on this handle (0 before the coarse level is built, and where the one-launch folded CG does not apply);
    "cg_persist_recovered" / "cg_persist_recover_fallbacks": one-launch solves so far (ps_problem_info.cg_persist_solves) that recover
    x inside the launch / that leave it to k_coarse_recover behind the launch.
-   "packed_prefetch": the option. */
+   "packed_prefetch", "pose_prefetch": the options. */
 int ps_get_option(ps_problem* h, const char* name, double* value);
 
 /* hipEvent stage timers on the handle's stream (the reference has no tracing). */

@@ -141,6 +141,7 @@ SIGNATURES = {
     'ps_debug_factor_blocks': (C.c_int, [H, c_f64p, c_f64p, c_f64p]),
     'ps_debug_table_checksums': (C.c_int, [H, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
     'ps_debug_packed_runs': (C.c_int, [H, c_i32p, C.c_int32, c_i32p, c_i32p, c_i32p, c_f64p]),
+    'ps_debug_pose_items': (C.c_int, [H, c_i32p, C.c_int32, c_i32p, c_f64p]),
     'ps_set_option': (C.c_int, [H, C.c_char_p, C.c_double]),
     'ps_get_option': (C.c_int, [H, C.c_char_p, c_f64p]),
     'ps_set_profiling': (C.c_int, [H, C.c_int]),

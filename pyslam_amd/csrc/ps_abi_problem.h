@@ -37,7 +37,7 @@ int ps_warm_up(void) {
         // when it loads).  Asking for the attributes of the kernels of the whole-iteration paths resolves them here.
         hipFuncAttributes a;
 #define PS_TOUCH(...) (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&__VA_ARGS__))
-        PS_TOUCH(k_landmark_pass<false>); PS_TOUCH(k_landmark_pass_packed<false, false, true>); PS_TOUCH(k_landmark_pass_packed<false, true, true>); PS_TOUCH(k_backsub_packed<false, true>); PS_TOUCH(k_pose_pass<false>); PS_TOUCH(k_pose_finalize); PS_TOUCH(k_schur_pairs_db<0>);
+        PS_TOUCH(k_landmark_pass<false>); PS_TOUCH(k_landmark_pass_packed<false, false, true>); PS_TOUCH(k_landmark_pass_packed<false, true, true>); PS_TOUCH(k_backsub_packed<false, true>); PS_TOUCH(k_pose_pass<false>); PS_TOUCH((k_pose_pass_pf<false, false>)); PS_TOUCH(k_pose_finalize); PS_TOUCH(k_schur_pairs_db<0>);
         PS_TOUCH(k_schur_combine); PS_TOUCH(k_backsub<false>); PS_TOUCH(k_cost_reproj<false>); PS_TOUCH(k_cost_packed<false, true>); PS_TOUCH(k_reduce3); PS_TOUCH(k_reduce_partials);
         PS_TOUCH(k_copy2); PS_TOUCH(k_zero4); PS_TOUCH(k_lag_status_check);
         PS_TOUCH(k_block_jacobi_factor<6>); PS_TOUCH(k_scale_blocks<6>); PS_TOUCH(k_scale_blocks_p<6>); PS_TOUCH(k_rows_setup<6, PS_RS_REGS>); PS_TOUCH(k_rows_setup<6, PS_RS_EXACT>);
@@ -313,6 +313,7 @@ static int create_pose_segments(ps_problem* h, const ps_problem_desc* d, ObsBuil
     //  28.3 / 25.9 / 28.6 us at C3 and 0.218 / 0.192 / 0.202 ms at C4)
     int pchunk = Np >= 512L * 256 ? 512 : 256;
     if (const char* e = ps_env("PS_POSE_CHUNK")) pchunk = std::max(256, atoi(e) / 256 * 256);
+    h->pose_chunk = pchunk;
     for (int r = 0; r < nr; ++r) {
         for (int s = pcount[r]; s < pcount[r + 1]; s += pchunk)
             pitems.push_back({r, s, std::min(s + pchunk, pcount[r + 1]), pose_of_rid[r]});

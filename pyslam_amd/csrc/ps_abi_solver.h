@@ -910,6 +910,23 @@ int ps_debug_packed_runs(ps_problem* h, int32_t* nwaves, int32_t capacity_waves,
     return 0;
 }
 
+// The pose pass's items and what its last launch left in their partial sums (tests/test_gpu_pose_prefetch.py): items as
+// (rid, start, end) triples, partial as [items][33]
+int ps_debug_pose_items(ps_problem* h, int32_t* nitems, int32_t capacity_items, int32_t* items, double* partial) {
+    if (!h || !nitems) return fail("null argument");
+    if (sync(h)) return -1;
+    const int ni = h->npitems;
+    *nitems = ni;
+    if ((items || partial) && capacity_items < ni) return fail("ps_debug_pose_items: capacity too small");
+    if (items && ni) {
+        std::vector<PItem> tab(ni);
+        HIP_OK(hipMemcpy(tab.data(), h->pitems, (size_t)ni * sizeof(PItem), hipMemcpyDeviceToHost));
+        for (int k = 0; k < ni; ++k) { items[3 * k] = tab[k].rid; items[3 * k + 1] = tab[k].start; items[3 * k + 2] = tab[k].end; }
+    }
+    if (partial && ni) HIP_OK(hipMemcpy(partial, h->ppartial, (size_t)ni * PS_NPOSE_ACC * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // What the lagged dense inverse of a live handle holds (csrc/ps_host_ldi.h; tests/test_gpu_ldi_kernels.py), as doubles (the
 // fp32 matrices convert exactly).  Waits for the solver stream, the side stream and the direct seed's stream / ev_ldi, copies,
 // and touches nothing: the state machine, the counters and the schedule are where they were.
@@ -1001,6 +1018,12 @@ int ps_set_option(ps_problem* h, const char* name, double value) {
         h->prelin_valid = h->prelm_valid = h->ride_valid = false;
         return 0;
     }
+    // the pose pass with both observations' operands up front and the sums formed at the end (csrc/ps_core.hip: pose_prefetch); 0: k_pose_pass
+    if (!std::strcmp(name, "pose_prefetch")) {
+        h->pose_prefetch = value != 0 ? 1 : 0;
+        h->prelin_valid = h->prelm_valid = h->ride_valid = false;
+        return 0;
+    }
     h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     const char* refusal = nullptr;
     const int fx = ps_option_apply(*h, name, value, &refusal);
@@ -1031,6 +1054,7 @@ int ps_get_option(ps_problem* h, const char* name, double* value) {
     else if (n == "exact_row_setups") *value = (double)h->exact_row_setups;
     else if (n == "rows_lci_in_lds") *value = h->coarse_built && h->lagx_ok && h->rows_lci_lds ? 1.0 : 0.0;
     else if (n == "packed_prefetch") *value = (double)h->packed_prefetch;
+    else if (n == "pose_prefetch") *value = (double)h->pose_prefetch;
     else if (n == "cg_persist_recover") *value = (double)h->cg_persist_recover;
     else if (n == "cg_persist_recover_lds") *value = (double)h->cg_persist_recover_lds;
     else if (n == "cg_persist_recover_need") *value = h->coarse_built && h->cp_ok ? (double)h->cp_rec_lds : 0.0;

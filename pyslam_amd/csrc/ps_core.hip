@@ -500,6 +500,13 @@ struct ps_problem : PsOptions, PsCostHistory, PsCarried {
     // seven (ps_k_packed.h: PF).  0: the load order they had before.  Every value is the same either way.
     LmwRun* lmw_run = nullptr;
     int packed_prefetch = 1;
+    // option "pose_prefetch" (ps_set_option, ahead of the table): the pose pass asks for both observations of a thread, their gathers
+    // and the group record up front and forms its 33 sums only at the end (ps_k_linearize.h: k_pose_pass_pf) -- under 128 VGPRs
+    // without damping, four waves per SIMD: the items of C3 in one resident round instead of two.  It serves items of at most
+    // PS_POSE_PF_OBS observations (pose_chunk: what create_pose_segments cut; larger only in the measurement build).  0, or a
+    // larger chunk: k_pose_pass.  Every value is the same either way.
+    int pose_prefetch = 1;
+    int pose_chunk = 256;
     // lagged dense inverse of the reduced system as the CG preconditioner (ps_k_ldi.h / ps_host_ldi.h)
     bool ldi_ready = false;         // buffers allocated
     int ldi_n = 0, ldi_np = 0, ldi_kp = 0;

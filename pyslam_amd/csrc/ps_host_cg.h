@@ -1154,7 +1154,15 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
         const int ntail = zero_by_list ? h->nr * 6 + 2 + (lm_here ? 0 : ST_NWORDS / 2) : 0;
         const int nzs = zero_by_list ? h->nzero_slots : 0;
         const int nzblk = zero_by_list ? cdiv((long)nzs * 36 + ntail, 256) : 0;
-        if (h->wide_obs)
+        // (option "pose_prefetch", default on: k_pose_pass_pf -- both observations' operands up front, damping sums only under lambda != 0)
+#define PS_PPF_LAUNCH(W, D) hipLaunchKernelGGL((k_pose_pass_pf<W, D>), dim3(nblk + nzblk), dim3(256), 0, h->stream, h->pitems, h->pobs,       \
+                               h->poses, h->points, h->ogroups, h->Cinv, h->cvec, h->ppartial, wp, h->npitems, per_xcd,                  \
+                               nblk, (const int32_t*)h->zero_slots, nzs, h->S, h->g, ntail)
+        if (h->pose_prefetch && h->pose_chunk <= PS_POSE_PF_OBS) {
+            if (h->wide_obs) { if (lambda != 0.0) PS_PPF_LAUNCH(true, true); else PS_PPF_LAUNCH(true, false); }
+            else if (lambda != 0.0) PS_PPF_LAUNCH(false, true); else PS_PPF_LAUNCH(false, false);
+        }
+        else if (h->wide_obs)
             hipLaunchKernelGGL(k_pose_pass<true>, dim3(nblk + nzblk), dim3(256), 0, h->stream, h->pitems, h->pobs,
                                h->poses, h->points, h->ogroups, h->Cinv, h->cvec, h->ppartial, lambda != 0.0 ? 1 : 0, wp, h->npitems, per_xcd,
                                nblk, (const int32_t*)h->zero_slots, nzs, h->S, h->g, ntail);
@@ -1162,6 +1170,7 @@ int linearize(ps_problem* h, double lambda, bool allow_prelm) {
             hipLaunchKernelGGL(k_pose_pass<false>, dim3(nblk + nzblk), dim3(256), 0, h->stream, h->pitems, h->pobs,
                                h->poses, h->points, h->ogroups, h->Cinv, h->cvec, h->ppartial, lambda != 0.0 ? 1 : 0, wp, h->npitems, per_xcd,
                                nblk, (const int32_t*)h->zero_slots, nzs, h->S, h->g, ntail);
+#undef PS_PPF_LAUNCH
         // tiled Schur: the combine launch also finalizes the poses (unless a task writes a diagonal block)
         fin_in_combine = h->Spart && h->npair_items > 0 && !h->has_diag_tasks && h->D == 6;
         // untiled Schur with the pipelined pair kernel: its trailing workgroups finalize the poses

@@ -352,6 +352,167 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PS_POSE_WAV
             ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
+// ---------------------------------------------------------------------------
+// pose pass, operands up front (option "pose_prefetch", default): k_pose_pass above is bound neither by bytes nor by issue
+//  -- its 164 VGPRs hold it at three waves per SIMD, i.e. 768 resident workgroups for the 1 034 items of
+// C3, so a launch lasts two workgroup lifetimes, and inside one lifetime the two observations of a thread run their chains of
+// dependent loads one after the other.  Here a workgroup serves an item of at most 512 observations (all the product library
+// builds), two per thread, and asks in as few dependent trips as the data allow:
+//   trip 1  items[item] (scalar);
+//   trip 2  the pose (scalar) and BOTH records pobs[ia], pobs[ia + 256];
+//   trip 3  points / C^-1 / c of both observations and the whole group record of the first lane's group (obs_group_fetch).
+// Each observation is evaluated down to what the sums need -- G (6), t (3), pc (3) and under DIAG the six damping terms -- and the
+// 33 accumulators are formed only at the end, acc = 0; += a; += b: they are not live across an evaluation, which is what brings
+// <false, false> under 128 VGPRs (four waves per SIMD, four workgroups of 35 KB LDS per CU: 1 024 slots, one round at C3).
+// DIAG (lambda != 0) is a template flag the host chooses: without damping the six sums are not formed at all (they are zero).
+// Every accumulator receives the terms of k_pose_pass in its order (0.0 + a first, + b second), through the same functions
+// (reproj_eval_s, lm_emit_m, pose_sandwich): the partials are the same bits, the reduction below is k_pose_pass's.
+template <bool WIDE, bool DIAG>
+PS_DEV void pose_obs_compact(const Se3& T, const LObs& o, const double* __restrict__ pw, const double* __restrict__ m,
+                             double c0, double c1, double c2, int v, const ObsGroup* __restrict__ groups, int gfirst_id,
+                             const ObsGroup& gfirst, const double* __restrict__ Sl,
+                             double* __restrict__ G, double* __restrict__ t3, double* __restrict__ pc, double* __restrict__ dg) {
+    ReprojEval ev;
+    reproj_eval_obs_fetched<true, true, WIDE>(T, pw, &o.u, groups, PS_GRP_OF(o), gfirst_id, gfirst, Sl, ev);
+    {
+        const double* J = ev.Jp;
+        G[0] = J[0] * J[0] + J[6] * J[6] + J[12] * J[12];
+        G[1] = J[0] * J[1] + J[6] * J[7] + J[12] * J[13];
+        G[2] = J[0] * J[2] + J[6] * J[8] + J[12] * J[14];
+        G[3] = J[1] * J[1] + J[7] * J[7] + J[13] * J[13];
+        G[4] = J[1] * J[2] + J[7] * J[8] + J[13] * J[14];
+        G[5] = J[2] * J[2] + J[8] * J[8] + J[14] * J[14];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) t3[a] = J[a] * ev.r[0] + J[6 + a] * ev.r[1] + J[12 + a] * ev.r[2];
+    }
+    if (DIAG) {
+        double d21[21];
+#pragma unroll
+        for (int k = 0; k < 21; ++k) d21[k] = 0.0;
+        pose_sandwich(G, ev.pc, d21);
+        dg[0] = d21[0]; dg[1] = d21[6]; dg[2] = d21[11]; dg[3] = d21[15]; dg[4] = d21[18]; dg[5] = d21[20];
+    }
+    if (v >= 0) {
+        double m9[9];
+        lm_emit_m(ev, m[0], m[1], m[2], m[3], m[4], m[5], m9);
+        G[0] -= m9[0] * m9[0] + m9[1] * m9[1] + m9[2] * m9[2];
+        G[1] -= m9[0] * m9[3] + m9[1] * m9[4] + m9[2] * m9[5];
+        G[2] -= m9[0] * m9[6] + m9[1] * m9[7] + m9[2] * m9[8];
+        G[3] -= m9[3] * m9[3] + m9[4] * m9[4] + m9[5] * m9[5];
+        G[4] -= m9[3] * m9[6] + m9[4] * m9[7] + m9[5] * m9[8];
+        G[5] -= m9[6] * m9[6] + m9[7] * m9[7] + m9[8] * m9[8];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) t3[a] += m9[3 * a] * c0 + m9[3 * a + 1] * c1 + m9[3 * a + 2] * c2;
+    }
+    pc[0] = ev.pc[0]; pc[1] = ev.pc[1]; pc[2] = ev.pc[2];
+}
+
+// acc - (a b - c d) as k_pose_pass's gfx950 code forms it: the first product fused, the second rounded.  Left to the compiler,
+// this context turns x - (y - z) into x + (z - y) before the back end contracts, which fuses the OTHER product: the last bits
+// of the rotational half of g then differ (the only sums of the 33 that did).
+PS_DEV double pose_cross_sub(double acc, double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+    return acc - __builtin_fma(a, b, -(c * d));
+}
+
+// acc += the contribution of one observation (k_pose_pass's statements behind its evaluation)
+template <bool DIAG>
+PS_DEV void pose_acc_add(const double* __restrict__ G, const double* __restrict__ t3, const double* __restrict__ pc,
+                         const double* __restrict__ dg, double* __restrict__ acc) {
+    if (DIAG) { acc[27] += dg[0]; acc[28] += dg[1]; acc[29] += dg[2]; acc[30] += dg[3]; acc[31] += dg[4]; acc[32] += dg[5]; }
+    pose_sandwich(G, pc, acc);
+    acc[21] -= t3[0]; acc[22] -= t3[1]; acc[23] -= t3[2];
+    acc[24] = pose_cross_sub(acc[24], pc[1], t3[2], pc[2], t3[1]);
+    acc[25] = pose_cross_sub(acc[25], pc[2], t3[0], pc[0], t3[2]);
+    acc[26] = pose_cross_sub(acc[26], pc[0], t3[1], pc[1], t3[0]);
+}
+
+// the gathers an observation record addresses: point, C^-1 and c of its landmark (v < 0: constant landmark), WIDE: its stiffness
+template <bool WIDE>
+PS_DEV void pose_obs_gather(const LObs& o, int si, const double* __restrict__ points, const double* __restrict__ Cinv,
+                            const double* __restrict__ cvec, const ObsWide& wide, double* __restrict__ pw, double* __restrict__ m,
+                            double* __restrict__ c, double* __restrict__ Sl) {
+    const int v = PS_POSE_OF(o) - 1;
+    pw[0] = points[3 * (size_t)o.point]; pw[1] = points[3 * (size_t)o.point + 1]; pw[2] = points[3 * (size_t)o.point + 2];
+    if (v >= 0) {
+        const double* ci = Cinv + 6 * (size_t)v;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) m[k] = ci[k];
+        c[0] = cvec[3 * (size_t)v]; c[1] = cvec[3 * (size_t)v + 1]; c[2] = cvec[3 * (size_t)v + 2];
+    }
+    if (WIDE) {
+        const double* sp = wide.stiff + 9 * (size_t)si;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Sl[k] = sp[k];
+    }
+}
+
+#define PS_POSE_PF_OBS 512                     // observations per item k_pose_pass_pf serves: two per thread
+template <bool WIDE, bool DIAG>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((WIDE || DIAG) ? 3 : 4, 8))) void k_pose_pass_pf(
+    const PItem* __restrict__ items, const LObs* __restrict__ pobs, const double* __restrict__ poses,
+    const double* __restrict__ points, const ObsGroup* __restrict__ groups, const double* __restrict__ Cinv,
+    const double* __restrict__ cvec, double* __restrict__ partial, ObsWide wide, int nitems, int per_xcd,
+    int zero_first, const int32_t* __restrict__ zero_slots, int nzero_slots, double* __restrict__ S, double* __restrict__ ztail, int ntail)
+{
+    __shared__ double red[4][PS_NPOSE_ACC];
+    __shared__ double tr[4][64 * 17];
+    if ((int)blockIdx.x >= zero_first) {                          // (the zeroing workgroups of k_pose_pass)
+        const int e = ((int)blockIdx.x - zero_first) * 256 + (int)threadIdx.x, ns = 36 * nzero_slots;
+        if (e < ns) { const int k = e / 36; S[(size_t)zero_slots[k] * 36 + (e - 36 * k)] = 0.0; }
+        else if (e - ns < ntail) ztail[e - ns] = 0.0;
+        return;
+    }
+    const int item = per_xcd > 0 ? (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    if (item >= nitems) return;
+    const PItem it = items[item];                                 // trip 1
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ia = it.start + (int)threadIdx.x, ib = ia + 256;
+    const bool ha = ia < it.end, hb = ib < it.end;                // (hb implies ha; an item has at most PS_POSE_PF_OBS observations)
+    const Se3 T = se3_load(poses + 12 * (size_t)it.pad);          // trip 2: the pose and both records
+    LObs oa = {0.0, 0.0, 0.0, 0, 0}, ob = {0.0, 0.0, 0.0, 0, 0};
+    int sa = 0, sb = 0;
+    if (ha) { oa = pobs[ia]; if (WIDE) sa = wide.sidx[ia]; }
+    if (hb) { ob = pobs[ib]; if (WIDE) sb = wide.sidx[ib]; }
+    double pwa[3], ma[6] = {0, 0, 0, 0, 0, 0}, ca[3] = {0.0, 0.0, 0.0}, Sla[9];
+    double pwb[3], mb[6] = {0, 0, 0, 0, 0, 0}, cb[3] = {0.0, 0.0, 0.0}, Slb[9];
+    double Ga[6], ta[3], pca[3], da[6], Gb[6], tb[3], pcb[3], db[6];
+    if (ha) {                                                     // trip 3: what the records address, and the group record
+        pose_obs_gather<WIDE>(oa, sa, points, Cinv, cvec, wide, pwa, ma, ca, Sla);
+        if (hb) pose_obs_gather<WIDE>(ob, sb, points, Cinv, cvec, wide, pwb, mb, cb, Slb);
+        const int g0 = __builtin_amdgcn_readfirstlane((int)PS_GRP_OF(oa));
+        const ObsGroup g = obs_group_fetch(groups, g0);
+        pose_obs_compact<WIDE, DIAG>(T, oa, pwa, ma, ca[0], ca[1], ca[2], PS_POSE_OF(oa) - 1, groups, g0, g, Sla, Ga, ta, pca, da);
+        if (hb) pose_obs_compact<WIDE, DIAG>(T, ob, pwb, mb, cb[0], cb[1], cb[2], PS_POSE_OF(ob) - 1, groups, g0, g, Slb, Gb, tb, pcb, db);
+    }
+    double acc[PS_NPOSE_ACC];
+#pragma unroll
+    for (int k = 0; k < PS_NPOSE_ACC; ++k) acc[k] = 0.0;
+    if (ha) pose_acc_add<DIAG>(Ga, ta, pca, da, acc);
+    if (hb) pose_acc_add<DIAG>(Gb, tb, pcb, db, acc);
+    {   // (the LDS-transposed reduction of k_pose_pass)
+        double* trw = tr[w];
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2) {
+            const int k0 = 17 * h2, nk = h2 ? PS_NPOSE_ACC - 17 : 17;
+#pragma unroll
+            for (int k = 0; k < 17; ++k) if (k < nk) trw[lane * 17 + k] = acc[k0 + k];
+            __builtin_amdgcn_wave_barrier();
+            if (lane < nk) {
+                double s = 0.0;
+#pragma unroll 8
+                for (int l = 0; l < 64; ++l) s += trw[l * 17 + lane];
+                red[w][k0 + lane] = s;
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < PS_NPOSE_ACC)
+        partial[(size_t)item * PS_NPOSE_ACC + threadIdx.x] =
+            ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
 // one wave (64 lanes, 33 active) per reduced pose: chunk partials -> diagonal S block, g
 // (s_new / g_new: what lane < 36 / lane < 6 has just stored, for a caller that goes on with the block -- ps_k_schur2.h)
 PS_DEV void pose_finalize_wave(int rid, int lane, const int32_t* __restrict__ pitem_ptr,

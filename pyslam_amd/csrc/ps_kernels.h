@@ -2,7 +2,8 @@
 //
 // Pipeline per iteration:
 //   k_landmark_pass      16 lanes / landmark  : H_ll, b_l -> chol -> c_l, Z_i = W_i C^-T (LDS-transposed stores)
-//   k_pose_pass          WG / pose chunk      : J_p^T J_p - Z Z^T, -J_p^T r - Z c, Z recomputed in registers
+//   k_pose_pass_pf       WG / pose chunk      : J_p^T J_p - Z Z^T, -J_p^T r - Z c, Z recomputed in registers; two observations per
+//                                               thread, operands up front, sums formed at the end (k_pose_pass: option "pose_prefetch" 0)
 //   k_pose_finalize      WG / pose            : chunk partials -> diagonal S block, g
 //   k_schur_pairs        wave / (tile, block) : S_ij = -sum Z_i Z_j^T, rows straight into LDS (global_load_lds)
 //   k_schur_combine      wave / block         : tiled mode: partials summed in tile order

@@ -451,6 +451,16 @@ class DeviceProblem:
         nat.check(self._lib.ps_debug_packed_runs(self._h, C.byref(nw), n, i32(run), i32(first), i32(lm_ptr), nat.f64p(sq)))
         return run, first, lm_ptr, sq
 
+    def pose_items(self):
+        """(items (nitems, 3) = {reduced pose, first row, one past the last row}, partial (nitems, 33)) of the pose pass as the
+        handle holds them after its last launch (include/pyslam_hip.h: ps_debug_pose_items)."""
+        ni = C.c_int32(0)
+        nat.check(self._lib.ps_debug_pose_items(self._h, C.byref(ni), 0, None, None))
+        n = ni.value
+        items, partial = np.zeros((n, 3), dtype=np.int32), np.zeros((n, 33))
+        nat.check(self._lib.ps_debug_pose_items(self._h, C.byref(ni), n, items.ctypes.data_as(C.POINTER(C.c_int32)), nat.f64p(partial)))
+        return items, partial
+
     def debug_reproj_blocks(self):
         n = self.lp.num_obs
         r, jp, jl = np.zeros((n, 3)), np.zeros((n, 3, 6)), np.zeros((n, 3, 3))
