@@ -546,6 +546,14 @@ int ps_debug_pose_items(ps_problem* h, int32_t* nitems, int32_t capacity_items, 
      "lm_packed" [1; 0 / 1], "band_part" [1; 0 / 1], "band_part_chunk" [0 auto; 0 .. 4096 nodes], "sync_refactor" [1; 0 / 1],
      "hold_across_steps" [1; 0 / 1]: round-5 kernels and schedules against their predecessors (DESIGN.md sections 0 and 3)
      "cg_force_restart"   [0; 0 / 1] tests: end the first pass of a synchronous reduced solve at 1e-4 and restart from the true residual
+     "cg_force_breakdown" [0; integer] tests: n > 0 arms ONE forced breakdown -- in the first pass of the next reduced solve that sets
+                              up the folded CG or the explicit two-level PCG, CG iteration n - 1 reads a negative delta (a one-thread-
+                              block kernel overwrites it in front of that launch), finds denom <= 0 through its own branch and sets
+                              the breakdown flag; the host then takes its fallback.  That one pass runs launch by launch (never a
+                              one-launch-per-solve form, which takes no host step between iterations).  The set-up of that solve
+                              clears the option (ps_get_option reads it back), so the repeat runs untouched.  The three- and
+                              four-launch forms of the explicit PCG have no such branch: they consume the option and run as usual.
+                              Setting it invalidates nothing that was computed ahead
      "cg_lds"             [1; 0 / 1] small systems: the fused CG with the whole vector through LDS (k_cg_fused_lds)
      "big_chol"           [1; 0 / 1] coarse matrices of more than 90 unknowns: the blocked factorisation over many workgroups; 0: one workgroup
      "profile_every"      [1; >= 1] profiling level 1 times the Schur kernel of every n-th linearisation only

@@ -325,11 +325,10 @@ int ps_shard_buffer(ps_problem* h, void** dev_ptr) {
 // Sharded second half WITHOUT a host synchronisation: (first != 0: CG setup,) CG launches, gated
 // tail; cost and ||dx_point||^2 of this shard land in ps_shard_buffer for the caller's all-reduce.
 // Returns 1 when this was the last, ungated pass (max_iters exhausted), else 0.
-int ps_gn_solve_finish_enqueue(ps_problem* h, double pcg_tol, int pcg_max_iters, int linesearch, int first) {
-    if (!h) return fail("null argument");
-    if (h->nr == 0 || h->pcg_variant != 1) return fail("ps_gn_solve_finish_enqueue needs the fused CG and a reduced system");
-    pcg_tol = resolve_pcg_tol(h, pcg_tol);
-    if (first && z_of_last_linearize(h, "ps_gn_solve_finish_enqueue")) return -1;
+// (the body of ps_gn_solve_finish_enqueue, shared with the core's own sharded iteration: the check that Z, C^-1 and c are the last
+//  linearisation's is the PUBLIC call's -- the iteration linearises itself, and when it sets a solve up AGAIN after a breakdown
+//  the gated tail in between has only SAID that the parameters moved and that a landmark pass ran: the gate was closed)
+static int gn_solve_finish_enqueue(ps_problem* h, double pcg_tol, int pcg_max_iters, int linesearch, int first) {
     h->shard_out = true;
     // (a caller that drives the collectives itself cannot repeat a solve on ONE rank -- the others have applied their tails and
     //  wait in the next collective: it gets neither the explicit PCG's one-launch-per-iteration form, whose recurrences may break
@@ -342,7 +341,9 @@ int ps_gn_solve_finish_enqueue(ps_problem* h, double pcg_tol, int pcg_max_iters,
         // (a caller that drives the collectives itself cannot repeat a solve whose single-reduction recurrences broke
         //  down: it gets the three-launch form; the core's own sharded iteration below handles the fallback)
         if (!(h->nccl_allreduce && h->nccl_comm) && h->xf_skip == 0) h->xf_skip = 1;
-        if (h->cg_explicit) { if (h->D == 6 ? xcg_setup<6>(h, pcg_max_iters, true) : xcg_setup<3>(h, pcg_max_iters, true)) return -1; }
+        // (first == 2: the core's iteration sets the solve up AGAIN after a breakdown -- as the unsharded iteration does, with this
+        //  point's own coarse inverse, so that one rank reproduces it bit for bit)
+        if (h->cg_explicit) { if (h->D == 6 ? xcg_setup<6>(h, pcg_max_iters, first == 1) : xcg_setup<3>(h, pcg_max_iters, first == 1)) return -1; }
         else if (h->D == 6 ? cg_fused_setup<6>(h, pcg_max_iters, true) : cg_fused_setup<3>(h, pcg_max_iters, true)) return -1;
     }
     // (the explicit PCG runs iteration k in launch group k: one group less than the fused CG's launches)
@@ -368,6 +369,14 @@ int ps_gn_solve_finish_enqueue(ps_problem* h, double pcg_tol, int pcg_max_iters,
     else { if (!last) cg_fused_launch<3>(h, pcg_tol, count); cg_fused_recover<3>(h, gate); }
     if (gn_tail(h, linesearch, last ? nullptr : h->status)) return -1;
     return last ? 1 : 0;
+}
+
+int ps_gn_solve_finish_enqueue(ps_problem* h, double pcg_tol, int pcg_max_iters, int linesearch, int first) {
+    if (!h) return fail("null argument");
+    if (h->nr == 0 || h->pcg_variant != 1) return fail("ps_gn_solve_finish_enqueue needs the fused CG and a reduced system");
+    pcg_tol = resolve_pcg_tol(h, pcg_tol);
+    if (first && z_of_last_linearize(h, "ps_gn_solve_finish_enqueue")) return -1;
+    return gn_solve_finish_enqueue(h, pcg_tol, pcg_max_iters, linesearch, first);
 }
 
 // Synchronise and read back: done flag, the (all-reduced) shard buffer, ||dx_pose||^2, CG statistics.
@@ -437,7 +446,7 @@ static int gn_iteration_impl(ps_problem* h, double lambda, double pcg_tol, int p
         int first = 1, done = 0;
         double sb[2] = {0.0, 0.0}, dxp2 = 0.0;
         for (;;) {
-            const int last = ps_gn_solve_finish_enqueue(h, pcg_tol, pcg_max_iters, linesearch, first);
+            const int last = gn_solve_finish_enqueue(h, pcg_tol, pcg_max_iters, linesearch, first);
             if (last < 0) return -1;
             {
                 StageTimer tar(h, PS_ST_ALLREDUCE);
@@ -459,7 +468,7 @@ static int gn_iteration_impl(ps_problem* h, double lambda, double pcg_tol, int p
             if (h->xf_active && done == 2 && !h->h_status[ST_DIAG_FAIL]) {
                 // breakdown of the one-launch form's recurrences (the same on every rank: the solve is replicated): nothing
                 // applied; set the solve up again in the three-launch form
-                ++h->xf_fallbacks; h->xf_skip = 1; first = 1;
+                ++h->xf_fallbacks; h->xf_skip = 1; first = 2;
                 continue;
             }
             sb[0] = h->h_shard[0]; sb[1] = h->h_shard[1];
@@ -1024,7 +1033,9 @@ int ps_set_option(ps_problem* h, const char* name, double value) {
         h->prelin_valid = h->prelm_valid = h->ride_valid = false;
         return 0;
     }
-    h->prelin_valid = h->prelm_valid = h->ride_valid = false;
+    // (the test hook arms the next solve and changes nothing that was computed ahead: the landmark pass and the linearisation a
+    //  tail ran for this point stay valid, so that the forced breakdown is seen with them in place)
+    if (std::strcmp(name, "cg_force_breakdown")) h->prelin_valid = h->prelm_valid = h->ride_valid = false;
     const char* refusal = nullptr;
     const int fx = ps_option_apply(*h, name, value, &refusal);
     if (fx == PS_OPT_UNKNOWN) return fail(std::string("unknown option: ") + name);
@@ -1060,6 +1071,7 @@ int ps_get_option(ps_problem* h, const char* name, double* value) {
     else if (n == "cg_persist_recover_need") *value = h->coarse_built && h->cp_ok ? (double)h->cp_rec_lds : 0.0;
     else if (n == "cg_persist_recovered") *value = (double)h->cp_rec_inside;
     else if (n == "cg_persist_recover_fallbacks") *value = (double)h->cp_rec_behind;
+    else if (n == "cg_force_breakdown") *value = (double)h->cg_force_breakdown;      // (0 again once a solve's set-up has taken it)
     else return fail("ps_get_option: no read-back for option: " + n);
     return 0;
 }

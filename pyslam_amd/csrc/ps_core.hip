@@ -202,6 +202,7 @@ struct PsCarried {
     bool mc_active = false;         // the current system was built with a lagged factor in split mode
     bool last_setup_lagx = false;   // the current folded system was built with the lagged X~ (three-launch set-up)
     int xf_skip = 0;                // upcoming set-ups that must not use the one-launch form (a fallback after its breakdown)
+    int cg_break_at = 0;            // test hook "cg_force_breakdown" as THIS pass took it (cg_break_arm): the launch index whose delta is forced, 0 none
     // lagged dense inverse
     int ldi_state = 0;              // 0 none, 1 seed in flight, 2 valid (ldi_cur), 3 valid + update in flight
     int ldi_cur = -1, ldi_next = -1;

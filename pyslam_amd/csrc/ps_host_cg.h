@@ -745,10 +745,18 @@ inline bool ride_consume(ps_problem* h, const CgSetupPlan& plan) {
     return false;
 }
 
+// test hook "cg_force_breakdown": every set-up of a pass (cg_fused_setup, xcg_setup) takes the option and clears it, so the pass it
+// sets up is the one that breaks down and the repeat -- which sets up again -- finds nothing armed
+inline void cg_break_arm(ps_problem* h) {
+    h->cg_break_at = h->cg_force_breakdown > 0 ? h->cg_force_breakdown : 0;
+    h->cg_force_breakdown = 0;
+}
+
 template <int D>
 int cg_fused_setup(ps_problem* h, int max_iters, bool allow_lag = false, bool rhs_only = false) {
     const int nr = h->nr, cap = h->hist_cap;
     if (max_iters + 2 > cap) return fail("pcg max_iters exceeds the history buffer (4096)");
+    cg_break_arm(h);
     if (!h->coarse_built) { h->ride_valid = false; if (build_coarse(h)) return -1; }      // (a rebuilt level: other buffers, another plan)
     h->cg_max_launches = max_iters + 2;
     h->cp_recovered = false;
@@ -908,7 +916,8 @@ void cg_fused_launch(ps_problem* h, double tol, int count) {
 #ifdef PS_MEASURE
     if (ps_env("PS_CP_CLOCKS") && !h->cp_dbg) { hipMalloc(&h->cp_dbg, PS_CP_NCLK * 8); hipMemset(h->cp_dbg, 0, PS_CP_NCLK * 8); }
 #endif
-    if (h->cg_persist && h->cp_ok && h->G > 0 && h->cg_lds && !h->cg_split && !h->cg_two_level_reduce &&
+    // (not the pass the test hook "cg_force_breakdown" is armed for: one launch takes no host step between its iterations)
+    if (h->cg_persist && h->cp_ok && h->G > 0 && h->cg_lds && !h->cg_split && !h->cg_two_level_reduce && !h->cg_break_at &&
         !h->cg_ablate && h->cg_launched == 0 && h->cg_max_launches > 0 && h->cg_max_launches <= 4090 && !h->no_repeat &&
         h->persist_reserve(h->cp_cus_needed)) {          // (refused while launches of other handles hold the units: launch by launch)
         const int nl = h->cg_max_launches;
@@ -937,6 +946,13 @@ void cg_fused_launch(ps_problem* h, double tol, int count) {
         const double* tot = h->cg_two_level_reduce ? h->cg_tot : nullptr;
         if (tot && !h->cg_split && n > 0)
             hipLaunchKernelGGL(k_cg_reduce, dim3(1), dim3(1024), 0, h->stream, rows, h->cg_gd[o], h->cg_tot, h->status);
+        if (h->cg_break_at > 0 && n == h->cg_break_at) {
+            // test hook "cg_force_breakdown": launch n runs iteration n - 1 and sums delta from what launch n - 1 left -- the per-row
+            // shares of cg_gd[o], or their total in cg_tot (reduced above / by the last k_cg_reduce_split) and the coarse rows' cg_cgd[o]
+            if (tot) hipLaunchKernelGGL(k_force_delta, dim3(1), dim3(256), 0, h->stream, 1, h->cg_tot + 1, ncbs, ncbs ? h->cg_cgd[o] + ncbs : nullptr);
+            else hipLaunchKernelGGL(k_force_delta, dim3(1), dim3(256), 0, h->stream, rows, h->cg_gd[o] + rows, 0, (double*)nullptr);
+            h->cg_break_at = 0;
+        }
 #define PS_CG_LAUNCH(NWV)                                                                                          \
         hipLaunchKernelGGL((k_cg_fused<D, NWV>), dim3(rows), dim3(64 * NWV), 0, h->stream, rows, h->arow_ptr,           \
                            h->acol_idx, h->Saug, h->cg_r[o], h->cg_w[o], h->cg_s[o], h->cg_r[nw], h->cg_w[nw],        \

@@ -24,6 +24,7 @@ template <int D>
 int xcg_setup(ps_problem* h, int max_iters, bool allow_lag) {
     const int nr = h->nr, ncb = h->ncb, nc = h->nc;
     if (max_iters + 2 > h->hist_cap) return fail("pcg max_iters exceeds the history buffer (4096)");
+    cg_break_arm(h);                                        // (test hook "cg_force_breakdown": this pass, not its repeat)
     // (the side stream assembles A_c from SB and the basis blocks of the previous lagged set-up: both are rewritten below)
     if (h->acdone_pending) { HIP_OK(hipStreamWaitEvent(h->stream, h->ev_acdone, 0)); h->acdone_pending = false; }
     hipLaunchKernelGGL(k_block_jacobi_factor<D>, dim3(cdiv(nr, 4)), dim3(256), 0, h->stream, nr, h->diag_slot,
@@ -150,7 +151,8 @@ int xcg_setup(ps_problem* h, int max_iters, bool allow_lag) {
         // one launch per SOLVE (ps_k_xcg_persist.h): launch -1 is the first pass of the launch that runs them all (xcg_launch)
         // (long rows only -- bundle adjustment: what the launch saves is the matrix stream of every iteration; with the short rows
         //  of a pose graph there is little to save and the exchange between up to 256 workgroups costs more: 1 500 poses 5.48 -> 5.94 ms)
-        h->xp_defer = h->xcg_persist && h->xp_ok && !h->xf_two && h->xf_pf >= 6 && max_iters + 1 <= 4090 && !h->no_repeat &&
+        // (nor the pass the test hook "cg_force_breakdown" is armed for: one launch takes no host step between its iterations)
+        h->xp_defer = h->xcg_persist && h->xp_ok && !h->xf_two && h->xf_pf >= 6 && max_iters + 1 <= 4090 && !h->no_repeat && !h->cg_break_at &&
                       h->persist_reserve(h->xp_cus_needed);  // (its grid must be resident at once: ps_core.hip, PersistLedger)
         h->cg_max_launches = max_iters + 1;
         if (!h->xp_defer) xcg_launch<D>(h, 0.0, 1);        // launch -1 (cg_launched: -1 -> 0)
@@ -312,6 +314,12 @@ void xcg_launch(ps_problem* h, double tol, int count) {
             a.r_in = h->cg_r[in]; a.r_out = h->cg_r[out]; a.w_in = h->cg_w[in]; a.w_out = h->cg_w[out];
             a.s_in = h->cg_s[in]; a.s_out = h->cg_s[out];
             a.u = h->xp2; a.p = h->cg_p; a.x = h->cg_xh; a.y = h->xy;
+            if (h->cg_break_at > 0 && k == h->cg_break_at - 1) {
+                // test hook "cg_force_breakdown": iteration k sums delta from the workgroups' shares of launch k - 1 (k_xcg_fused1, or
+                // k_xcg_f2_coarse in the two-launch form)
+                hipLaunchKernelGGL(k_force_delta, dim3(1), dim3(256), 0, h->stream, h->xf_nwg, h->cg_gd[in] + h->xf_nwg, 0, (double*)nullptr);
+                h->cg_break_at = 0;
+            }
 #define PS_XF_LAUNCH(PF, TWO) hipLaunchKernelGGL((k_xcg_fused1<D, PF, TWO>), dim3(h->xf_nwg), dim3(64 * PS_XF_ROWS), lds, h->stream, nr, h->arow_ptr, \
                                h->ell_wf, h->Saug, a, k, tol * tol, h->hist, h->hist_cap, h->status, h->scalars, h->xstate)
             if (h->xf_two) {
@@ -559,6 +567,7 @@ int gn_solve_and_finish_async(ps_problem* h, double tol, int max_iters, int line
         if (h->h_status[ST_PCG_DONE] == 2 && !h->h_status[ST_DIAG_FAIL] && !h->h_status[ST_LM_FAIL]) {
             // breakdown of the pipelined recurrences (the gated tail applied nothing): the synchronous solver on the same
             // matrix (it restarts from the iterate it reaches, and ends at the classic PCG if that fails too), then the tail
+            ++h->cg_fallbacks;                          // (ps_problem_info.cg_restarts: this pass is given up, as one of cg_fused_run's is)
             if (cg_fused_run<D>(h, tol, max_iters, iters_out, relres_out, true)) return -1;
             if (gn_tail(h, linesearch, nullptr, true) || wait_published(h)) return -1;
             return 0;

@@ -641,6 +641,16 @@ __global__ __launch_bounds__(256) void k_zero4(size_t n0, double* __restrict__ p
     }
 }
 
+// test hook "cg_force_breakdown" (cg_fused_launch, xcg_launch): the delta shares the next CG launch will sum become -1 each (gamma
+// stays), so that launch finds denom = delta - beta gamma / alpha_prev < 0 through its own branch.  One workgroup, never on a
+// solve that was not asked to break down
+__global__ __launch_bounds__(256) void k_force_delta(int n0, double* __restrict__ d0, int n1, double* __restrict__ d1)
+{
+    for (int i = threadIdx.x; i < n0 + n1; i += 256) {
+        if (i < n0) d0[i] = -1.0; else d1[i - n0] = -1.0;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Direct solve of SMALL reduced systems (nr * D <= 90 unknowns: the reference's own examples, sliding
 // windows, motion-only problems): BSR -> dense, the LDS-resident blocked Cholesky + inverse of the

@@ -43,6 +43,9 @@ struct PsOptions {
     int xcg_persist = 1;            // the explicit two-level PCG as one launch per solve (ps_k_xcg_persist.h); cleared likewise
     int prof_every = 1;             // "profile_every": profiling level 1 times the Schur kernel of every n-th linearisation only
     int cg_force_restart = 0;       // tests: end the first pass of a synchronous solve at 1e-4 and restart from the true residual
+    // tests: n > 0 = CG iteration n - 1 of the first pass of the NEXT reduced solve finds denom <= 0 (its delta is overwritten in front
+    // of that launch: cg_fused_launch, xcg_launch) and reports a breakdown; cleared by the set-up of that solve
+    int cg_force_breakdown = 0;
     int cg_margin = 4;              // CG launches enqueued beyond the previous solve's iteration count
     int cg_split_min_rows = 1024;   // split mode (coarse rows owned by k_cg_reduce_split) beyond this many reduced poses
     int cg_explicit_min_rows = -1;  // explicit two-level PCG beyond this many reduced poses (-1: 400 for pose-graph rows, 540 for BA rows)
@@ -123,6 +126,7 @@ static const PsOptionRow PS_OPTION_TABLE[] = {
     {"schur_pipeline", &PsOptions::schur_pipeline, PS_OPT_BOOL, 0, 0, nullptr, 0, false},
     {"coarse_lag", &PsOptions::coarse_lag, PS_OPT_BOOL, 0, 0, nullptr, 0, false},
     {"cg_force_restart", &PsOptions::cg_force_restart, PS_OPT_BOOL, 0, 0, nullptr, 0, false},
+    {"cg_force_breakdown", &PsOptions::cg_force_breakdown, PS_OPT_INT, 0, 0, nullptr, 0, false},
     {"xcg_restrict_fused", &PsOptions::xcg_rt, PS_OPT_BOOL, 0, 0, nullptr, 0, false},
     {"band_chol", &PsOptions::band_chol, PS_OPT_BOOL, 0, 0, nullptr, PS_FX_DROP_FACTOR, false},
     {"lm_packed", &PsOptions::lm_packed, PS_OPT_BOOL, 0, 0, nullptr, 0, false},

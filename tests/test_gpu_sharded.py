@@ -113,6 +113,54 @@ def test_one_rank_core_segment_exchange_is_the_identity(dist1):
         ref.close()
 
 
+@pytest.mark.parametrize('arm_it', [1, 2])
+@pytest.mark.parametrize('exchange', [None, 'segments'])
+@pytest.mark.parametrize('expect', [False, True])
+def test_a_forced_breakdown_in_the_cores_sharded_iteration(dist1, expect, exchange, arm_it):
+    """The core's own sharded loop answers a breakdown of the explicit PCG's one-launch form (status word ST_PCG_DONE == 2 behind
+    the gated tail) by setting the solve up again in the three-launch form, as the unsharded iteration does -- driven on both by
+    the test hook "cg_force_breakdown" (tests/test_gpu_cg_breakdown.py), in front of iteration 1 (CG iteration 0 breaks down) or
+    iteration 2 (CG iteration 5; the lagged coarse inverse and, with expect_next, the tail's successor landmark pass exist).
+    One rank must still reproduce the unsharded iterations bit for bit.  With expect_next the closed tail has only SAID that a
+    landmark pass ran at a moved point: the second set-up must not take that for Z, C^-1 and c having left the linearisation."""
+    import torch
+    from pyslam_amd.device import DeviceProblem
+    from pyslam_amd.distributed import ShardedDeviceProblem
+    lp, _ = synthetic.stereo_ba(num_kf=40, num_lm=4000, obs_per_lm=6, half_window=8, seed=3)
+    ref = DeviceProblem(lp, stream=torch.cuda.current_stream().cuda_stream)
+    sh = ShardedDeviceProblem(lp, dist1, exchange=exchange)
+    assert sh.native is not None
+    ref.set_option('lagged_inverse', 0)
+    for d in (ref, sh.dev):
+        d.set_option('cg_explicit_min_rows', 0)
+        d.set_option('cg_split_min_rows', 0)
+        # (8 coarse intervals: the one-launch form needs at most three coarse nodes under eight consecutive rows -- build_coarse:
+        #  xf_ok --, and the 19 intervals these options get by themselves on 39 reduced poses leave the three-launch form, which
+        #  has no fallback to take)
+        d.set_option('coarse_groups', 8)
+    for d in (ref, sh):
+        d.set_expect_next(expect)
+    for it in (1, 2, 3):
+        if it == arm_it:
+            for d in (ref, sh.dev):
+                d.set_option('cg_force_breakdown', 1 if arm_it == 1 else 6)
+        a = ref.gn_iteration(0., 1e-12, 1000, True)
+        b = sh.gn_iteration(0., 1e-12, 1000, True)
+        assert a[0] == b[0] and a[2] == b[2]                            # cost and CG iterations: identical
+        assert abs(a[1] - b[1]) <= 1e-15 * a[1]
+        fell = 1 if it >= arm_it else 0
+        for d in (ref, sh.dev):
+            assert d.get_info()['xcg_fused_fallbacks'] == fell and d.get_option('cg_force_breakdown') == 0
+    pa, la = ref.get_params()
+    pb, lb = sh.get_params()
+    assert np.array_equal(pa, pb) and np.array_equal(la, lb)
+    assert sh.eval_cost(True) == ref.eval_cost(True)
+    for d in (ref, sh.dev):
+        assert d.get_info()['xcg_fused_solves'] >= 3                    # (one fallback, not for ever)
+    sh.close()
+    ref.close()
+
+
 def _two_rank_worker(rank, world, port, out, native, exchange='allreduce'):
     """One of two processes sharing cuda:0: the REAL device code on a landmark shard, the collectives over
     gloo (RCCL refuses two ranks on one device; the arithmetic of the exchange is the same)."""

@@ -32,6 +32,7 @@ CHAIN = {
     'schur_pipeline': (1, 'bool', None, None, None, 0),
     'coarse_lag': (1, 'bool', None, None, None, 0),
     'cg_force_restart': (0, 'bool', None, None, None, 0),
+    'cg_force_breakdown': (0, 'int', None, None, None, 0),
     'xcg_restrict_fused': (1, 'bool', None, None, None, 0),
     'band_chol': (1, 'bool', None, None, None, FACTOR),
     'lm_packed': (1, 'bool', None, None, None, 0),
@@ -120,8 +121,9 @@ def table(request, tmp_path_factory):
 def test_the_names_are_the_chains(table):
     assert len(table.names) == len(set(table.names))               # no name twice
     assert set(table.names) == set(CHAIN)
-    # 46 in the table + the two early names = the 48 names the chain compared against (in both builds)
-    assert len(CHAIN) == 46 and not set(EARLY) & set(CHAIN)
+    # 46 in the table + the two early names = the 48 names the chain compared against (in both builds); + the test hook
+    # "cg_force_breakdown", which the chain never had
+    assert len(CHAIN) == 47 and not set(EARLY) & set(CHAIN)
     for name in REMOVED + EARLY + ('', 'pcg_variant ', 'PCG_VARIANT'):
         buf = table.fresh()
         before = buf.raw

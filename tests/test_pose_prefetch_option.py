@@ -1,7 +1,7 @@
 """The option of the pose pass's load order and accumulation ("pose_prefetch") is handled by ps_set_option ahead of the option
 table, as "rows_regs" and "packed_prefetch" are (tests/test_options_host.py pins the table's rows to the chain it replaced).
 No GPU: the sources, the public header and the binding are read and held together -- the name is set, read back and documented,
-it is not also a row of the table (which keeps its 46 names), the launch site names both kernels and every instantiation of the
+it is not also a row of the table (whose names stay those of tests/test_options_host.py), the launch site names both kernels and every instantiation of the
 new one, and the parity tap the GPU test uses is declared where the binding expects it."""
 import os
 import re
@@ -29,12 +29,13 @@ def test_the_name_is_set_read_back_and_documented():
         assert '`%s`' % NAME in read(doc), doc
 
 
-def test_the_option_table_keeps_its_46_names():
+def test_the_option_is_not_a_row_of_the_table():
+    """(47 rows: the 46 of the chain the table replaced and the test hook "cg_force_breakdown")"""
     table = read('pyslam_amd', 'csrc', 'ps_options.h')
     assert '"%s"' % NAME not in table
     rows = re.findall(r'^\s*\{"(\w+)", ', table, re.M)
     from test_options_host import CHAIN
-    assert len(rows) == 46 and set(rows) == set(CHAIN) and NAME not in CHAIN
+    assert len(rows) == 47 and set(rows) == set(CHAIN) and NAME not in CHAIN
 
 
 def test_the_launch_site_chooses_by_the_option_the_chunk_and_lambda():
