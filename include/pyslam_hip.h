@@ -618,6 +618,29 @@ int ps_sparse_normal_direct(int32_t m, int32_t n, const int32_t* j_row_ptr, cons
  * Stands in for the coarse-level part of scipy.sparse.linalg.spsolve (reference pyslam/problem.py:186); test and measurement entry. */
 int ps_debug_band_inverse(const double* a, int32_t ncb, int32_t dof, int32_t bw, int32_t chunk_nodes, float* ainv_out,
                           double* elapsed_us);
+/* The blocked dense factorisation chain on its own (csrc/ps_host_bchol.h: bchol_chain, the one launch sequence behind the coarse
+ * level beyond 90 unknowns, the lagged inverse's direct seed, ps_covariance_marginals and ps_sparse_normal_direct; kernels
+ * k_bchol_panel / k_bchol_update / k_btri_inverse / k_btri_merge / k_btri_clear and k_xcg_ainv).  Test and measurement entries;
+ * no production path calls them.
+ * ps_debug_dense_factor: `a` is a symmetric positive definite matrix on the host, n x n row-major, n <= 8192; the lower triangle
+ *   is read.  Runs the chain as production does, on a stream of its own, and returns every stage (any out pointer may be NULL):
+ *   l_out (n x n): the working matrix, L below the 24 x 24 diagonal tiles (the tiles themselves and the upper triangle keep A: the
+ *   tiles' factors are never written back); tinv_out (ceil(n / 24) tiles of 24 x 24, lower triangular, zero-padded): the inverses
+ *   of the diagonal tiles' factors; li_out, lit_out (n x n): L^-1 and its transpose; ainv_out (n x ld floats): A^-1 in fp32, both
+ *   triangles; diag_fail: the count of non-positive (or NaN) pivots -- with diag_fail NULL such a matrix is an error instead;
+ *   elapsed_us: GPU time of the chain's launches (second of two runs).
+ *   flags bit 0: the folded CG's dense-output form (zero fill, k_btri_clear: the strict upper triangle of li_out and the strict
+ *   lower triangle of lit_out are zero); without it the explicit PCG's form, where li_out outside its lower triangle and the
+ *   192 x 192 diagonal blocks (lit_out: outside the upper triangle and those blocks) is unspecified and comes back as NaN, the
+ *   entry's pre-fill.  flags bits 8..15: ld = n + that many columns; ainv_out's contents go in, and what k_xcg_ainv leaves alone
+ *   (the columns from n on) comes back unchanged.
+ * ps_debug_bchol_slab: host only, no device needed.  Which rows of a panel of m rows and w (1..24) columns workgroup `block` of
+ *   k_bchol_panel owns, found by walking its 256 threads x 4 entries through the kernel's own mapping function (ps_bchol_slab,
+ *   csrc/ps_k_coarse.h): rows [row_lo, row_hi), `entries` cells, `grid` workgroups in the launch.  A workgroup owns whole rows:
+ *   the panel is factored in place, and a row shared between two workgroups would be read by one while the other overwrites it. */
+int ps_debug_dense_factor(const double* a, int32_t n, int32_t flags, double* l_out, double* tinv_out, double* li_out, double* lit_out,
+                          float* ainv_out, int32_t* diag_fail, double* elapsed_us);
+int ps_debug_bchol_slab(int32_t m, int32_t w, int32_t block, int32_t* row_lo, int32_t* row_hi, int32_t* entries, int32_t* grid);
 /* The lagged dense inverse's kernels on their own (csrc/ps_k_ldi.h; option "lagged_inverse"): test entries that run the
  * production kernels and change nothing in them; no production path calls them.
  * ps_debug_ldi_gemm: C = alpha A B + beta Dm + gamma I by the fp32 MFMA product k_ldi_gemm, launched exactly as the Newton-Schulz
@@ -647,7 +670,8 @@ int ps_debug_ldi_read(ps_problem* h, int32_t what, double* out, int64_t capacity
  * factorisation kernels run `launches` times on a stream of their own -- lowest priority if `lowprio` -- while, if `aggressor`,
  * streaming copy kernels keep an ordinary stream busy; every output is compared bit for bit with one produced on an idle device.
  * mode 0: serial band walk (k_band_chol + k_band_inverse_rl); 1: partitioned band factorisation (BandPart); 2: dense LDS-resident
- * k_coarse_chol + k_xcg_ainv (ncb dof <= 90); 3: the same with its matrices in global scratch; + 8: the input is produced on the
+ * k_coarse_chol + k_xcg_ainv (ncb dof <= 90); 3: the same with its matrices in global scratch; 4: the blocked chain (bchol_chain:
+ * k_bchol_panel / k_bchol_update / k_btri_inverse / k_btri_merge) + k_xcg_ainv on a working copy, any ncb dof, `bw` ignored; + 8: the input is produced on the
  * same stream by a copy kernel in front of every factorisation (the buffer holds 2 A before); + 16: with an event recorded in
  * between.  `a` as ps_debug_band_inverse.
  * -> n_diff: launches whose fp32 inverse differs from the reference in any bit; n_pivot: launches that reported a non-positive

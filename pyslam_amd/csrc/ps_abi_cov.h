@@ -53,16 +53,7 @@ int ps_covariance_marginals(ps_problem* h, double* pose_blocks, double* point_bl
         if (D == 6) hipLaunchKernelGGL(k_ldi_dense64<6>, dim3(h->nnzb), dim3(64), 0, st, h->brow_of, h->col_idx, h->S, A, (int)n);
         else hipLaunchKernelGGL(k_ldi_dense64<3>, dim3(h->nnzb), dim3(64), 0, st, h->brow_of, h->col_idx, h->S, A, (int)n);
         hipLaunchKernelGGL(k_cov_diag_save, dim3(cdiv(n, 256)), dim3(256), 0, st, (int)n, A, diag);
-        const int nsteps = cdiv(n, PS_BC_W);
-        for (int s2 = 0; s2 < nsteps; ++s2) {
-            const int j0 = s2 * PS_BC_W, w = std::min<int>(PS_BC_W, (int)n - j0), m = (int)n - j0 - w;
-            hipLaunchKernelGGL(k_bchol_panel, dim3(std::max(1, cdiv((long)m * w, 1024))), dim3(256), 0, st, (int)n, j0, A,
-                               Tinv + (size_t)s2 * PS_BC_W * PS_BC_W, stat);
-            if (m > 0) {
-                const int nt = cdiv(m, 32);
-                hipLaunchKernelGGL(k_bchol_update, dim3(nt * (nt + 1) / 2), dim3(256), 0, st, (int)n, j0, w, A);
-            }
-        }
+        if (bchol_chain(st, (int)n, BCHOL_FACTOR, A, Tinv, stat, nullptr, nullptr, nullptr, 0)) return -1;
         hipLaunchKernelGGL(k_cov_pivot_check, dim3(cdiv(n, 256)), dim3(256), 0, st, (int)n, diag, Tinv, stat);
         int32_t hstat[ST_NWORDS];
         HIP_OK(hipMemcpyAsync(hstat, stat, sizeof(hstat), hipMemcpyDeviceToHost, st));
@@ -71,13 +62,8 @@ int ps_covariance_marginals(ps_problem* h, double* pose_blocks, double* point_bl
             return fail("ps_covariance_marginals: the reduced system is singular or not positive definite (gauge freedom? hold a "
                         "pose constant or add a prior)");
         // L^-1 and L^-T, then Sigma = L^-T L^-1 into A's place (A is not read after the merges), mirrored
-        const size_t inv_lds = ((size_t)PS_BI_S0 + PS_BC_W) * PS_BI_CW * sizeof(double);
-        hipLaunchKernelGGL(k_btri_inverse, dim3(cdiv(n, PS_BI_CW)), dim3(256), inv_lds, st, (int)n, A, Tinv, Li, LiT);
-        for (int s2 = PS_BI_S0; s2 < n; s2 *= 2) {
-            const int pairs = cdiv(n, 2 * s2), nt = cdiv(s2, PS_BM_T);
-            for (int stage = 0; stage < 2; ++stage)
-                hipLaunchKernelGGL(k_btri_merge, dim3(pairs * nt * nt), dim3(256), 0, st, (int)n, s2, stage, A, Li, LiT);
-        }
+        // (k_cov_sigma reads the lower triangle of L^-1 only: the chain's form without zero fill, ps_host_bchol.h)
+        if (bchol_chain(st, (int)n, BCHOL_INVERSE, A, Tinv, stat, Li, LiT, nullptr, 0)) return -1;
         const int nt = cdiv(n, PS_CS_T);
         hipLaunchKernelGGL(k_cov_sigma, dim3(nt * (nt + 1) / 2), dim3(256), 0, st, (int)n, Li, A);
         hipLaunchKernelGGL(k_cov_mirror, dim3(cdiv(n, 32), cdiv(n, 32)), dim3(256), 0, st, (int)n, A);

@@ -307,15 +307,8 @@ int ps_sparse_normal_direct(int32_t m, int32_t n, const int32_t* j_row_ptr, cons
     hipLaunchKernelGGL(k_spd_normal, dim3(cdiv((long)n * n, 256)), dim3(256), 0, st, n, bJr.as<int32_t>(), bJc.as<int32_t>(), bJv.as<double>(),
                        bTr.as<int32_t>(), bTc.as<int32_t>(), bTv.as<double>(), H);
     HIP_OK(hipMemcpyAsync(A, H, (size_t)n * n * 8, hipMemcpyDeviceToDevice, st));
-    for (int s2 = 0; s2 < nsteps; ++s2) {                      // blocked right-looking Cholesky over the whole chip
-        const int j0 = s2 * PS_BC_W, w = std::min(PS_BC_W, n - j0), mrem = n - j0 - w;
-        hipLaunchKernelGGL(k_bchol_panel, dim3(std::max(1, cdiv((long)mrem * w, 1024))), dim3(256), 0, st, n, j0, A,
-                           bTi.as<double>() + (size_t)s2 * PS_BC_W * PS_BC_W, bst.as<int32_t>());
-        if (mrem > 0) {
-            const int nt = cdiv(mrem, 32);
-            hipLaunchKernelGGL(k_bchol_update, dim3(nt * (nt + 1) / 2), dim3(256), 0, st, n, j0, w, A);
-        }
-    }
+    // blocked right-looking Cholesky over the whole chip (ps_host_bchol.h; substitutions through the factor, no inverse)
+    if (bchol_chain(st, n, BCHOL_FACTOR, A, bTi.as<double>(), bst.as<int32_t>(), nullptr, nullptr, nullptr, 0)) return -1;
     auto solve_into = [&](double* v) {                         // v <- (L L^T)^-1 v
         hipLaunchKernelGGL(k_spd_subst, dim3(1), dim3(512), 0, st, n, (const double*)A, (const double*)bTi.as<double>(), v, 0);
         hipLaunchKernelGGL(k_spd_subst, dim3(1), dim3(512), 0, st, n, (const double*)A, (const double*)bTi.as<double>(), v, 1);
@@ -337,9 +330,10 @@ int ps_sparse_normal_direct(int32_t m, int32_t n, const int32_t* j_row_ptr, cons
     }
     int32_t stw[ST_NWORDS];
     HIP_OK(hipMemcpy(stw, bst.p, sizeof(stw), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(dx, bx.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     if (relres_out) *relres_out = rel;
+    // (a failed factor leaves NaNs in x: dx stays as the caller gave it)
     if (stw[ST_DIAG_FAIL]) return fail("normal matrix is not positive definite to rounding (dense direct solve)");
+    HIP_OK(hipMemcpy(dx, bx.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -355,16 +349,17 @@ int ps_debug_factor_stress(const double* a, int32_t ncb, int32_t dof, int32_t bw
     // 16 = an event is recorded between producer and factorisation (as xcg_side_enqueue does with ev_acdone)
     const bool produce = (mode & 8) != 0, with_event = (mode & 16) != 0;
     mode &= 7;
-    if (!a || !n_diff || !n_pivot || ncb <= 0 || (dof != 3 && dof != 6) || mode < 0 || mode > 3 || launches < 1) return fail("bad argument");
+    if (!a || !n_diff || !n_pivot || ncb <= 0 || (dof != 3 && dof != 6) || mode < 0 || mode > 4 || launches < 1) return fail("bad argument");
     if (mode <= 1 && (bw < 1 || bw > PS_BAND_MAXB)) return fail("bad band width");
     if (need_device()) return -1;
     const int nc = ncb * dof;
     if (mode == 2 && nc > 90) return fail("mode 2 (LDS-resident k_coarse_chol) needs ncb dof <= 90");
-    DevBuf bA, bInv, bLr, bLc, brd, bXs, bst, bLi, bLiT, bsc, ga, gb;
+    DevBuf bA, bInv, bLr, bLc, brd, bXs, bst, bLi, bLiT, bsc, bTi, ga, gb;
     const size_t gn = (size_t)16 << 20;
     if (bA.get((size_t)nc * nc * 8) || bInv.get((size_t)nc * nc * 4) || bst.get(ST_NWORDS * 4) || bLr.get((size_t)nc * PS_BAND_W * 8) ||
         bLc.get((size_t)nc * PS_BAND_W * 8) || brd.get((size_t)nc * 8) || bXs.get((size_t)nc * nc * 8) || bLi.get((size_t)nc * nc * 8) ||
-        bLiT.get((size_t)nc * nc * 8) || bsc.get((size_t)2 * nc * nc * 8) || ga.get(gn * 8) || gb.get(gn * 8)) return -1;
+        bLiT.get((size_t)nc * nc * 8) || bsc.get((size_t)2 * nc * nc * 8) || bTi.get((size_t)cdiv(nc, PS_BC_W) * PS_BC_W * PS_BC_W * 8) ||
+        ga.get(gn * 8) || gb.get(gn * 8)) return -1;
     HIP_OK(hipMemcpy(bA.p, a, (size_t)nc * nc * 8, hipMemcpyHostToDevice));
     HIP_OK(hipMemset(ga.p, 0, gn * 8));
     DevBuf bA1, bA2;
@@ -410,6 +405,11 @@ int ps_debug_factor_stress(const double* a, int32_t ncb, int32_t dof, int32_t bw
                                (const double*)brd.as<double>(), bXs.as<double>(), bInv.as<float>(), (const BandInvItem*)nullptr, (double*)nullptr, nc);
         } else if (mode == 1) {
             if (dof == 6 ? bp->run<6>(st, bA.as<double>(), nc, bInv.as<float>(), nc, bst.as<int32_t>()) : bp->run<3>(st, bA.as<double>(), nc, bInv.as<float>(), nc, bst.as<int32_t>())) return -1;
+        } else if (mode == 4) {
+            // the blocked chain as xcg_coarse_inverse runs it: working copy of A by a kernel, factor, L^-1 without zero fill, A^-1
+            copy_doubles(st, bsc.as<double>(), bA.as<double>(), (size_t)nc * nc);
+            if (bchol_chain(st, nc, BCHOL_FACTOR | BCHOL_INVERSE | BCHOL_AINV, bsc.as<double>(), bTi.as<double>(), bst.as<int32_t>(),
+                            bLi.as<double>(), bLiT.as<double>(), bInv.as<float>(), nc)) return -1;
         } else {
             if (mode == 2) {
                 if (dof == 6) hipLaunchKernelGGL((k_coarse_chol<6, true>), dim3(1), dim3(1024), chol_lds, st, ncb, bA.as<double>(), bLi.as<double>(), bLiT.as<double>(), bst.as<int32_t>(), nullptr);
@@ -418,7 +418,7 @@ int ps_debug_factor_stress(const double* a, int32_t ncb, int32_t dof, int32_t bw
                 if (dof == 6) hipLaunchKernelGGL((k_coarse_chol<6, false>), dim3(1), dim3(1024), 0, st, ncb, bA.as<double>(), bLi.as<double>(), bLiT.as<double>(), bst.as<int32_t>(), bsc.as<double>());
                 else hipLaunchKernelGGL((k_coarse_chol<3, false>), dim3(1), dim3(1024), 0, st, ncb, bA.as<double>(), bLi.as<double>(), bLiT.as<double>(), bst.as<int32_t>(), bsc.as<double>());
             }
-            hipLaunchKernelGGL(k_xcg_ainv, dim3(cdiv(nc, PS_AI_T) * (cdiv(nc, PS_AI_T) + 1) / 2), dim3(256), 0, st, nc, bLi.as<double>(), bInv.as<float>(), nc);
+            bchol_ainv(st, nc, bLi.as<double>(), bInv.as<float>(), nc);
         }
         return 0;
     };
@@ -501,6 +501,85 @@ int ps_debug_band_inverse(const double* a, int32_t ncb, int32_t dof, int32_t bw,
     HIP_OK(hipMemcpy(stw, bst.p, sizeof(stw), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(ainv_out, bInv.p, (size_t)nc * nc * 4, hipMemcpyDeviceToHost));
     if (stw[ST_DIAG_FAIL]) return fail("band factorisation: the matrix is not positive definite");
+    return 0;
+}
+
+// ---- the blocked dense factorisation chain on its own (csrc/ps_host_bchol.h; tests/test_gpu_bchol_kernels.py) ----------------
+// Every stage's output of bchol_chain on a host matrix, on a stream of its own.  flags bit 0: the folded CG's dense-output form
+// (zero fill + k_btri_clear), else the explicit PCG's; bits 8..15: extra columns of ainv_out's leading dimension (ld = n + that;
+// ainv_out's contents go in, what k_xcg_ainv leaves alone comes back unchanged).  Li and LiT are pre-filled with NaN bit patterns:
+// what a form leaves unspecified comes back as NaN, and a kernel that read it would show.
+int ps_debug_dense_factor(const double* a, int32_t n, int32_t flags, double* l_out, double* tinv_out, double* li_out, double* lit_out,
+                          float* ainv_out, int32_t* diag_fail, double* elapsed_us) {
+    if (!a || n <= 0 || (flags & ~0xff01)) return fail("ps_debug_dense_factor: bad argument");
+    if (n > PS_SPD_MAXN) return fail("ps_debug_dense_factor: more than 8192 unknowns");
+    if (need_device()) return -1;
+    const int ld = n + ((flags >> 8) & 0xff), nsteps = cdiv(n, PS_BC_W);
+    const size_t nn = (size_t)n * n, nti = (size_t)nsteps * PS_BC_W * PS_BC_W, ninv = (size_t)n * ld;
+    DevBuf bA0, bA, bTi, bLi, bLiT, bInv, bInv0, bst;
+    if (bA0.get(nn * 8) || bA.get(nn * 8) || bTi.get(nti * 8) || bLi.get(nn * 8) || bLiT.get(nn * 8) || bInv.get(ninv * 4) ||
+        bInv0.get(ninv * 4) || bst.get(ST_NWORDS * 4)) return -1;
+    HIP_OK(hipMemcpy(bA0.p, a, nn * 8, hipMemcpyHostToDevice));
+    if (ainv_out) HIP_OK(hipMemcpy(bInv0.p, ainv_out, ninv * 4, hipMemcpyHostToDevice));
+    else HIP_OK(hipMemset(bInv0.p, 0, ninv * 4));
+    hipStream_t st = nullptr;
+    HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    struct St { hipStream_t s; ~St() { hipStreamDestroy(s); } } stg{st};
+    hipEvent_t e0, e1;
+    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+    struct Ev { hipEvent_t a, b; ~Ev() { hipEventDestroy(a); hipEventDestroy(b); } } evs{e0, e1};
+    const int stages = BCHOL_FACTOR | BCHOL_INVERSE | BCHOL_AINV | ((flags & 1) ? BCHOL_DENSE_OUT : 0);
+    for (int rep = 0; rep < 2; ++rep) {                       // (the second run is the one timed: the first loads the kernels)
+        HIP_OK(hipMemcpyAsync(bA.p, bA0.p, nn * 8, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipMemcpyAsync(bInv.p, bInv0.p, ninv * 4, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipMemsetAsync(bst.p, 0, ST_NWORDS * 4, st));
+        HIP_OK(hipMemsetAsync(bTi.p, 0, nti * 8, st));
+        HIP_OK(hipMemsetAsync(bLi.p, 0xff, nn * 8, st));
+        HIP_OK(hipMemsetAsync(bLiT.p, 0xff, nn * 8, st));
+        HIP_OK(hipEventRecord(e0, st));
+        if (bchol_chain(st, n, stages, bA.as<double>(), bTi.as<double>(), bst.as<int32_t>(), bLi.as<double>(), bLiT.as<double>(),
+                        bInv.as<float>(), ld)) return -1;
+        HIP_OK(hipEventRecord(e1, st));
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+    if (elapsed_us) *elapsed_us = 1e3 * ms;
+    int32_t stw[ST_NWORDS];
+    HIP_OK(hipMemcpy(stw, bst.p, sizeof(stw), hipMemcpyDeviceToHost));
+    if (l_out) HIP_OK(hipMemcpy(l_out, bA.p, nn * 8, hipMemcpyDeviceToHost));
+    if (tinv_out) HIP_OK(hipMemcpy(tinv_out, bTi.p, nti * 8, hipMemcpyDeviceToHost));
+    if (li_out) HIP_OK(hipMemcpy(li_out, bLi.p, nn * 8, hipMemcpyDeviceToHost));
+    if (lit_out) HIP_OK(hipMemcpy(lit_out, bLiT.p, nn * 8, hipMemcpyDeviceToHost));
+    if (ainv_out) HIP_OK(hipMemcpy(ainv_out, bInv.p, ninv * 4, hipMemcpyDeviceToHost));
+    if (diag_fail) *diag_fail = stw[ST_DIAG_FAIL];
+    else if (stw[ST_DIAG_FAIL]) return fail("ps_debug_dense_factor: the matrix is not positive definite");
+    return 0;
+}
+
+// Host only: which rows of a panel of m rows x w columns workgroup `block` of k_bchol_panel owns -- found by walking every
+// (thread, entry) of that workgroup through ps_bchol_slab, the function the kernel itself uses.  [row_lo, row_hi): the rows it
+// touches; entries: the distinct (row, column) cells it owns; grid: workgroups of the launch.  Needs no device.
+int ps_debug_bchol_slab(int32_t m, int32_t w, int32_t block, int32_t* row_lo, int32_t* row_hi, int32_t* entries, int32_t* grid) {
+    if (m < 0 || m > (1 << 24) || w < 1 || w > PS_BC_W || block < 0 || block > (1 << 20) || !row_lo || !row_hi || !entries || !grid) return fail("ps_debug_bchol_slab: bad argument");
+    int lo = INT_MAX, hi = -1, g = 0;
+    std::vector<std::pair<int, int>> cells;
+    for (int t = 0; t < 256; ++t)
+        for (int k = 0; k < PS_BC_SLAB / 256; ++k) {
+            int r, c;
+            g = ps_bchol_slab(m, w, block, t, k, &r, &c);
+            if (r < 0) continue;
+            if (r >= m || c < 0 || c >= w) return fail("ps_debug_bchol_slab: the mapping leaves the panel");
+            lo = std::min(lo, r); hi = std::max(hi, r);
+            cells.emplace_back(r, c);
+        }
+    std::sort(cells.begin(), cells.end());
+    if (std::adjacent_find(cells.begin(), cells.end()) != cells.end()) return fail("ps_debug_bchol_slab: a cell is owned twice");
+    *entries = (int32_t)cells.size();
+    *row_lo = hi < 0 ? 0 : lo;
+    *row_hi = hi < 0 ? 0 : hi + 1;
+    *grid = g;
     return 0;
 }
 

@@ -1149,10 +1149,10 @@ int ps_dense_normal_solve(const double* J, const double* r, int32_t m, int32_t n
     HIP_OK(hipMemcpy(B.data(), dB, B.size() * sizeof(double), hipMemcpyDeviceToHost));
     int32_t st[ST_NWORDS];
     HIP_OK(hipMemcpy(st, dst, sizeof(st), hipMemcpyDeviceToHost));
+    if (st[ST_DIAG_FAIL]) return fail("normal matrix is not positive definite");     // (dx and covariance stay as the caller gave them)
     for (int i = 0; i < n; ++i) {
         dx[i] = B[(size_t)i * nrhs];
         if (covariance) for (int j = 0; j < n; ++j) covariance[(size_t)i * n + j] = B[(size_t)i * nrhs + 1 + j];
     }
-    if (st[ST_DIAG_FAIL]) return fail("normal matrix is not positive definite");
     return 0;
 }

@@ -636,32 +636,11 @@ int coarse_factor(ps_problem* h, hipStream_t st, int buf, int32_t* stat) {
         double* A = h->chol_scratch;
         double* Tinv = A + (size_t)nc * nc;
         copy_doubles(st, A, h->Ac, (size_t)nc * nc);
-        const int nsteps = cdiv(nc, PS_BC_W);
-        for (int s2 = 0; s2 < nsteps; ++s2) {
-            const int j0 = s2 * PS_BC_W, w = std::min(PS_BC_W, nc - j0), m = nc - j0 - w;
-            hipLaunchKernelGGL(k_bchol_panel, dim3(std::max(1, cdiv((long)m * w, 1024))), dim3(256), 0, st, nc, j0, A,
-                               Tinv + (size_t)s2 * PS_BC_W * PS_BC_W, stat);
-            if (m > 0) {
-                const int nt = cdiv(m, 32);
-                hipLaunchKernelGGL(k_bchol_update, dim3(nt * (nt + 1) / 2), dim3(256), 0, st, nc, j0, w, A);
-            }
-        }
-        // L^-1: diagonal blocks by substitution, the rest merged level by level with triangular products
-        // (the explicit PCG only reads the lower triangle of L^-1 and overwrites the transpose: no zero fill there)
+        // factor, then L^-1 (ps_host_bchol.h).  The explicit PCG only reads the lower triangle of L^-1 and overwrites the
+        // transpose: no zero fill there
         const bool dense_out = nc > PS_BI_S0 && !h->cg_explicit;
-        if (dense_out) {
-            HIP_OK(hipMemsetAsync(h->Lci2[buf], 0, (size_t)nc * nc * sizeof(double), st));
-            HIP_OK(hipMemsetAsync(h->LciT2[buf], 0, (size_t)nc * nc * sizeof(double), st));
-        }
-        const size_t inv_lds = ((size_t)PS_BI_S0 + PS_BC_W) * PS_BI_CW * sizeof(double);
-        hipLaunchKernelGGL(k_btri_inverse, dim3(cdiv(nc, PS_BI_CW)), dim3(256), inv_lds, st, nc, A, Tinv, h->Lci2[buf], h->LciT2[buf]);
-        for (int s2 = PS_BI_S0; s2 < nc; s2 *= 2) {
-            const int pairs = cdiv(nc, 2 * s2), nt = cdiv(s2, PS_BM_T);
-            for (int stage = 0; stage < 2; ++stage)
-                hipLaunchKernelGGL(k_btri_merge, dim3(pairs * nt * nt), dim3(256), 0, st, nc, s2, stage, A, h->Lci2[buf], h->LciT2[buf]);
-        }
-        if (dense_out)
-            hipLaunchKernelGGL(k_btri_clear, dim3(cdiv((long)nc * nc, 256)), dim3(256), 0, st, nc, h->LciT2[buf]);
+        if (bchol_chain(st, nc, BCHOL_FACTOR | BCHOL_INVERSE | (dense_out ? BCHOL_DENSE_OUT : 0), A, Tinv, stat, h->Lci2[buf],
+                        h->LciT2[buf], nullptr, 0)) return -1;
     } else {
         hipLaunchKernelGGL((k_coarse_chol<D, false>), dim3(1), dim3(1024), 0, st, ncb, h->Ac, h->Lci2[buf],
                            h->LciT2[buf], stat, h->chol_scratch);
@@ -703,7 +682,7 @@ int xcg_coarse_inverse(ps_problem* h, hipStream_t st, int buf, int32_t* stat) {
         return 0;
     }
     if (coarse_factor<D>(h, st, buf, stat)) return -1;
-    hipLaunchKernelGGL(k_xcg_ainv, dim3(cdiv(nc, PS_AI_T) * (cdiv(nc, PS_AI_T) + 1) / 2), dim3(256), 0, st, nc, h->Lci2[buf], (float*)h->LciT2[buf], nc);
+    bchol_ainv(st, nc, h->Lci2[buf], (float*)h->LciT2[buf], nc);
     return 0;
 }
 

@@ -121,25 +121,11 @@ int ldi_direct_enqueue(ps_problem* h, int state, int lag) {
     hipLaunchKernelGGL(k_ldi_dense64<D>, dim3(h->nnzb), dim3(64), 0, st, h->brow_of, h->col_idx, h->S, A, n);
     HIP_OK(hipEventRecord(h->ev_ldi_sread, st));              // S has been read: the next linearisation may overwrite it
     h->ldi_sread_pending = true;
-    for (int s2 = 0; s2 < nsteps; ++s2) {
-        const int j0 = s2 * PS_BC_W, w = std::min(PS_BC_W, n - j0), m = n - j0 - w;
-        hipLaunchKernelGGL(k_bchol_panel, dim3(std::max(1, cdiv((long)m * w, 1024))), dim3(256), 0, st, n, j0, A,
-                           h->ldi_Tinv + (size_t)s2 * PS_BC_W * PS_BC_W, h->ldi_stat);
-        if (m > 0) {
-            const int nt = cdiv(m, 32);
-            hipLaunchKernelGGL(k_bchol_update, dim3(nt * (nt + 1) / 2), dim3(256), 0, st, n, j0, w, A);
-        }
-    }
-    const size_t inv_lds = ((size_t)PS_BI_S0 + PS_BC_W) * PS_BI_CW * sizeof(double);
-    hipLaunchKernelGGL(k_btri_inverse, dim3(cdiv(n, PS_BI_CW)), dim3(256), inv_lds, st, n, A, h->ldi_Tinv, h->ldi_Li, h->ldi_LiT);
-    for (int s2 = PS_BI_S0; s2 < n; s2 *= 2) {
-        const int pairs = cdiv(n, 2 * s2), nt = cdiv(s2, PS_BM_T);
-        for (int stage = 0; stage < 2; ++stage)
-            hipLaunchKernelGGL(k_btri_merge, dim3(pairs * nt * nt), dim3(256), 0, st, n, s2, stage, A, h->ldi_Li, h->ldi_LiT);
-    }
+    // (the explicit PCG's form of the chain, ps_host_bchol.h: k_xcg_ainv reads the lower triangle of L^-1 only, no zero fill)
+    if (bchol_chain(st, n, BCHOL_FACTOR | BCHOL_INVERSE, A, h->ldi_Tinv, h->ldi_stat, h->ldi_Li, h->ldi_LiT, nullptr, 0)) return -1;
     const int wb = h->ldi_cur < 0 ? 0 : (h->ldi_cur ^ 1);
     HIP_OK(hipMemsetAsync(h->ldi_Xu[wb], 0, (size_t)np * np * sizeof(float), st));
-    hipLaunchKernelGGL(k_xcg_ainv, dim3(cdiv(n, PS_AI_T) * (cdiv(n, PS_AI_T) + 1) / 2), dim3(256), 0, st, n, h->ldi_Li, h->ldi_Xu[wb], np);
+    bchol_ainv(st, n, h->ldi_Li, h->ldi_Xu[wb], np);
     hipLaunchKernelGGL(k_ldi_direct_done, dim3(1), dim3(64), 0, st, h->ldi_stat, h->h_ldi_fro_dev);
     HIP_OK(hipEventRecord(h->ev_ldi, st));
     h->ldi_state = state; h->ldi_next = wb; h->ldi_ready_at = h->ldi_iter + lag; h->ldi_fro_limit = 0.1;

@@ -315,15 +315,32 @@ __global__ __launch_bounds__(1024) void k_coarse_chol(int ncb, const double* __r
 // single-workgroup factorisation out of L2.
 // ---------------------------------------------------------------------------
 #define PS_BC_W 24
+#define PS_BC_SLAB 1024                                    // panel entries one workgroup of k_bchol_panel owns at most: 4 per thread
+#define PS_HOSTDEV __host__ __device__
+// Who computes which entry of the panel below the tile (m rows of w columns): workgroup `block` owns PS_BC_SLAB / w WHOLE rows
+// (42 at w = 24), thread t its entries e = t + 256 n, n < 4, of that slab in row-major order.  -> the number of workgroups of
+// the launch (1 when m = 0: the tile alone); *row (0 .. m - 1, relative to the first row below the tile) and *col, *row = -1
+// where the thread has no such entry.  The kernel and every host-side grid computation go through this one function: a row
+// that two workgroups shared would be read by one while the other overwrites it in place (see k_bchol_panel).
+PS_HOSTDEV inline int ps_bchol_slab(int m, int w, int block, int t, int n, int* row, int* col)
+{
+    const int rows = PS_BC_SLAB / w, e = t + n * 256;
+    const int r = block * rows + e / w;
+    const bool mine = e < rows * w && r < m;
+    *row = mine ? r : -1;
+    *col = e % w;
+    return m > 0 ? (m + rows - 1) / rows : 1;
+}
+
 __global__ __launch_bounds__(256) void k_bchol_panel(
     int nc, int j0, double* __restrict__ A /* nc x nc row-major: lower triangle in, L (below the tiles) out */,
     double* __restrict__ Tinv /* PS_BC_W x PS_BC_W: inverse of this step's diagonal factor */,
     int32_t* __restrict__ status)
 {
     // Every workgroup factors the (tiny) diagonal tile itself -- 24 sequential steps in LDS, cheaper than a
-    // launch boundary -- and then owns a slab of 1024 panel entries, so the panel below the tile is spread over
-    // the chip.  The tile's factor itself is never needed again (only its inverse, Tinv), so nobody writes the
-    // tile back and the redundant readers do not race with a writer.
+    // launch boundary -- and then owns a slab of whole panel rows (ps_bchol_slab: at most 1024 entries), so the panel
+    // below the tile is spread over the chip.  The tile's factor itself is never needed again (only its inverse, Tinv),
+    // so nobody writes the tile back and the redundant readers do not race with a writer.
     __shared__ double sD[PS_BC_W * PS_BC_W], sI[PS_BC_W * PS_BC_W];
     const int t = threadIdx.x, w = min(PS_BC_W, nc - j0);
     for (int k = t; k < PS_BC_W * PS_BC_W; k += 256) {
@@ -358,16 +375,20 @@ __global__ __launch_bounds__(256) void k_bchol_panel(
     __syncthreads();
     if (blockIdx.x == 0)
         for (int k = t; k < PS_BC_W * PS_BC_W; k += 256) Tinv[k] = sI[k];
-    // this workgroup's slab of the panel below the tile: L_IJ = A_IJ L_JJ^-T.  A row's outputs only read that
-    // row's own w entries; they are all computed into registers before anything is overwritten.
-    const int total = (nc - j0 - w) * w, base = blockIdx.x * 1024;
+    // this workgroup's slab of the panel below the tile, in place: L_IJ = A_IJ L_JJ^-T.  Output (i, c) reads the ORIGINAL
+    // A[i][j0 .. j0 + c] of its own row only, and a row belongs to ONE workgroup: all of the slab's outputs are computed into
+    // registers, then the barrier, then the stores -- so nothing is overwritten that anybody still reads.  (Slabs of 1024
+    // consecutive ENTRIES cut a row of 24 in two at every slab boundary: the second workgroup read what the first one was
+    // overwriting, ordered by nothing but both being resident and in step.)
+    const int m = nc - j0 - w;
     double out[4];
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
-        const int idx = base + t + n * 256;
+        int r, c;
+        ps_bchol_slab(m, w, blockIdx.x, t, n, &r, &c);
         double v = 0.0;
-        if (idx < total) {
-            const int i = j0 + w + idx / w, c = idx % w;
+        if (r >= 0) {
+            const int i = j0 + w + r;
             for (int k = 0; k <= c; ++k) v += A[(size_t)i * nc + j0 + k] * sI[c * PS_BC_W + k];
         }
         out[n] = v;
@@ -375,8 +396,9 @@ __global__ __launch_bounds__(256) void k_bchol_panel(
     __syncthreads();
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
-        const int idx = base + t + n * 256;
-        if (idx < total) A[(size_t)(j0 + w + idx / w) * nc + j0 + idx % w] = out[n];
+        int r, c;
+        ps_bchol_slab(m, w, blockIdx.x, t, n, &r, &c);
+        if (r >= 0) A[(size_t)(j0 + w + r) * nc + j0 + c] = out[n];
     }
 }
 

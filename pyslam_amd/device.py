@@ -572,6 +572,45 @@ def band_inverse(A, ncb, dof, bw, chunk_nodes=0):
     return out, us.value
 
 
+def dense_factor(A, dense_out=False, ld_extra=0, ainv_fill=0.0):
+    """Every stage of the blocked dense factorisation chain on a host matrix (include/pyslam_hip.h: ps_debug_dense_factor).
+    -> dict: L (working matrix), Tinv (steps x 24 x 24), Li, LiT, ainv (n x (n + ld_extra) float32, pre-filled with ainv_fill),
+    diag_fail, us."""
+    lib = nat.require_gpu()
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    n = A.shape[0]
+    assert A.shape == (n, n) and 0 <= ld_extra < 256
+    steps = (n + 23) // 24
+    out = dict(L=np.zeros((n, n)), Tinv=np.zeros((steps, 24, 24)), Li=np.zeros((n, n)), LiT=np.zeros((n, n)),
+               ainv=np.full((n, n + ld_extra), ainv_fill, dtype=np.float32))
+    fail, us = C.c_int32(-1), C.c_double(0.0)
+    nat.check(lib.ps_debug_dense_factor(nat.f64p(A), n, (1 if dense_out else 0) | (ld_extra << 8), nat.f64p(out['L']), nat.f64p(out['Tinv']),
+                                        nat.f64p(out['Li']), nat.f64p(out['LiT']), out['ainv'].ctypes.data_as(C.POINTER(C.c_float)),
+                                        C.byref(fail), C.cast(C.byref(us), nat.c_f64p)))
+    out['diag_fail'], out['us'] = int(fail.value), us.value
+    return out
+
+
+def bchol_slab(m, w, block):
+    """(row_lo, row_hi, entries, grid) of workgroup `block` of k_bchol_panel on a panel of m rows x w columns (ps_debug_bchol_slab:
+    host only, no GPU needed)."""
+    lib = nat.load()
+    v = [C.c_int32() for _ in range(4)]
+    nat.check(lib.ps_debug_bchol_slab(m, w, block, *[C.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
+
+
+def factor_stress(A, ncb, dof, bw, mode, launches, lowprio=0, aggressor=0):
+    """(n_diff, n_pivot) of ps_debug_factor_stress: `launches` runs of a factorisation family beside an aggressor, each output
+    compared bit for bit with an idle run."""
+    lib = nat.require_gpu()
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    assert A.shape == (ncb * dof, ncb * dof)
+    nd, npv = C.c_int32(), C.c_int32()
+    nat.check(lib.ps_debug_factor_stress(nat.f64p(A), ncb, dof, bw, mode, launches, lowprio, aggressor, C.byref(nd), C.byref(npv)))
+    return int(nd.value), int(npv.value)
+
+
 def ldi_gemm(A, B, C0, M, N, K, alpha=1.0, beta=0.0, Dm=None, gamma=0.0, lda=None, ldb=None, ldd=None, ldc=None, krange=None,
              upper_only=False, dev_scale=None, fro_sentinel=None, need_gpu=True):
     """C = alpha A B + beta Dm + gamma I by the lagged inverse's fp32 MFMA product (include/pyslam_hip.h: ps_debug_ldi_gemm).

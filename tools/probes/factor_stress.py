@@ -1,5 +1,5 @@
 """The coarse level's factorisation kernels under a foreign load (include/pyslam_hip.h: ps_debug_factor_stress; DESIGN.md section 3
-"side stream"): every kernel family on a lowest-priority / an ordinary stream, with / without streaming kernels on another stream,
+"side stream"): every kernel family (modes 0-3: band forms and k_coarse_chol; 4: the blocked dense chain) on a lowest-priority / an ordinary stream, with / without streaming kernels on another stream,
 outputs compared bit for bit with an idle run.  Measurement infrastructure.   python tools/probes/factor_stress.py [launches]"""
 import ctypes as C
 import os
@@ -32,10 +32,11 @@ def banded_spd(ncb, dof, bw, seed):
 
 CASES = [('serial band walk  k_band_chol + k_band_inverse_rl', 0, 45, 6, 3), ('partitioned band  BandPart', 1, 101, 6, 3),
          ('dense LDS         k_coarse_chol<6,true> + k_xcg_ainv', 2, 13, 6, 12), ('dense global      k_coarse_chol<6,false> + k_xcg_ainv', 3, 20, 6, 19),
-         ('serial band, SE(2)', 0, 60, 3, 2), ('dense LDS, SE(2)', 2, 24, 3, 23)]
+         ('serial band, SE(2)', 0, 60, 3, 2), ('dense LDS, SE(2)', 2, 24, 3, 23),
+         ('blocked chain     k_bchol_* / k_btri_* + k_xcg_ainv (bw ignored)', 4, 64, 6, 6), ('blocked chain, 798 unknowns', 4, 133, 6, 6)]
 VARIANTS = [('', 0), (' [input produced by a kernel in front]', 8), (' [produced + event recorded in between]', 24)]
 if '--produce' in sys.argv:
-    CASES = [(n + v, m | bits, a, b, c) for n, m, a, b, c in CASES[:4] for v, bits in VARIANTS[1:]]
+    CASES = [(n + v, m | bits, a, b, c) for n, m, a, b, c in CASES[:4] + CASES[6:] for v, bits in VARIANTS[1:]]
 for name, mode, ncb, dof, bw in CASES:
     A = banded_spd(ncb, dof, bw, 11 + (mode & 7))
     for lowprio in (0, 1):
