@@ -768,6 +768,41 @@ int ps_sim3_ransac(const double* pts_1, const double* pts_2, const double* obs_1
                    const int32_t* sample_idx, int32_t num_hyp, const double* cam5, double thresh, int32_t fixed_scale,
                    int32_t refit_iters, double* S_21, double* scale, uint8_t* mask, int32_t* info, double* sq_err);
 
+/* Sim(3) pose graph: what consumes a verified loop constraint (definition: DESIGN.md section 7; restatement:
+   pyslam_amd/pipelines/simgraph.py; kernels: csrc/ps_k_sim3pg.h).  A stand-alone handle with kernels of its own; the core's
+   D = 3 / 6 solver is not involved.
+   Element: 13 doubles [R row-major (9) | t (3) | s], s > 0, p -> s R p + t.  Tangent [rho | phi | sigma]; update S <- exp(dx) S.
+   Edge (i, j, S_ji, W): r = W log(S_j S_i^-1 S_ji^-1) with a 7 x 7 stiffness W (edge_stiffness49 NULL: identity; an all-zero row
+   is an absent row), J_i = -W Ad(S_j S_i^-1), J_j = W, the robust loss per component as the pose factors of the core apply it.
+   held[v] != 0: vertex v contributes no unknowns (at least one must be held; an edge between two held vertices adds cost only).
+   The system is DENSE, n = 7 free vertices <= 8192, solved by the blocked Cholesky chain with one refinement step; a larger
+   graph, an index out of range, i == j, a non-finite input and a non-positive pivot are errors.
+   create:     host tables in; `stream` as everywhere (NULL: the default stream).
+   eval_cost:  the cost at the current vertices, summed in a fixed order (bit-reproducible).
+   linearize:  H_out (n x n, diagonal times 1 + lambda, both triangles), g_out (n; H dx = g), cost; any out pointer may be NULL.
+   iteration:  linearise, factor, solve, refine, retract, cost after the step; relres: ||g - H dx|| / ||g|| after the refinement.
+   solve:      the loop of Problem.solve under the linesearch != 0 meaning (an iteration's cost is the cost after its step) with
+               csrc/ps_stop_rule.h and options->lm_lambda as the fixed damping; cost_history needs max_iters + 2 entries.
+   debug_edges / debug_explog: test entries -- the edge kernel's tap, 105 doubles per edge: scaled residual (7), scaled J_i (49),
+               scaled J_j (49); the device exp, log of that and adjoint of that on a host table of n tangent vectors.
+   profile:    measurement entry -- enable != 0 times the stages of later iterations with events; stage_ms5 (or NULL): the last
+               iteration's edges, assemble, factor, substitute + refine, retract + cost, in ms. */
+typedef struct ps_sim3pg ps_sim3pg;
+int ps_sim3pg_create(int32_t num_vertices, const double* vertices13, const uint8_t* held, int32_t num_edges, const int32_t* edge_i,
+                     const int32_t* edge_j, const double* edge_obs13, const double* edge_stiffness49, int32_t loss_id, double loss_k,
+                     void* stream, ps_sim3pg** out);
+int ps_sim3pg_destroy(ps_sim3pg* h);
+int ps_sim3pg_set_vertices(ps_sim3pg* h, const double* vertices13);
+int ps_sim3pg_get_vertices(ps_sim3pg* h, double* vertices13);
+int ps_sim3pg_eval_cost(ps_sim3pg* h, double* cost);
+int ps_sim3pg_linearize(ps_sim3pg* h, double lambda, double* H_out, double* g_out, double* cost);
+int ps_sim3pg_iteration(ps_sim3pg* h, double lambda, double* cost_after, double* dx_norm, double* relres);
+int ps_sim3pg_solve(ps_sim3pg* h, const ps_solve_options* options, double* cost_history, int32_t cap, int32_t* n_history,
+                    int32_t* iterations, double* last_dx_norm);
+int ps_sim3pg_debug_edges(ps_sim3pg* h, double* tap105);
+int ps_sim3pg_debug_explog(int32_t n, const double* xi_in, double* S13_out, double* xi_back, double* adj49_out);
+int ps_sim3pg_profile(ps_sim3pg* h, int32_t enable, double* stage_ms5);
+
 /* Dense photometric alignment: one SE(3) pose, one residual per reference pixel --
    PhotometricResidualSE3 (pyslam/residuals/photometric_residual.py:38-161) inside Problem's Gauss-Newton
    iteration with element-wise IRLS (pyslam/problem.py:279-360), as the dense VO pipeline runs it per pyramid

@@ -8,3 +8,4 @@ from pyslam_amd.pipelines.keyframes import (Keyframe, DenseKeyframe, DenseRGBDKe
 from pyslam_amd.pipelines.sparse import SparseVOPipeline, SparseStereoPipeline, SparseRGBDPipeline  # noqa: F401
 from pyslam_amd.pipelines.mono import track_frame, relocalise_frame, SparseMonoPipeline, SparseMonoKeyframe  # noqa: F401
 from pyslam_amd.pipelines.loop import loop_candidates, verify_loop, detect_loop  # noqa: F401
+from pyslam_amd.pipelines.posegraph import Sim3PoseGraph, correct_loop  # noqa: F401

@@ -163,6 +163,19 @@ SIGNATURES = {
     'ps_sim3_score': (C.c_int, [c_f64p, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p, C.c_int32, c_f64p, C.c_double, c_u8p, c_i32p]),
     'ps_sim3_ransac': (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p, C.c_int32, c_i32p, C.c_int32, c_f64p, C.c_double, C.c_int32, C.c_int32,
                                  c_f64p, c_f64p, c_u8p, c_i32p, c_f64p]),
+    'ps_sim3pg_create': (C.c_int, [C.c_int32, c_f64p, c_u8p, C.c_int32, c_i32p, c_i32p, c_f64p, c_f64p, C.c_int32, C.c_double, C.c_void_p,
+                                   C.POINTER(H)]),
+    'ps_sim3pg_destroy': (C.c_int, [H]),
+    'ps_sim3pg_set_vertices': (C.c_int, [H, c_f64p]),
+    'ps_sim3pg_get_vertices': (C.c_int, [H, c_f64p]),
+    'ps_sim3pg_eval_cost': (C.c_int, [H, c_f64p]),
+    'ps_sim3pg_linearize': (C.c_int, [H, C.c_double, c_f64p, c_f64p, c_f64p]),
+    'ps_sim3pg_iteration': (C.c_int, [H, C.c_double, c_f64p, c_f64p, c_f64p]),
+    'ps_sim3pg_solve': (C.c_int, [H, C.POINTER(SolveOptions), c_f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_double)]),
+    'ps_sim3pg_debug_edges': (C.c_int, [H, c_f64p]),
+    'ps_sim3pg_debug_explog': (C.c_int, [C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p]),
+    'ps_sim3pg_profile': (C.c_int, [H, C.c_int32, c_f64p]),
     'ps_photometric_create': (C.c_int, [C.POINTER(PhotoDesc), C.c_void_p, C.POINTER(H)]),
     'ps_photometric_destroy': (C.c_int, [H]),
     'ps_photometric_set_pose': (C.c_int, [H, c_f64p]),

@@ -28,6 +28,7 @@
 #include "ps_k_twoview.h"
 #include "ps_k_pnp.h"
 #include "ps_k_sim3.h"
+#include "ps_k_sim3pg.h"
 #include "ps_photo.h"
 #include "ps_k_dense.h"
 #include "ps_k_feat.h"
@@ -717,6 +718,8 @@ extern "C" {
 #include "ps_abi_twoview.h"
 #include "ps_abi_pnp.h"
 #include "ps_abi_sim3.h"
+#include "ps_host_sim3pg.h"
+#include "ps_abi_sim3pg.h"
 #include "ps_abi_dense.h"
 #include "ps_abi_feat.h"
 

@@ -10,7 +10,9 @@ map or another keyframe (similarity: its host restatement).
 mono: matching by projection composed into ``track_frame``, matching without a prior composed into ``relocalise_frame``, and the
 monocular pipeline ``SparseMonoPipeline``.
 loop: the matcher's keyframe database composed with matching without a prior and the Sim(3) RANSAC into ``detect_loop`` (place
-recognition and its geometric verification; nothing corrects the map).
+recognition and its geometric verification).
+posegraph: the Sim(3) pose graph that consumes a verified loop constraint and corrects the map -- ``Sim3PoseGraph``, ``correct_loop``
+(simgraph: its host restatement).
 The stereo dense pipeline (cv2.StereoBM) is not in scope (out of scope)."""
 from .ransac import FrameToFrameRANSAC, compute_transform_fast  # noqa: F401
 from .twoview import EssentialRANSAC, bootstrap  # noqa: F401
@@ -22,3 +24,4 @@ from .sparse import SparseVOPipeline, SparseStereoPipeline, SparseRGBDPipeline  
 from .matcher import Matcher, Matcher_parameters  # noqa: F401
 from .mono import track_frame, relocalise_frame, SparseMonoPipeline, SparseMonoKeyframe  # noqa: F401
 from .loop import loop_candidates, verify_loop, detect_loop  # noqa: F401
+from .posegraph import Sim3PoseGraph, correct_loop  # noqa: F401

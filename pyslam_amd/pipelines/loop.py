@@ -5,7 +5,7 @@ The reference has no counterpart.  Everything is a composition of pieces that ru
 matcher's keyframe database (``Matcher.dbAdd`` / ``dbQuery``, DESIGN.md section 7 step 10: per stored keyframe the number of its
 descriptors that pass step 9's test against the frame, all keyframes in one launch), matching without a prior (``setMap`` /
 ``matchMapGlobal``, step 9) and ``Sim3RANSAC``.  There is no CPU path.  Nothing here corrects a map: a hit is the constraint
-``p_query = scale R p_entry + t`` between two camera frames that a Sim(3) pose graph would consume.
+``p_query = scale R p_entry + t`` between two camera frames that the Sim(3) pose graph (pipelines/posegraph.py) consumes.
 
 An *entry* is what a caller keeps of a keyframe, as a mapping or an object with ``desc`` (n, 32) uint8, ``points_c`` (n, 3) -- the
 features' landmarks in the keyframe's camera frame, non-finite rows for features without one -- ``uv`` (n, 2) and optionally ``ids``

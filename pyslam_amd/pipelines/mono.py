@@ -25,11 +25,17 @@ after which landmarks behind one of their cameras are dropped.
 
 The map lives on the host as arrays -- ``points_w`` (L, 3), ``descriptors`` (L, 32), ``alive`` (L,) and the observation table
 ``obs_kf`` / ``obs_lm`` / ``obs_uv`` -- and is uploaded to the matcher when the landmarks tracked against change.  Its scale is
-that of the initialisation; nothing corrects its drift (no loop closure, no scale prior: DESIGN.md section 7, limits).
+that of the initialisation; its drift is corrected only by ``loop_correction`` below (no scale prior: DESIGN.md section 7, limits).
 
 Loop detection (``loop_detection``, off by default): every keyframe's descriptors join the matcher's keyframe database, and after a
 new keyframe k and its bundle adjustment ``loop.detect_loop`` runs over the entries ``[0, k - loop_gap)``.  A hit is recorded in
-``loop_closures``; it corrects nothing, and poses and map are those of the same run with the switch off.
+``loop_closures``; on its own it corrects nothing, and poses and map are those of the same run with the switch off.
+
+Loop correction (``loop_correction``, off by default; needs ``loop_detection``): a recorded closure runs ``posegraph.correct_loop`` over
+all keyframes -- a Sim(3) pose graph of the odometry edges, the covisibility edges between keyframes that share at least
+``loop_min_shared`` landmarks and the closure, solved on the device -- and keyframe poses, landmarks (each with its first observing
+keyframe) and the poses of the frames in between (each with its preceding keyframe) move; ``loop_corrections`` records the run.
+Without a closure the switch changes nothing.
 
 Tracking loss (``relocalise``): a frame on which ``register_frame`` raises ValueError is relocalised against all live landmarks.
 Where that fails too the frame's pose is ``None`` and the pipeline is ``lost``: every further frame is relocalised until one
@@ -237,6 +243,14 @@ class SparseMonoPipeline:
         """One dict per detected loop: keyframe, entry, scale, T_21 (p_keyframe = scale R p_entry + t), pairs, connected"""
         self.loop_queries = []
         """One dict per query: keyframe, scores, candidates, verified ((entry, counts) per verification)"""
+        self.loop_correction = False
+        """Correct poses and map with a Sim(3) pose graph over all keyframes whenever a loop closure is recorded"""
+        self.loop_min_shared = 15
+        """Number of shared landmarks from which two keyframes are joined by a covisibility edge of that graph"""
+        self.loop_corrections = []
+        """One dict per correction: keyframe, entry, edges, iterations, cost_history, scales (the vertices' scales afterwards)"""
+        self.keyframe_frames = []
+        """Index into ``T_c_w`` of every keyframe's frame"""
 
     def set_mode(self, mode):
         """Set the localization mode to ['map'|'track']"""
@@ -272,6 +286,7 @@ class SparseMonoPipeline:
         """Track one uint8 image; its pose (SE3, or None before the map exists) is appended to ``T_c_w`` and returned."""
         if not self.keyframes:
             self.keyframes.append(SparseMonoKeyframe(image, self.first_pose))
+            self.keyframe_frames.append(len(self.T_c_w))
             self.T_c_w.append(self.first_pose)
             return self.first_pose
         if len(self.keyframes) == 1:
@@ -306,6 +321,7 @@ class SparseMonoPipeline:
         self._add_observations(0, lm, m[ok, 0:2])
         self._add_observations(1, lm, m[ok, 4:6])
         self.keyframes.append(kf)
+        self.keyframe_frames.append(len(self.T_c_w))
         self.landmark_counts.append(int(self.alive.sum()))
         if self.loop_detection:
             self._db_sync()
@@ -356,6 +372,7 @@ class SparseMonoPipeline:
         kf.landmark[feature] = lm
         self._add_observations(k, lm, obs)
         self.keyframes.append(kf)
+        self.keyframe_frames.append(len(self.T_c_w))
         self._new_landmarks(prev, kf, k)
         if self.local_ba and k + 1 >= 3:
             self._bundle_adjust()
@@ -408,6 +425,62 @@ class SparseMonoPipeline:
             e, scale, T_21, pairs = hit
             self.loop_closures.append(dict(keyframe=k, entry=e, scale=scale, T_21=T_21, pairs=pairs,
                                            connected=query['verified'][-1][1]['connected']))
+            if self.loop_correction:
+                self.correct_loop_closure(self.loop_closures[-1])
+
+    # ---- loop correction ----
+    def covisibility_edges(self):
+        """Keyframe pairs (i < j) that share at least ``loop_min_shared`` landmarks, ascending."""
+        K = len(self.keyframes)
+        order = np.lexsort((self.obs_kf, self.obs_lm))
+        lm, kf = self.obs_lm[order], self.obs_kf[order]
+        keys = []
+        for d in range(1, K):
+            same = lm[d:] == lm[:-d]
+            if not same.any():
+                break
+            a, b = kf[:-d][same], kf[d:][same]
+            keys.append(a[a != b] * K + b[a != b])
+        if not keys:
+            return []
+        key, count = np.unique(np.concatenate(keys), return_counts=True)
+        key = key[count >= int(self.loop_min_shared)]
+        return [(int(k // K), int(k % K)) for k in key]
+
+    def landmark_owners(self):
+        """The first observing keyframe of every landmark (0 for one without an observation)."""
+        owner = np.full(self.points_w.shape[0], len(self.keyframes), dtype=np.int64)
+        np.minimum.at(owner, self.obs_lm, self.obs_kf)
+        owner[owner == len(self.keyframes)] = 0
+        return owner
+
+    def correct_loop_closure(self, closure):
+        """The correction step for one closure dict (keyframe, entry, scale, T_21): ``posegraph.correct_loop`` over all keyframes,
+        then keyframe poses, landmarks and the frames in between moved; the run is appended to ``loop_corrections``."""
+        from pyslam_amd.liegroups import Sim3
+        from pyslam_amd.pipelines import posegraph
+        old = [Sim3.from_se3(kf.T_c_w) for kf in self.keyframes]
+        extra = self.covisibility_edges()
+        poses, scales, points = posegraph.correct_loop(
+            [kf.T_c_w for kf in self.keyframes], [(closure['entry'], closure['keyframe'], closure['scale'], closure['T_21'])],
+            extra_edges=extra, held=(0,), landmark_owner=self.landmark_owners(), points_w=self.points_w)
+        graph = posegraph.correct_loop.last_graph
+        new = graph.vertices
+        frames = np.asarray(self.keyframe_frames)
+        for f, T in enumerate(self.T_c_w):
+            k = int(np.searchsorted(frames, f, side='right')) - 1
+            if T is None or k < 0:
+                continue
+            if frames[k] == f:
+                self.T_c_w[f] = poses[k]
+            else:                                              # with its preceding keyframe: the relative similarity is kept
+                self.T_c_w[f] = Sim3.from_se3(T).dot(old[k].inv()).dot(new[k]).to_se3()
+        for kf, T in zip(self.keyframes, poses):
+            kf.T_c_w = T
+        self.points_w = points
+        self.loop_corrections.append(dict(keyframe=closure['keyframe'], entry=closure['entry'], edges=len(graph.edges),
+                                          covisibility=len(extra), iterations=graph.iterations,
+                                          cost_history=list(graph.cost_history), scales=scales))
 
     def _new_landmarks(self, prev, kf, k):
         """Flow matches between the previous keyframe and the new one whose features are bound to no landmark: those that agree

@@ -700,3 +700,76 @@ def sim3_scene(num_pts=192, seed=11, scale=2.5, outlier_fraction=0.3, point_nois
     T_21 = T.copy()
     T_21[:3, 3] = scale * T[:3, 3]
     return pts_1, pts_2, obs_1, obs_2, float(scale), T_21, outlier
+
+
+# ---------------------------------------------------------------------------
+# Sim(3) pose graphs (pipelines/posegraph.py, pipelines/simgraph.py)
+# ---------------------------------------------------------------------------
+def sim3_graph(num_vertices=12, num_chords=2, seed=0, perturbation=0.05):
+    """A consistent ring graph of similarities: vertex k is a true similarity on a circle of radius 3 with a rotation about a
+    tilted axis and the scale exp(0.4 sin(2 pi k / N)); one edge k -> k + 1 (mod N) and ``num_chords`` chords, from every 5th vertex
+    to the vertex a third of the ring ahead; every edge is exact (S_j S_i^-1 of the truth).  The start is exp(xi) S_true with
+    xi ~ N(0, perturbation^2) per component, except the held vertex 0.
+    -> (truth: list of Sim3, start: list of Sim3, held (N,) bool, edges: list of (i, j, S_ji, None))."""
+    from pyslam_amd.liegroups import Sim3
+    N = int(num_vertices)
+    if N < 3:
+        raise ValueError("sim3_graph: a ring needs at least 3 vertices")
+    rng = np.random.default_rng([seed, 7])
+    axis = np.array([0.2, 1.0, -0.3]) / np.linalg.norm([0.2, 1.0, -0.3])
+    truth = []
+    for k in range(N):
+        a = 2. * np.pi * k / N
+        R = SO3.exp(a * axis + 0.1 * rng.standard_normal(3))
+        t = np.array([3. * np.cos(a), 0.5 * np.sin(2. * a), 3. * np.sin(a)]) + 0.2 * rng.standard_normal(3)
+        truth.append(Sim3(R, t, np.exp(0.4 * np.sin(a))))
+    pairs = [(k, (k + 1) % N) for k in range(N)]
+    pairs += [((5 * c) % N, (5 * c + N // 3) % N) for c in range(int(num_chords))]
+    edges = [(i, j, truth[j].dot(truth[i].inv()), None) for i, j in pairs if i != j]
+    held = np.arange(N) == 0
+    start = [truth[0]] + [Sim3.exp(perturbation * rng.standard_normal(7)).dot(S) for S in truth[1:]]
+    return truth, start, held, edges
+
+
+def sim3_drift_loop(num_keyframes=40, scale_drift=0.01, rot_noise=0.002, seed=0, points_per_keyframe=4):
+    """A monocular map that has drifted around a loop.  True poses: ``num_keyframes`` cameras on 97 % of a circle of radius 10,
+    looking along the direction of travel.  Estimates: the true relative motions chained from the true first pose, each step's
+    translation times (1 + scale_drift)^k -- the local scale of the map grows by ``scale_drift`` per keyframe -- and each step's
+    rotation perturbed by ``rot_noise`` rad per axis.  One exact closure between the last keyframe and the first, in
+    ``detect_loop``'s convention (entry 0, keyframe K - 1, scale, T_21: p_last = scale R p_first + t, each in its own keyframe's
+    local map scale).  Landmarks are owned by keyframes: ``points_per_keyframe`` points in front of each, placed in the estimated map
+    at their owner's local scale.
+    -> dict: poses_true, poses_est (K, 4, 4 world-to-camera), closure, owner (L,), points_true, points_est (L, 3), scales (K,)."""
+    K = int(num_keyframes)
+    if K < 3:
+        raise ValueError("sim3_drift_loop: at least 3 keyframes")
+    rng = np.random.default_rng([seed, 8])
+    true = np.zeros((K, 4, 4))
+    for k in range(K):
+        a = 0.97 * 2. * np.pi * k / K
+        R_wc = SO3.roty(-a).as_matrix()                       # camera axes in the world: z along the tangent of the circle
+        c = np.array([10. * np.cos(a), 0., 10. * np.sin(a)])
+        R_wc = R_wc @ SO3.roty(0.5 * np.pi).as_matrix().T
+        true[k] = np.identity(4)
+        true[k, :3, :3] = R_wc.T
+        true[k, :3, 3] = -R_wc.T @ c
+    scales = (1. + scale_drift) ** np.arange(K)
+    est = np.zeros_like(true)
+    est[0] = true[0]
+    for k in range(K - 1):
+        rel = true[k + 1] @ np.linalg.inv(true[k])
+        rel[:3, :3] = SO3.exp(rot_noise * rng.standard_normal(3)).as_matrix() @ rel[:3, :3]
+        rel[:3, 3] *= scales[k + 1]
+        est[k + 1] = rel @ est[k]
+    rel = true[K - 1] @ np.linalg.inv(true[0])
+    T_21 = rel.copy()
+    T_21[:3, 3] *= scales[K - 1]
+    m = int(points_per_keyframe)
+    owner = np.repeat(np.arange(K), m)
+    p_c = np.stack([rng.uniform(-2., 2., K * m), rng.uniform(-1., 1., K * m), rng.uniform(3., 8., K * m)], axis=1)
+    inv_true, inv_est = np.linalg.inv(true), np.linalg.inv(est)
+    points_true = np.einsum('nij,nj->ni', inv_true[owner, :3, :3], p_c) + inv_true[owner, :3, 3]
+    p_local = scales[owner][:, None] * p_c
+    points_est = np.einsum('nij,nj->ni', inv_est[owner, :3, :3], p_local) + inv_est[owner, :3, 3]
+    return dict(poses_true=true, poses_est=est, closure=(0, K - 1, float(scales[K - 1]), T_21), owner=owner, points_true=points_true,
+                points_est=points_est, scales=scales)
