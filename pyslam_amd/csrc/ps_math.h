@@ -49,15 +49,18 @@ PS_DEV double ps_loss_rho(int id, double k, double x) {
     }
 }
 
+// (pinned like ps_loss_rho: the weight scales every entry of r~ and J~ in every observation and factor kernel it is inlined into; the
+//  one sum of a product in each smooth loss is an explicit fused multiply-add, so no copy can be fused differently from another)
 PS_DEV double ps_loss_weight(int id, double k, double x) {
+#pragma clang fp contract(off)
     const double a = fabs(x);
     switch (id) {
     case PS_LOSS_L2: return 1.0;
     case PS_LOSS_L1: return (a <= PS_SMALL_ANGLE) ? __builtin_nan("") : 1.0 / a;  // losses.py:30-33
-    case PS_LOSS_CAUCHY: { const double q = x / k; return 1.0 / (1.0 + q * q); }
+    case PS_LOSS_CAUCHY: { const double q = x / k; return 1.0 / __builtin_fma(q, q, 1.0); }
     case PS_LOSS_HUBER: return (a <= k) ? 1.0 : k / a;
-    case PS_LOSS_TUKEY: { const double q = x / k; return (a <= k) ? 1.0 - q * q : 0.0; }
-    default: return (k + 1.0) / (k + x * x);
+    case PS_LOSS_TUKEY: { const double q = x / k; return (a <= k) ? __builtin_fma(-q, q, 1.0) : 0.0; }
+    default: return (k + 1.0) / __builtin_fma(x, x, k);
     }
 }
 
@@ -365,29 +368,37 @@ PS_DEV void reproj_eval_s(const Se3& T, const double* __restrict__ pw, const dou
     const double j00 = g.fu * iz, j02 = -g.fu * pc[0] * iz2;
     const double j11 = g.fv * iz, j12 = -g.fv * pc[1] * iz2;
     const double j22 = mono ? 0.0 : (rgbd ? 1.0 : -g.fu * g.b * iz2);
+    // The sums of two and three products below are explicit fused multiply-adds too: this function is inlined into every
+    // observation kernel, and left to the compiler its copies were not fused alike once a stiffness is not diagonal or a wave
+    // mixes cameras (packed_prefetch / pose_prefetch on against off: tests/test_gpu_offbox.py).  One product of a sum is
+    // rounded, the others are fused onto it.  With one camera and a diagonal stiffness all but one product of SJ's sums are
+    // zero and J~l's last product is the fused one either way: the bits of such scenes are what they were.
     double SJ[9];                       // diag(s) * S * Jc
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        SJ[3 * i] = s[i] * (Sv[3 * i] * j00);
-        SJ[3 * i + 1] = s[i] * (Sv[3 * i + 1] * j11);
-        SJ[3 * i + 2] = s[i] * (Sv[3 * i] * j02 + Sv[3 * i + 1] * j12 + Sv[3 * i + 2] * j22);
-    }
-    if (WITH_JP) {
+    {
+#pragma clang fp contract(off)
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            const double a = SJ[3 * i], b = SJ[3 * i + 1], c = SJ[3 * i + 2];
-            o.Jp[6 * i] = a; o.Jp[6 * i + 1] = b; o.Jp[6 * i + 2] = c;
-            o.Jp[6 * i + 3] = -b * pc[2] + c * pc[1];      // SJ * (-pc)^
-            o.Jp[6 * i + 4] = a * pc[2] - c * pc[0];
-            o.Jp[6 * i + 5] = -a * pc[1] + b * pc[0];
+            SJ[3 * i] = s[i] * (Sv[3 * i] * j00);
+            SJ[3 * i + 1] = s[i] * (Sv[3 * i + 1] * j11);
+            SJ[3 * i + 2] = s[i] * __builtin_fma(Sv[3 * i + 2], j22, __builtin_fma(Sv[3 * i], j02, Sv[3 * i + 1] * j12));
         }
-    }
-    if (WITH_JL) {
+        if (WITH_JP) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+            for (int i = 0; i < 3; ++i) {
+                const double a = SJ[3 * i], b = SJ[3 * i + 1], c = SJ[3 * i + 2];
+                o.Jp[6 * i] = a; o.Jp[6 * i + 1] = b; o.Jp[6 * i + 2] = c;
+                o.Jp[6 * i + 3] = __builtin_fma(c, pc[1], -(b * pc[2]));    // SJ * (-pc)^
+                o.Jp[6 * i + 4] = __builtin_fma(a, pc[2], -(c * pc[0]));
+                o.Jp[6 * i + 5] = __builtin_fma(b, pc[0], -(a * pc[1]));
+            }
+        }
+        if (WITH_JL) {
 #pragma unroll
-            for (int j = 0; j < 3; ++j)
-                o.Jl[3 * i + j] = SJ[3 * i] * T.R[j] + SJ[3 * i + 1] * T.R[3 + j] + SJ[3 * i + 2] * T.R[6 + j];
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    o.Jl[3 * i + j] = __builtin_fma(SJ[3 * i + 2], T.R[6 + j], __builtin_fma(SJ[3 * i], T.R[j], SJ[3 * i + 1] * T.R[3 + j]));
+        }
     }
 }
 

@@ -47,3 +47,10 @@ for name in SOLVE_CASES:
 os.makedirs(os.path.join(REPO, 'gpurun_out'), exist_ok=True)
 with open(os.path.join(REPO, 'gpurun_out', 'parity_margins.json'), 'w') as f:
     json.dump(out, f, indent=1)
+
+# the off-box scenes (tests/test_gpu_offbox.py): per scene and quantity the device's distance from the long-double reference, e64 and
+# the bound that follows from e64
+import offbox_scenes                                                                 # noqa: E402
+import test_gpu_offbox                                                               # noqa: E402
+for name in offbox_scenes.SCENES:
+    test_gpu_offbox.margins(name)
