@@ -401,9 +401,12 @@ int ps_covariance_cross_blocks(ps_problem* h, int64_t n, const int32_t* kind_a, 
         (x_n r3 - r1) p = -(x_n t3 - t1) and (y_n r3 - r2) p = -(y_n t3 - t2); a stereo (z = fu b / d) or RGB-D (z = d) observation
         also r3 p = z - t3; the 3 x 3 normal equations are solved by Cholesky;
      2. refine_iters Gauss-Newton steps on the landmark's own robust reprojection cost (the iteration's evaluator: camera
-        types, stiffness, IRLS weights), poses held; a step that does not lower the cost is not taken and ends the iteration;
+        types, stiffness, IRLS weights), poses held; a step that does not lower the cost is not taken and ends the iteration,
+        and so does a step whose 3 x 3 system cannot be solved (a pivot that is not positive, NaN -- the L1 weight of a
+        residual component at zero): the landmark keeps its last accepted point and its status;
      3. status 0 ok | 1 fewer than two observations and none bearing depth | 2 no depth and the largest angle between two
-        viewing rays below min_parallax_deg, or a 3 x 3 system that is not positive definite | 3 behind one of its cameras.
+        viewing rays below min_parallax_deg, or a linear start whose normal equations are not positive definite | 3 behind one
+        of its cameras.
    points_out (n, 3): the new point, or the old one where the status is not 0; status_out (n).  write_back != 0: points
    with status 0 replace the handle's (as ps_set_params would).  One launch, one synchronisation. */
 int ps_triangulate(ps_problem* h, int64_t n, const int32_t* vids /* (n) or NULL */, int refine_iters, double min_parallax_deg,

@@ -12,10 +12,12 @@
 //   2. `refine_iters` Gauss-Newton steps on the landmark's own robust reprojection cost, every pose held, through the solver's
 //      evaluator (reproj_eval_obs<false, true>: camera types, stiffness and IRLS weights are the solver's):
 //      H = sum J~l^T J~l, g = sum J~l^T r~, H dx = -g by Cholesky.  A step that does not lower the cost is not taken and ends
-//      that landmark's iteration.
+//      that landmark's iteration; so does a step whose system cannot be solved (a pivot that is not positive, NaN: under L1
+//      the IRLS weight of a residual component within PS_SMALL_ANGLE of zero is NaN, which is where a converging landmark
+//      ends up).  Either way the landmark keeps its last accepted point and its status.
 //   3. Status: 0 ok | 1 fewer than two observations, none bearing depth | 2 no depth and the largest angle between two
-//      viewing rays below the minimum parallax, or a 3 x 3 matrix that is not positive definite | 3 the result lies behind
-//      one of its cameras (z <= 0).  A landmark with a non-zero status keeps its old value.
+//      viewing rays below the minimum parallax, or normal equations of the linear start that are not positive definite |
+//      3 the result lies behind one of its cameras (z <= 0).  A landmark with a non-zero status keeps its old value.
 #pragma once
 
 enum { PS_TRI_OK = 0, PS_TRI_FEW_OBS = 1, PS_TRI_DEGENERATE = 2, PS_TRI_BEHIND = 3 };
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(256) void k_triangulate(
             double dx[3];
             const double mg[3] = {-gr[0], -gr[1], -gr[2]};
             if (tri_chol_solve(H, mg, dx)) { cand[0] = p[0] + dx[0]; cand[1] = p[1] + dx[1]; cand[2] = p[2] + dx[2]; }
-            else { status = PS_TRI_DEGENERATE; active = false; }
+            else active = false;                            // no step to try (pivot not positive, NaN): done, like a step not taken
         }
     }
     if (status == PS_TRI_OK && behind > 0.0) status = PS_TRI_BEHIND;

@@ -353,7 +353,9 @@ def triangulate_tables(lp, refine_iters=5, min_parallax_deg=1.0, stream=None, de
     ``lp``'s poses (constant ones included): a linear start, ``refine_iters`` Gauss-Newton steps on the landmark's own robust
     reprojection cost with the poses held, a status per landmark (pyslam_amd/triangulation.py is the same
     definition in numpy).  -> (points (L, 3): ``lp.points`` with the landmarks of status 0 replaced, status (L,) int32: 0 ok,
-    1 too few observations, 2 no parallax / not positive definite, 3 behind a camera, -1 a constant point, not touched).
+    1 too few observations, 2 no parallax / linear start not positive definite, 3 behind a camera, -1 a constant point, not
+    touched).  A refinement step whose 3 x 3 system cannot be solved (L1's NaN weight at a zero residual) ends the refinement
+    like a step that does not lower the cost: the landmark keeps its last accepted point and stays 0.
     ``device``: a DeviceProblem of the same tables kept from an earlier call (its parameters are reset to ``lp``'s)."""
     from pyslam_amd.device import DeviceProblem
     dev = device
@@ -598,9 +600,11 @@ class Problem:
         and the CURRENT poses (constant poses included) and write the new points into the problem's parameters: a linear
         start from all views, `refine_iters` Gauss-Newton steps on the landmark's own robust cost with every pose held
         (pyslam_amd.triangulate_tables).  -> dict key -> status: 0 ok, 1 fewer than two observations and none with depth,
-        2 largest angle between two viewing rays below `min_parallax_deg` and no depth, or a 3 x 3 system that is not
-        positive definite, 3 the result lies behind one of its cameras.  A landmark with a non-zero status keeps its
-        value.  Typed problems only (a block without a device kernel raises NotLowerable); a constant or unknown key raises
+        2 largest angle between two viewing rays below `min_parallax_deg` and no depth, or a linear start whose normal
+        equations are not positive definite, 3 the result lies behind one of its cameras.  A landmark with a non-zero
+        status keeps its value.  A refinement step that does not lower the cost, or whose 3 x 3 system cannot be solved
+        (not positive definite, NaN: the L1 weight at a zero residual), ends that landmark's refinement at its last accepted
+        point, status 0.  Typed problems only (a block without a device kernel raises NotLowerable); a constant or unknown key raises
         KeyError."""
         dev = self._get_device()
         if self._photometric_form() or not hasattr(dev, 'triangulate'):

@@ -9,10 +9,13 @@ Per variable landmark, from its observations and the poses of the tables (consta
    Cholesky.
 2. ``refine_iters`` Gauss-Newton steps on the landmark's own robust reprojection cost with every pose held: r = S (project
    (R p + t) - obs), IRLS-scaled as the solver scales it, H = sum J~^T J~, g = sum J~^T r~, H dx = -g by Cholesky.  A step that
-   does not lower the cost is not taken and ends that landmark's iteration.
+   does not lower the cost is not taken and ends that landmark's iteration.  So does a step whose 3 x 3 system cannot be
+   solved (a pivot that is not positive, NaN): under L1 the IRLS weight of a residual component within 1e-8 of zero is NaN
+   (the reference's losses.py), and that is where a landmark with an L1 observation converges to.  The landmark keeps its
+   last accepted point and its status.
 3. Status: 0 ok; 1 fewer than two observations and none bearing depth; 2 no depth and the largest angle between two viewing
-   rays below ``min_parallax_deg``, or a 3 x 3 system that is not positive definite; 3 the result lies behind one of its
-   cameras.  A landmark with a non-zero status keeps its old value.
+   rays below ``min_parallax_deg``, or a linear start whose normal equations are not positive definite; 3 the result lies
+   behind one of its cameras.  A landmark with a non-zero status keeps its old value.
 
 Order: a landmark's observations in the order of the observation table (the device's landmark sort is stable); observation
 q of a landmark goes to lane q mod 16, a lane adds its observations in order, and the 16 lane sums are added in the
@@ -199,8 +202,7 @@ def triangulate(lp, vids=None, refine_iters=5, min_parallax_deg=1.0):
         p, H, g = np.where(take[:, None], cand, p), np.where(take[:, None], Hn, H), np.where(take[:, None], gn, g)
         if it < refine_iters:
             dx, ok = _chol_solve(H, -g)
-            status[active & ~ok] = DEGENERATE
-            active &= ok
+            active &= ok                                      # no step to try: done, at the last accepted point (status kept)
             cand = np.where(active[:, None], p + dx, p)
     status[(status == OK) & (behind > 0.)] = BEHIND
     return np.where((status == OK)[:, None], p, old), status

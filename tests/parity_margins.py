@@ -54,3 +54,13 @@ import offbox_scenes                                                            
 import test_gpu_offbox                                                               # noqa: E402
 for name in offbox_scenes.SCENES:
     test_gpu_offbox.margins(name)
+
+# multi-view triangulation (tests/test_gpu_triang.py): per scene and stage the device's distance from the long-double restatement, e64,
+# the bound, the share of landmarks each condition leaves out and the status counts
+import triang_scenes                                                                 # noqa: E402
+import test_gpu_triang                                                               # noqa: E402
+for name in triang_scenes.SCENES:
+    test_gpu_triang.margins(name)
+test_gpu_triang.status('far100')
+for dev in test_gpu_triang._HANDLES.values():
+    dev.close()
