@@ -28,6 +28,9 @@ authoring container (with a decorator-only numba stand-in and this build's
 liegroups).  The liegroups arithmetic itself is third-party and absent, so its
 element-level parity is pinned independently (scipy) rather than by the
 reference.
+
+PRECISION: `unpack` casts to float and `wedge3` allocates fp64, so the pose-graph side computes in fp64 whatever dtype its
+tables have (long-double tables give a float128 array of fp64 values); tests/longdouble_posegraph.py is the long-double definition.
 """
 import numpy as np
 import scipy.sparse as sp

@@ -55,6 +55,13 @@ import test_gpu_offbox                                                          
 for name in offbox_scenes.SCENES:
     test_gpu_offbox.margins(name)
 
+# the pose-factor scenes (tests/test_gpu_posegraph.py): per scene, group and quantity the device's distance from the long-double
+# reference, e64 and the bound
+import posegraph_scenes                                                              # noqa: E402
+import test_gpu_posegraph                                                            # noqa: E402
+for case in posegraph_scenes.cases():
+    test_gpu_posegraph.margins(case)
+
 # multi-view triangulation (tests/test_gpu_triang.py): per scene and stage the device's distance from the long-double restatement, e64,
 # the bound, the share of landmarks each condition leaves out and the status counts
 import triang_scenes                                                                 # noqa: E402
