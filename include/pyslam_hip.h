@@ -776,7 +776,9 @@ int ps_sim3_ransac(const double* pts_1, const double* pts_2, const double* obs_1
    D = 3 / 6 solver is not involved.
    Element: 13 doubles [R row-major (9) | t (3) | s], s > 0, p -> s R p + t.  Tangent [rho | phi | sigma]; update S <- exp(dx) S.
    Edge (i, j, S_ji, W): r = W log(S_j S_i^-1 S_ji^-1) with a 7 x 7 stiffness W (edge_stiffness49 NULL: identity; an all-zero row
-   is an absent row), J_i = -W Ad(S_j S_i^-1), J_j = W, the robust loss per component as the pose factors of the core apply it.
+   is an absent row), J_i = -W Ad(S_j S_i^-1), J_j = W, the robust loss per component as the pose factors of the core apply it,
+   with one exception: L1's IRLS weight is 1 / max(|r_k|, 1e-8) here (the core's is NaN within 1e-8 of zero) -- the edges of a loop
+   correction start at zero residual, and an L1 solve converges to zero components; the cost stays |r_k|.
    held[v] != 0: vertex v contributes no unknowns (at least one must be held; an edge between two held vertices adds cost only).
    The system is DENSE, n = 7 free vertices <= 8192, solved by the blocked Cholesky chain with one refinement step; a larger
    graph, an index out of range, i == j, a non-finite input and a non-positive pivot are errors.

@@ -3,7 +3,8 @@
 // the core's D = 3 / 6 machinery is touched.  fp64 throughout, no atomics: every sum runs in a fixed order.
 //
 // Element: 13 doubles [R row-major (9) | t (3) | s], p -> s R p + t.  Tangent [rho | phi | sigma].  Edge (i, j, S_ji, W):
-// r = W log(S_j S_i^-1 S_ji^-1), J_i = -W Ad(S_j S_i^-1), J_j = W (first order), IRLS per component through ps_loss_weight.
+// r = W log(S_j S_i^-1 S_ji^-1), J_i = -W Ad(S_j S_i^-1), J_j = W (first order), IRLS per component through s3g_loss_weight
+// (ps_loss_weight with L1's weight capped at 1 / PS_SMALL_ANGLE).
 #pragma once
 
 #define PS_S3G_EDGES 64                // edges per workgroup of k_s3g_edges
@@ -153,6 +154,16 @@ PS_DEV double sim3_adj(const double* __restrict__ S, int m, int c) {
     return c == 6 ? 1.0 : 0.0;
 }
 
+// The IRLS weight of a residual component in this graph: ps_loss_weight, except that L1's 1 / |r| is capped at
+// 1 / PS_SMALL_ANGLE (ps_loss_weight says NaN there; its other users keep that).  Zero components are structural here: every
+// odometry and covisibility edge of a loop correction is measured from the current estimates, and zero is where an L1 solve
+// converges to -- the capped weight is the usual IRLS regularisation.  Above PS_SMALL_ANGLE the bits are ps_loss_weight's;
+// the cost stays |r|.
+PS_DEV double s3g_loss_weight(int id, double k, double x) {
+    if (id == PS_LOSS_L1) return 1.0 / fmax(fabs(x), PS_SMALL_ANGLE);
+    return ps_loss_weight(id, k, x);
+}
+
 // Two phases per workgroup of 64 edges, as k_factor_pass has them (one logarithm per edge, not 64 copies of it):
 //   1. one THREAD per edge: S_j S_i^-1, E = that times S_ji^-1, xi = log(E), r = W xi, the IRLS scales, the edge's cost;
 //   2. one WAVE per edge, lane (r, c) of 49: J~1 = -diag(s) W Ad(S_j S_i^-1), J~2 = diag(s) W in LDS, then the three 7 x 7 products
@@ -188,7 +199,7 @@ __global__ __launch_bounds__(256) void k_s3g_edges(
 #pragma unroll
                     for (int m = 0; m < D; ++m) { rk += Wm[k * D + m] * xi[m]; present = present || Wm[k * D + m] != 0.0; }
                 }
-                const double sk = present ? sqrt(ps_loss_weight(loss_id, loss_k, rk)) : 0.0;
+                const double sk = present ? sqrt(s3g_loss_weight(loss_id, loss_k, rk)) : 0.0;
                 if (present) cst += ps_loss_rho(loss_id, loss_k, rk);
                 sS[el][k] = sk;
                 sSr[el][k] = sk * rk;

@@ -268,7 +268,9 @@ def correct_loop(poses_cw, closures, extra_edges=(), held=(0,), landmark_owner=N
     """Correct a keyframe map for its detected loops.  ``poses_cw``: world-to-camera poses of the keyframes (SE3 or 4 x 4);
     ``closures``: (entry, keyframe, scale, T_21) in ``detect_loop``'s convention p_keyframe = scale R p_entry + t;
     ``extra_edges``: further keyframe pairs (covisibility), measured like the odometry edges from the current estimates;
-    ``landmark_owner`` / ``points_w``: one keyframe per point, and the points.  -> (poses_cw_new, scales, points_w_new); the graph
+    ``landmark_owner`` / ``points_w``: one keyframe per point, and the points.  ``loss``: None (L2) or a built-in loss, per residual
+    component; under ``L1Loss`` the IRLS weight is 1 / max(|r_k|, 1e-8) -- the odometry and covisibility edges start at zero residual,
+    where the plain 1 / |r_k| is undefined.  -> (poses_cw_new, scales, points_w_new); the graph
     that ran stays in ``correct_loop.last_graph``."""
     graph = loop_graph(poses_cw, closures, extra_edges, held, stiffness, loss)
     old = list(graph.vertices)

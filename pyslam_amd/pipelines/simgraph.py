@@ -45,9 +45,18 @@ def _free_index(num, held):
     return held, rid
 
 
+L1_WEIGHT_CAP = 1e-8     # PS_SMALL_ANGLE of the device
+
+
 def _rho_weight(loss, r):
+    """(rho, IRLS weight) per component.  L1's weight is 1 / max(|r_k|, 1e-8) in this graph (``L1Loss.weight`` is NaN within 1e-8 of
+    zero): the odometry and covisibility edges of a loop correction are measured from the current estimates, so their components
+    START at zero, and zero is where an L1 solve converges to; the capped weight is the usual IRLS regularisation.  The cost stays
+    |r_k| (csrc/ps_k_sim3pg.h: s3g_loss_weight)."""
     if loss is None:
         return 0.5 * r * r, np.ones(r.size)
+    if getattr(loss, 'LOSS_ID', None) == 1:
+        return np.abs(r), 1. / np.maximum(np.abs(r), L1_WEIGHT_CAP)
     return np.asarray(loss.loss(r), dtype=np.float64).reshape(r.size), np.asarray(loss.weight(r), dtype=np.float64).reshape(r.size)
 
 

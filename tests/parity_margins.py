@@ -71,3 +71,10 @@ for name in triang_scenes.SCENES:
 test_gpu_triang.status('far100')
 for dev in test_gpu_triang._HANDLES.values():
     dev.close()
+
+# the Sim(3) pose-graph scenes (tests/test_gpu_sim3graph_rows.py): per scene and quantity the device's distance from the long-double
+# definition, e64 and the bound
+import sim3graph_row_scenes                                                          # noqa: E402
+import test_gpu_sim3graph_rows                                                       # noqa: E402
+for name in sim3graph_row_scenes.ROW_SCENES:
+    test_gpu_sim3graph_rows.margins(name)
