@@ -545,6 +545,11 @@ int ps_debug_pose_items(ps_problem* h, int32_t* nitems, int32_t capacity_items, 
                               compiled out of the launches with lambda = 0.  Under 128 registers there: four waves per SIMD instead of
                               three.  0: k_pose_pass, one observation after the other.  Speed only, same bits.  Handled ahead of the
                               option table
+     "coarse_chol_band"   [1; 0 / 1] coarse levels of at most 90 unknowns: the factorisation of A_c = P^T S^ P leaves out the blocks that the
+                              pattern makes structurally zero (k_coarse_chol_band with the block half-bandwidth the coarse-level
+                              planner derived from the run tables -- ps_get_option "coarse_chol_bw"; ncb - 1, the dense matrix,
+                              where a loop closure spans the trajectory), on the solver stream and on the side stream.  0:
+                              k_coarse_chol on every launch.  Speed only, same bits.  Handled ahead of the option table
      "schur_pipeline"    [1; 0 / 1] the Schur pair kernel with two chunks per wave in flight (k_schur_pairs_db); 0: k_schur_pairs
      "lm_packed" [1; 0 / 1], "band_part" [1; 0 / 1], "band_part_chunk" [0 auto; 0 .. 4096 nodes], "sync_refactor" [1; 0 / 1],
      "hold_across_steps" [1; 0 / 1]: round-5 kernels and schedules against their predecessors (DESIGN.md sections 0 and 3)
@@ -581,7 +586,9 @@ int ps_set_option(ps_problem* h, const char* name, double value);
    take on this handle (0 before the coarse level is built, and where the one-launch folded CG does not apply);
    "cg_persist_recovered" / "cg_persist_recover_fallbacks": one-launch solves so far (ps_problem_info.cg_persist_solves) that recover
    x inside the launch / that leave it to k_coarse_recover behind the launch.
-   "packed_prefetch", "pose_prefetch": the options. */
+   "packed_prefetch", "pose_prefetch", "coarse_chol_band": the options.  "coarse_chol_bw": the block half-bandwidth of the coarse
+   matrix on this handle, 0 .. ncb - 1 (ncb - 1: no band; -1 before the coarse level is built and without one); "coarse_nodes": ncb,
+   the coarse nodes of this handle (0 before the coarse level is built and without one). */
 int ps_get_option(ps_problem* h, const char* name, double* value);
 
 /* hipEvent stage timers on the handle's stream (the reference has no tracing). */
@@ -621,6 +628,18 @@ int ps_sparse_normal_direct(int32_t m, int32_t n, const int32_t* j_row_ptr, cons
  * Stands in for the coarse-level part of scipy.sparse.linalg.spsolve (reference pyslam/problem.py:186); test and measurement entry. */
 int ps_debug_band_inverse(const double* a, int32_t ncb, int32_t dof, int32_t bw, int32_t chunk_nodes, float* ainv_out,
                           double* elapsed_us);
+/* The LDS-resident coarse factorisation kernels on their own (csrc/ps_k_coarse.h): one launch of k_coarse_chol (variant 0) or of
+ * k_coarse_chol_band (variant 1: as the solver launches it; 64 .. 1024 in steps of 64: with that many threads) on a host matrix
+ * `a` (dense, row-major, (ncb dof)^2 doubles, ncb dof <= 90, dof 3 or 6), on a stream of its own.  bw: block half-bandwidth handed
+ * to the band kernel, 0 .. ncb - 1 (outside it `a` must hold +0.0; variant 0 ignores it).  Li, LiT: L^-1 and its transpose, whole,
+ * zeros above / below the diagonal (an entry the kernel did not write comes back as NaN).  status: the 8 status words (word 1: non-
+ * positive or NaN pivots).  elapsed_us (or NULL): GPU time of a second launch, between events.  Test and measurement entry; no
+ * solver path calls it.  ps_debug_coarse_chol_clocks (measurement build; the product build refuses): six stamps of the kernel's
+ * thread 0 in microseconds from kernel entry -- entry, band loaded, factor loop done, diagonal inverses done, doubling levels done,
+ * outputs stored. */
+int ps_debug_coarse_chol(const double* a, int32_t ncb, int32_t dof, int32_t bw, int32_t variant, double* Li, double* LiT,
+                         int32_t* status, double* elapsed_us);
+int ps_debug_coarse_chol_clocks(const double* a, int32_t ncb, int32_t dof, int32_t bw, int32_t variant, double* clocks);
 /* The blocked dense factorisation chain on its own (csrc/ps_host_bchol.h: bchol_chain, the one launch sequence behind the coarse
  * level beyond 90 unknowns, the lagged inverse's direct seed, ps_covariance_marginals and ps_sparse_normal_direct; kernels
  * k_bchol_panel / k_bchol_update / k_btri_inverse / k_btri_merge / k_btri_clear and k_xcg_ainv).  Test and measurement entries;

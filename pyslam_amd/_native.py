@@ -217,6 +217,8 @@ SIGNATURES = {
     'ps_sparse_normal_direct': (C.c_int, [C.c_int32, C.c_int32, c_i32p, c_i32p, c_f64p, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p,
                                           C.c_int32, c_f64p, c_f64p]),
     'ps_debug_band_inverse': (C.c_int, [c_f64p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), c_f64p]),
+    'ps_debug_coarse_chol': (C.c_int, [c_f64p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f64p, c_f64p, c_i32p, c_f64p]),
+    'ps_debug_coarse_chol_clocks': (C.c_int, [c_f64p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f64p]),
     'ps_debug_dense_factor': (C.c_int, [c_f64p, C.c_int32, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p, C.POINTER(C.c_float), c_i32p, c_f64p]),
     'ps_debug_bchol_slab': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, c_i32p, c_i32p]),
     'ps_debug_ldi_gemm': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.c_int32,

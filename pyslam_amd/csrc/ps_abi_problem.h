@@ -41,7 +41,7 @@ int ps_warm_up(void) {
         PS_TOUCH(k_schur_combine); PS_TOUCH(k_backsub<false>); PS_TOUCH(k_cost_reproj<false>); PS_TOUCH(k_cost_packed<false, true>); PS_TOUCH(k_reduce3); PS_TOUCH(k_reduce_partials);
         PS_TOUCH(k_copy2); PS_TOUCH(k_zero4); PS_TOUCH(k_lag_status_check);
         PS_TOUCH(k_block_jacobi_factor<6>); PS_TOUCH(k_scale_blocks<6>); PS_TOUCH(k_scale_blocks_p<6>); PS_TOUCH(k_rows_setup<6, PS_RS_REGS>); PS_TOUCH(k_rows_setup<6, PS_RS_EXACT>);
-        PS_TOUCH(k_coarse_rowsums<6>); PS_TOUCH(k_coarse_matrix<6>); PS_TOUCH(k_coarse_chol<6, true>); PS_TOUCH(k_coarse_border<6>);
+        PS_TOUCH(k_coarse_rowsums<6>); PS_TOUCH(k_coarse_matrix<6>); PS_TOUCH(k_coarse_chol<6, true>); PS_TOUCH(k_coarse_chol_band<6>); PS_TOUCH(k_coarse_border<6>);
         PS_TOUCH(k_coarse_mreduce<6>); PS_TOUCH(k_coarse_xbuild<6>); PS_TOUCH(k_coarse_recover<6>); PS_TOUCH(k_cg_fused_lds<6, 8>);
         PS_TOUCH(k_cg_fused<6, 8>); PS_TOUCH(k_cg_unscale<6>); PS_TOUCH(k_update_poses<6>); PS_TOUCH(k_update_points);
         PS_TOUCH(k_xcoarse_rowsums<6>); PS_TOUCH(k_xcoarse_matrix<6>); PS_TOUCH(k_band_chol<6>); PS_TOUCH(k_band_inverse); PS_TOUCH(k_band_inverse_rl<false>);
@@ -57,7 +57,7 @@ int ps_warm_up(void) {
         PS_TOUCH(k_ldi_scaled_dense<6>); PS_TOUCH(k_ldi_sym_unscale<6>); PS_TOUCH(k_ldi_scaled_dense<3>); PS_TOUCH(k_ldi_sym_unscale<3>);
         PS_TOUCH(k_shard_pack<6>); PS_TOUCH(k_shard_unpack<6>); PS_TOUCH(k_publish); PS_TOUCH(k_cov_rhs); PS_TOUCH(k_triangulate<false>);
         PS_TOUCH(k_scale_blocks<3>); PS_TOUCH(k_rows_setup<3, PS_RS_REGS>); PS_TOUCH(k_rows_setup<3, PS_RS_EXACT>); PS_TOUCH(k_coarse_rowsums<3>); PS_TOUCH(k_coarse_matrix<3>);
-        PS_TOUCH(k_coarse_chol<3, true>); PS_TOUCH(k_coarse_border<3>); PS_TOUCH(k_coarse_mreduce<3>); PS_TOUCH(k_coarse_xbuild<3>);
+        PS_TOUCH(k_coarse_chol<3, true>); PS_TOUCH(k_coarse_chol_band<3>); PS_TOUCH(k_coarse_border<3>); PS_TOUCH(k_coarse_mreduce<3>); PS_TOUCH(k_coarse_xbuild<3>);
         PS_TOUCH(k_coarse_recover<3>); PS_TOUCH(k_cg_fused_lds<3, 8>); PS_TOUCH(k_cg_unscale<3>);
 #undef PS_TOUCH
     });

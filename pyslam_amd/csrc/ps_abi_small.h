@@ -504,6 +504,81 @@ int ps_debug_band_inverse(const double* a, int32_t ncb, int32_t dof, int32_t bw,
     return 0;
 }
 
+// ---- the LDS-resident coarse factorisation kernels on their own (csrc/ps_k_coarse.h; tests/test_gpu_coarse_chol_band.py) ------
+// One launch of k_coarse_chol<dof, true> (variant 0) or k_coarse_chol_band<dof> (variant 1: the production launch; 64 .. 1024, a
+// multiple of 64: that many threads) on a host matrix (nc x nc row-major, nc = ncb dof <= 90), on a stream of its own.  Li and LiT
+// are pre-filled with NaN bit patterns, so an entry a kernel failed to write would show.  status: the ST_NWORDS status words.
+// clocks (may be NULL; measurement build only): six wall-clock stamps of thread 0 -- entry | loaded | factor loop done |
+// diagonal inverses done | doubling done | stored -- in microseconds from the first.
+static int debug_coarse_chol(const double* a, int32_t ncb, int32_t dof, int32_t bw, int32_t variant, double* Li, double* LiT,
+                             int32_t* status, double* elapsed_us, double* clocks) {
+    if (!a || !Li || !LiT || !status || ncb <= 0 || (dof != 3 && dof != 6)) return fail("ps_debug_coarse_chol: bad argument");
+    const int nc = ncb * dof;
+    if (nc > 90) return fail("ps_debug_coarse_chol: the LDS-resident kernels take ncb dof <= 90");
+    if (variant != 0 && variant != 1 && (variant < 64 || variant > 1024 || variant % 64)) return fail("ps_debug_coarse_chol: bad variant");
+    if (variant != 0 && (bw < 0 || bw > ncb - 1)) return fail("ps_debug_coarse_chol: bw must be 0 .. ncb - 1");
+    if (clocks && !PS_MEASURE_BUILD) return fail("ps_debug_coarse_chol_clocks: phase clocks exist in the measurement build only");
+    if (need_device()) return -1;
+    const size_t nn = (size_t)nc * nc;
+    DevBuf bA, bLi, bLiT, bst, bck;
+    if (bA.get(nn * 8) || bLi.get(nn * 8) || bLiT.get(nn * 8) || bst.get(ST_NWORDS * 4) || bck.get(8 * 8)) return -1;
+    HIP_OK(hipMemcpy(bA.p, a, nn * 8, hipMemcpyHostToDevice));
+    hipStream_t st = nullptr;
+    HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    struct St { hipStream_t s; ~St() { hipStreamDestroy(s); } } stg{st};
+    hipEvent_t e0, e1;
+    HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+    struct Ev { hipEvent_t a, b; ~Ev() { hipEventDestroy(a); hipEventDestroy(b); } } evs{e0, e1};
+    const size_t chol_lds = 2 * nn * sizeof(double);
+    const int threads = variant == 1 ? PS_CCB_THREADS : variant;
+    if (variant == 0 ? (dof == 6 ? ensure_dynamic_lds((const void*)k_coarse_chol<6, true>, chol_lds) : ensure_dynamic_lds((const void*)k_coarse_chol<3, true>, chol_lds))
+                     : (dof == 6 ? ensure_dynamic_lds((const void*)k_coarse_chol_band<6>, chol_lds) : ensure_dynamic_lds((const void*)k_coarse_chol_band<3>, chol_lds))) return -1;
+    for (int rep = 0; rep < (elapsed_us ? 2 : 1); ++rep) {    // (a timed call: the second run is the one timed, the first loads the kernel)
+        HIP_OK(hipMemsetAsync(bst.p, 0, ST_NWORDS * 4, st));
+        HIP_OK(hipMemsetAsync(bck.p, 0, 8 * 8, st));
+        HIP_OK(hipMemsetAsync(bLi.p, 0xff, nn * 8, st));
+        HIP_OK(hipMemsetAsync(bLiT.p, 0xff, nn * 8, st));
+        HIP_OK(hipEventRecord(e0, st));
+        if (variant == 0) {
+            double* ck = clocks ? bck.as<double>() : nullptr;       // (k_coarse_chol's measurement build stamps its scratch argument)
+            if (dof == 6) hipLaunchKernelGGL((k_coarse_chol<6, true>), dim3(1), dim3(1024), chol_lds, st, ncb, bA.as<double>(), bLi.as<double>(), bLiT.as<double>(), bst.as<int32_t>(), ck);
+            else hipLaunchKernelGGL((k_coarse_chol<3, true>), dim3(1), dim3(1024), chol_lds, st, ncb, bA.as<double>(), bLi.as<double>(), bLiT.as<double>(), bst.as<int32_t>(), ck);
+        } else {
+            long long* ck = clocks ? bck.as<long long>() : nullptr;
+            if (dof == 6) hipLaunchKernelGGL(k_coarse_chol_band<6>, dim3(1), dim3(threads), chol_lds, st, ncb, bw, (const double*)bA.as<double>(), bLi.as<double>(), bLiT.as<double>(), bst.as<int32_t>(), ck);
+            else hipLaunchKernelGGL(k_coarse_chol_band<3>, dim3(1), dim3(threads), chol_lds, st, ncb, bw, (const double*)bA.as<double>(), bLi.as<double>(), bLiT.as<double>(), bst.as<int32_t>(), ck);
+        }
+        HIP_OK(hipEventRecord(e1, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    if (elapsed_us) { float ms = 0.f; HIP_OK(hipEventElapsedTime(&ms, e0, e1)); *elapsed_us = 1e3 * ms; }
+    HIP_OK(hipMemcpy(status, bst.p, ST_NWORDS * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(Li, bLi.p, nn * 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(LiT, bLiT.p, nn * 8, hipMemcpyDeviceToHost));
+    if (clocks) {
+        long long c[6];
+        int khz = 100000;
+        HIP_OK(hipMemcpy(c, bck.p, sizeof c, hipMemcpyDeviceToHost));
+        HIP_OK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, 0));
+        if (!c[3]) c[3] = c[2];                               // (a single block row: no doubling level stamps it)
+        for (int k = 0; k < 6; ++k) clocks[k] = (double)(c[k] - c[0]) * 1e3 / khz;
+    }
+    return 0;
+}
+
+int ps_debug_coarse_chol(const double* a, int32_t ncb, int32_t dof, int32_t bw, int32_t variant, double* Li, double* LiT,
+                         int32_t* status, double* elapsed_us) {
+    return debug_coarse_chol(a, ncb, dof, bw, variant, Li, LiT, status, elapsed_us, nullptr);
+}
+
+int ps_debug_coarse_chol_clocks(const double* a, int32_t ncb, int32_t dof, int32_t bw, int32_t variant, double* clocks /* 6 */) {
+    if (!clocks || !a || ncb <= 0 || (dof != 3 && dof != 6) || ncb * dof > 90) return fail("ps_debug_coarse_chol_clocks: bad argument");
+    std::vector<double> li((size_t)ncb * dof * ncb * dof), lit(li.size());
+    int32_t stw[ST_NWORDS];
+    double us = 0.0;
+    return debug_coarse_chol(a, ncb, dof, bw, variant, li.data(), lit.data(), stw, &us, clocks);
+}
+
 // ---- the blocked dense factorisation chain on its own (csrc/ps_host_bchol.h; tests/test_gpu_bchol_kernels.py) ----------------
 // Every stage's output of bchol_chain on a host matrix, on a stream of its own.  flags bit 0: the folded CG's dense-output form
 // (zero fill + k_btri_clear), else the explicit PCG's; bits 8..15: extra columns of ainv_out's leading dimension (ld = n + that;

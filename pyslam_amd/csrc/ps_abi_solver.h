@@ -1033,6 +1033,9 @@ int ps_set_option(ps_problem* h, const char* name, double value) {
         h->prelin_valid = h->prelm_valid = h->ride_valid = false;
         return 0;
     }
+    // coarse_factor's LDS branch with the structural zeros of A_c left out (csrc/ps_core.hip: coarse_chol_band); 0: k_coarse_chol.
+    // A lagged factor in flight was made from the same A_c and has the same bits: nothing is dropped
+    if (!std::strcmp(name, "coarse_chol_band")) { h->coarse_chol_band = value != 0 ? 1 : 0; return 0; }
     // (the test hook arms the next solve and changes nothing that was computed ahead: the landmark pass and the linearisation a
     //  tail ran for this point stay valid, so that the forced breakdown is seen with them in place)
     if (std::strcmp(name, "cg_force_breakdown")) h->prelin_valid = h->prelm_valid = h->ride_valid = false;
@@ -1071,6 +1074,9 @@ int ps_get_option(ps_problem* h, const char* name, double* value) {
     else if (n == "cg_persist_recover_need") *value = h->coarse_built && h->cp_ok ? (double)h->cp_rec_lds : 0.0;
     else if (n == "cg_persist_recovered") *value = (double)h->cp_rec_inside;
     else if (n == "cg_persist_recover_fallbacks") *value = (double)h->cp_rec_behind;
+    else if (n == "coarse_chol_band") *value = (double)h->coarse_chol_band;
+    else if (n == "coarse_nodes") *value = h->coarse_built ? (double)h->ncb : 0.0;
+    else if (n == "coarse_chol_bw") *value = h->coarse_built && h->ncb > 0 ? (double)std::min(std::max(h->coarse_chol_bw, 0), h->ncb - 1) : -1.0;
     else if (n == "cg_force_breakdown") *value = (double)h->cg_force_breakdown;      // (0 again once a solve's set-up has taken it)
     else return fail("ps_get_option: no read-back for option: " + n);
     return 0;

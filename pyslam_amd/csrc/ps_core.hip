@@ -164,6 +164,7 @@ PersistLedger& ps_persist_ledger() { static PersistLedger* p = new PersistLedger
 #include "ps_host_bandpart.h"
 #include "ps_host_bchol.h"
 #include "ps_options.h"
+#include "ps_coarse_band.h"
 #include "ps_structure.h"
 
 // ---- the handle by role -------------------------------------------------------------------------------------------------
@@ -510,6 +511,12 @@ struct ps_problem : PsOptions, PsCostHistory, PsCarried {
     // larger chunk: k_pose_pass.  Every value is the same either way.
     int pose_prefetch = 1;
     int pose_chunk = 256;
+    // option "coarse_chol_band" (ps_set_option, ahead of the table): coarse_factor's LDS branch (nc <= 90) launches
+    // k_coarse_chol_band with the block half-bandwidth of A_c -- coarse_chol_bw: what build_coarse derived from the run tables
+    // (ps_coarse_band.h; the explicit form: from its segment lists), ncb - 1 where the pattern has no band.  0: k_coarse_chol.
+    // Every value is the same either way.
+    int coarse_chol_band = 1;
+    int coarse_chol_bw = 0;
     // lagged dense inverse of the reduced system as the CG preconditioner (ps_k_ldi.h / ps_host_ldi.h)
     bool ldi_ready = false;         // buffers allocated
     int ldi_n = 0, ldi_np = 0, ldi_kp = 0;

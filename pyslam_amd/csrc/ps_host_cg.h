@@ -389,6 +389,7 @@ int build_coarse(ps_problem* h) {
         for (int q = 0; q < ncb; ++q)
             for (int q2 = 0; q2 < ncb; ++q2)
                 if (sptr[(size_t)q * ncb + q2 + 1] > sptr[(size_t)q * ncb + q2]) h->ac_bw = std::max(h->ac_bw, std::abs(q - q2));
+        h->coarse_chol_bw = h->ac_bw;                       // (k_coarse_chol_band takes any width)
         if (h->ac_bw > PS_BAND_MAXB) h->ac_bw = -1;
         // More than 255 coarse nodes are only affordable with the BANDED factorisation (round-2 ADVICE): a coarse matrix
         // that turns out not to be banded (long loop closures) would take the dense one at ~4x the work and ~7 nc^2
@@ -401,6 +402,8 @@ int build_coarse(ps_problem* h) {
             h->upload(&h->ent_hi, ehi) || h->upload(&h->seg_ptr, sptr) || h->upload(&h->seg_ent, sent) ||
             h->upload(&h->seg_row, srow)) return -1;
     }
+    // the folded path's A_c through coarse_factor's LDS branch: its block half-bandwidth for k_coarse_chol_band
+    if (!h->cg_explicit) h->coarse_chol_bw = ncb * D <= 90 ? ps_coarse_band(ncb, slo.data(), shi.data(), rlo.data(), rhi.data()) : ncb - 1;
     lap("runs");
     h->ncb = ncb; h->nc = ncb * D; h->nr_aug = nr + ncb; h->nnzb_aug = (int)aci.size();
     if (h->upload(&h->pnode, pnode) || h->upload(&h->slo, slo) || h->upload(&h->shi, shi) ||
@@ -628,6 +631,13 @@ int coarse_factor(ps_problem* h, hipStream_t st, int buf, int32_t* stat) {
     const int nc = h->nc, ncb = h->ncb;
     if (nc <= 90) {                                        // 2 nc^2 doubles of dynamic LDS (<= 130 KB)
         const size_t chol_lds = 2 * (size_t)nc * nc * sizeof(double);
+        if (h->coarse_chol_band) {                         // the structural zeros of A_c left out (same bits): ps_k_coarse.h
+            if (ensure_dynamic_lds((const void*)k_coarse_chol_band<D>, (size_t)(chol_lds))) return -1;
+            hipLaunchKernelGGL(k_coarse_chol_band<D>, dim3(1), dim3(PS_CCB_THREADS), chol_lds, st, ncb,
+                               std::min(std::max(h->coarse_chol_bw, 0), ncb - 1), (const double*)h->Ac, h->Lci2[buf], h->LciT2[buf], stat,
+                               (long long*)nullptr);
+            return 0;
+        }
         if (ensure_dynamic_lds((const void*)k_coarse_chol<D, true>, (size_t)(chol_lds))) return -1;
         hipLaunchKernelGGL((k_coarse_chol<D, true>), dim3(1), dim3(1024), chol_lds, st, ncb, h->Ac, h->Lci2[buf],
                            h->LciT2[buf], stat, nullptr);

@@ -136,6 +136,15 @@ __global__ __launch_bounds__(256) void k_xcoarse_matrix(
     Ac[(size_t)(q * D + e / D) * nc + q2 * D + e % D] = acc;
 }
 
+// Measurement build: phase clocks of the LDS-resident variant (load | factor loop | diagonal inverses | doubling levels | store),
+// thread 0's wall_clock64 (100 MHz) into the otherwise unused `gscratch` argument when the caller passes six words there
+// (ps_debug_coarse_chol_clocks).  The product build compiles none of it.
+#ifdef PS_MEASURE
+#define PS_CC_CLK(i) do { if (IN_LDS && gscratch && t == 0) ((long long*)gscratch)[i] = (long long)wall_clock64(); } while (0)
+#else
+#define PS_CC_CLK(i) do { } while (0)
+#endif
+
 // A_c = L_c L_c^T and Li = L_c^-1 by ONE workgroup, blocked by D x D (ncb block steps instead of
 // nc scalar steps), both matrices full row-major in LDS: 2 nc^2 doubles (nc <= 96).
 // Outputs Li and its transpose LiT (row-major, global) so later kernels read either coalesced.
@@ -155,6 +164,7 @@ __global__ __launch_bounds__(1024) void k_coarse_chol(int ncb, const double* __r
     double* sX = sL + nc * nc;                              // nc x nc: L^-1
     __shared__ double sRl[64 * 6];      // reciprocal diagonal of L
     const int t = threadIdx.x, nt = blockDim.x;
+    PS_CC_CLK(0);
     for (int k = t; k < nc * nc; k += nt) { sL[k] = A[k]; sX[k] = 0.0; }
     // Round 5: the serial part of a block step is the D x D Cholesky ALONE (reciprocal square roots, no division, ~150
     // instructions of one thread); the panel below it is solved row by row against L_JJ^T (one thread per row, in place: no
@@ -194,6 +204,7 @@ __global__ __launch_bounds__(1024) void k_coarse_chol(int ncb, const double* __r
         }
     };
     __syncthreads();
+    PS_CC_CLK(1);
     if (t == 0) factor_diag(0);
     for (int J = 0; J < ncb; ++J) {
         __syncthreads();
@@ -244,6 +255,7 @@ __global__ __launch_bounds__(1024) void k_coarse_chol(int ncb, const double* __r
     // intermediate T = L21 X11 of a pair is kept TRANSPOSED in that pair's (still unused) upper-right block of sX; the upper
     // triangle is dropped on the way out.
     __syncthreads();
+    PS_CC_CLK(2);
     for (int k = t; k < ncb * D; k += nt) {
         const int R = k / D, c = k % D;
         double col[D];
@@ -287,6 +299,7 @@ __global__ __launch_bounds__(1024) void k_coarse_chol(int ncb, const double* __r
     };
     for (int sg = 1, lg = 1; sg < ncb; sg *= 2, ++lg) {    // lg = log2(2 sg)
         __syncthreads();
+        if (sg == 1) PS_CC_CLK(3);
         if (IN_LDS) {
 #pragma unroll
             for (int u = 0; u < NEX; ++u) if (ei[u] >= 0) t_entry(ei[u], ej[u], sg, lg);
@@ -298,12 +311,215 @@ __global__ __launch_bounds__(1024) void k_coarse_chol(int ncb, const double* __r
         } else for (int idx = t; idx < nc * nc; idx += nt) x_entry(idx / nc, idx % nc, sg, lg);
     }
     __syncthreads();
+    PS_CC_CLK(4);
     for (int k = t; k < nc * nc; k += nt) {
         const int r = k / nc, c = k % nc;
         const double v = (c <= r) ? sX[k] : 0.0;
         Li[k] = v;
         LiT[(size_t)c * nc + r] = v;
     }
+    PS_CC_CLK(5);
+}
+
+// ---------------------------------------------------------------------------
+// The same factorisation for a BLOCK-BANDED A_c (option "coarse_chol_band"): block (q, q') of A_c = P^T S^ P is structurally
+// non-zero only if some pose of supp(q) has a run in supp(q') (ps_coarse_band.h: the host derives the block half-bandwidth
+// `bw` from the run tables) -- 3 of 12 at C3 --, and outside the band k_coarse_matrix leaves exactly +0.0.  Cholesky makes no
+// fill outside a band, so k_coarse_chol spends most of its multiply-adds and LDS reads on exact zeros:
+//   * a block step's panel and trailing update touch min(bw, ncb - J - 1) block rows, not ncb - J - 1;
+//   * T = L21 X11 of a doubling level has terms only where L21 is inside the band, and rows only for the first bw block rows of
+//     group 2; X21 = -X22 T has terms only for those rows of T.
+// Leaving them out changes no bit (finite input, successful factorisation): every sum starts at +0.0 and accumulates fma terms;
+// a term with a +0.0 factor is +-0, which leaves a non-zero partial sum as it is and +0.0 as +0.0; a - (+-0) = a; and an entry of
+// L outside the band stays +0.0 through the panel solve (rl > 0).  Every entry that is computed goes through k_coarse_chol's
+// operations in k_coarse_chol's order (tests/test_gpu_coarse_chol_band.py holds the two kernels together bit for bit);
+// bw = ncb - 1 is the dense matrix.  A non-positive or NaN pivot is reported through ST_DIAG_FAIL as there.
+// With a quarter of the work per step the factor loop is ONE wave's (wave barriers only: no workgroup barrier inside the loop;
+// the other waves wait at the barrier behind it), only the band of A is loaded, nothing is cleared (every entry that is read
+// was written), an entry's indices come from shifts and constant divisions, and both outputs are written row by row.
+// LDS-resident only (nc <= 90).  clk: measurement build's phase clocks (six words, thread 0), else NULL.
+// ---------------------------------------------------------------------------
+template <int D>
+PS_DEV void coarse_factor_diag(double* sL, double* sRl, int nc, int J, int32_t* __restrict__ status)
+{
+    // (k_coarse_chol's factor_diag, operation for operation)
+    double a[D][D], rl[D];
+    bool ok = true;
+#pragma unroll
+    for (int r = 0; r < D; ++r)
+#pragma unroll
+        for (int c = 0; c <= r; ++c) a[r][c] = sL[(J * D + r) * nc + J * D + c];
+#pragma unroll
+    for (int jj = 0; jj < D; ++jj) {
+        double d = a[jj][jj];
+#pragma unroll
+        for (int k = 0; k < jj; ++k) d -= a[jj][k] * a[jj][k];
+        if (!(d > 0.0)) { ok = false; d = 1.0; }
+        rl[jj] = ps_rsqrt(d);
+        a[jj][jj] = d * rl[jj];
+#pragma unroll
+        for (int r = jj + 1; r < D; ++r) {
+            double v = a[r][jj];
+#pragma unroll
+            for (int k = 0; k < jj; ++k) v -= a[r][k] * a[jj][k];
+            a[r][jj] = v * rl[jj];
+        }
+    }
+    if (!ok) atomicAdd(&status[ST_DIAG_FAIL], 1);
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+        sRl[J * D + r] = rl[r];
+#pragma unroll
+        for (int c = 0; c < D; ++c) sL[(J * D + r) * nc + J * D + c] = c <= r ? a[r][c] : 0.0;
+    }
+}
+
+// entry (a, b2) of the MB (MB + 1) / 2 trailing blocks of block step J, MB = the block rows the band reaches: v = sum_k L_IJ[a][k]
+// L_KJ[b2][k] from +0.0 with k ascending, then A_IK[a][b2] -= v -- k_coarse_chol's sums; all loads first
+template <int D, int MB>
+PS_DEV void coarse_trail_step(double* sL, int nc, int J, int a, int b2)
+{
+    double la[MB][D], lb[MB][D], tg[MB][MB];
+#pragma unroll
+    for (int r = 0; r < MB; ++r)
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            la[r][k] = sL[((J + 1 + r) * D + a) * nc + J * D + k];
+            lb[r][k] = sL[((J + 1 + r) * D + b2) * nc + J * D + k];
+        }
+#pragma unroll
+    for (int r = 0; r < MB; ++r)
+#pragma unroll
+        for (int s = 0; s <= r; ++s) tg[r][s] = sL[((J + 1 + r) * D + a) * nc + (J + 1 + s) * D + b2];
+#pragma unroll
+    for (int r = 0; r < MB; ++r)
+#pragma unroll
+        for (int s = 0; s <= r; ++s) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) v += la[r][k] * lb[s][k];
+            sL[((J + 1 + r) * D + a) * nc + (J + 1 + s) * D + b2] = tg[r][s] - v;
+        }
+}
+
+#define PS_CCB_THREADS 1024
+#define PS_CCB_CLK(i) do { if (clk && t == 0) clk[i] = (long long)wall_clock64(); } while (0)
+
+template <int D>
+__global__ __launch_bounds__(1024) void k_coarse_chol_band(int ncb, int bw, const double* __restrict__ A,
+                                                            double* __restrict__ Li, double* __restrict__ LiT,
+                                                            int32_t* __restrict__ status, long long* __restrict__ clk)
+{
+    constexpr int DD = D * D;
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int nc = ncb * D;
+    double* sL = sm;                                        // nc x nc: the band of A's lower triangle, overwritten by L
+    double* sX = sm + nc * nc;                              // nc x nc: L^-1 (T of a level in the upper triangle)
+    __shared__ double sRl[64 * 6];                          // reciprocal diagonal of L
+    const int t = threadIdx.x, nt = blockDim.x;
+    const int g = t >> 5, gl = t & 31, ng = nt >> 5;        // 32 lanes walk one matrix row
+    PS_CCB_CLK(0);
+    for (int i = g; i < nc; i += ng) {                      // block columns bi - bw .. bi of row i (the diagonal block whole)
+        const int j0 = (i / D - bw) * D;
+        for (int jo = gl; jo < (bw + 1) * D; jo += 32)
+            if (j0 + jo >= 0) sL[i * nc + j0 + jo] = A[(size_t)i * nc + j0 + jo];
+    }
+    __syncthreads();
+    PS_CCB_CLK(1);
+    if (t < 64) {
+        if (t == 0) coarse_factor_diag<D>(sL, sRl, nc, 0, status);
+        for (int J = 0; J < ncb; ++J) {
+            __builtin_amdgcn_wave_barrier();
+            const int mb = min(bw, ncb - J - 1);            // block rows below the diagonal that the band reaches
+            for (int row = t; row < mb * D; row += 64) {    // panel: k_coarse_chol's row recurrence
+                double* ar = sL + ((J + 1) * D + row) * nc + J * D;
+                double x[D];
+#pragma unroll
+                for (int c = 0; c < D; ++c) {
+                    double v = ar[c];
+#pragma unroll
+                    for (int k = 0; k < c; ++k) v -= x[k] * sL[(J * D + c) * nc + J * D + k];
+                    x[c] = v * sRl[J * D + c];
+                }
+#pragma unroll
+                for (int c = 0; c < D; ++c) ar[c] = x[c];
+            }
+            if (J + 1 == ncb) break;
+            __builtin_amdgcn_wave_barrier();
+            if (t < DD) {                                   // trailing update A_IK -= L_IJ L_KJ^T, J < K <= I <= J + mb: a lane per entry
+                const int a = t / D, b2 = t % D;
+                // (narrow bands: every operand of the step asked for before the first sum -- one trip to LDS instead of one per
+                //  block, the blocks' sums independent of one another; the sums themselves as below)
+                if (mb == 1) coarse_trail_step<D, 1>(sL, nc, J, a, b2);
+                else if (mb == 2) coarse_trail_step<D, 2>(sL, nc, J, a, b2);
+                else if (mb == 3) coarse_trail_step<D, 3>(sL, nc, J, a, b2);
+                else if (mb == 4) coarse_trail_step<D, 4>(sL, nc, J, a, b2);
+                else for (int I = J + 1; I <= J + mb; ++I) {
+                    double la[D];
+#pragma unroll
+                    for (int k = 0; k < D; ++k) la[k] = sL[(I * D + a) * nc + J * D + k];
+                    for (int K = J + 1; K <= I; ++K) {
+                        double v = 0.0;
+#pragma unroll
+                        for (int k = 0; k < D; ++k) v += la[k] * sL[(K * D + b2) * nc + J * D + k];
+                        sL[(I * D + a) * nc + K * D + b2] -= v;
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (t == 0) coarse_factor_diag<D>(sL, sRl, nc, J + 1, status);
+        }
+    }
+    __syncthreads();
+    PS_CCB_CLK(2);
+    for (int k = t; k < ncb * D; k += nt) {                 // the diagonal blocks' inverses: k_coarse_chol's column recurrence
+        const int R = k / D, c = k % D;
+        double col[D];
+#pragma unroll
+        for (int r = 0; r < D; ++r) {
+            double v = (r == c) ? 1.0 : 0.0;
+#pragma unroll
+            for (int q = 0; q < r; ++q) v -= (q >= c) ? sL[(R * D + r) * nc + R * D + q] * col[q] : 0.0;
+            col[r] = (r >= c) ? v * sRl[R * D + r] : 0.0;
+            sX[(R * D + r) * nc + R * D + c] = col[r];
+        }
+    }
+    if (clk) { __syncthreads(); PS_CCB_CLK(3); }
+    // recursive doubling, level sg: the entries (i, jj) of every pair's lower-left block are items w = row * (sg D) + column --
+    // the rows are those of the block rows with bit sg set (nb2 of them), the columns the sg D of the row's group 1
+    for (int sg = 1, lg = 1; sg < ncb; sg *= 2, ++lg) {     // lg = log2(2 sg)
+        const int nb2 = (ncb >> lg) * sg + max(0, (ncb & (2 * sg - 1)) - sg);
+        const int cw = sg * D, items = nb2 * D * cw;
+        __syncthreads();
+        for (int w = t; w < items; w += nt) {               // T[i][j] = sum_{k >= j, k in group 1, inside the band} L[i][k] X11[k][j], kept transposed
+            const int rr = (w >> (lg - 1)) / D, jc = w - rr * cw, bq = rr / D;
+            const int bi = ((bq >> (lg - 1)) << lg) | sg | (bq & (sg - 1));
+            const int g0 = (bi >> lg) << lg, g1 = g0 + sg;  // first block of group 1, of group 2
+            if (bi - g1 >= bw) continue;                    // L21's block row is outside the band: T's row is +0.0 and nobody reads it
+            const int i = bi * D + (rr - bq * D), jj = g0 * D + jc, k1 = g1 * D;
+            double v = 0.0;
+            for (int k = max(jj, (bi - bw) * D); k < k1; ++k) v += sL[i * nc + k] * sX[k * nc + jj];
+            sX[jj * nc + i] = v;
+        }
+        __syncthreads();
+        for (int w = t; w < items; w += nt) {               // X21[i][j] = -sum_{k <= i, k in group 2, T's row k not +0.0} X22[i][k] T[k][j]
+            const int rr = (w >> (lg - 1)) / D, jc = w - rr * cw, bq = rr / D;
+            const int bi = ((bq >> (lg - 1)) << lg) | sg | (bq & (sg - 1));
+            const int g0 = (bi >> lg) << lg, g1 = g0 + sg;
+            const int i = bi * D + (rr - bq * D), jj = g0 * D + jc, kend = min(i, (g1 + bw) * D - 1);
+            double v = 0.0;
+            for (int k = g1 * D; k <= kend; ++k) v -= sX[i * nc + k] * sX[jj * nc + k];
+            sX[i * nc + jj] = v;
+        }
+    }
+    __syncthreads();
+    PS_CCB_CLK(4);
+    for (int i = g; i < nc; i += ng)                        // both outputs whole, zeros above the diagonal
+        for (int j = gl; j < nc; j += 32) {
+            Li[(size_t)i * nc + j] = (j <= i) ? sX[i * nc + j] : 0.0;
+            LiT[(size_t)i * nc + j] = (i <= j) ? sX[j * nc + i] : 0.0;
+        }
+    PS_CCB_CLK(5);
 }
 
 // ---------------------------------------------------------------------------

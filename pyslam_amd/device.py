@@ -572,6 +572,32 @@ def band_inverse(A, ncb, dof, bw, chunk_nodes=0):
     return out, us.value
 
 
+def coarse_chol(A, ncb, dof, bw, variant, timed=False):
+    """One launch of an LDS-resident coarse factorisation kernel on a host matrix (include/pyslam_hip.h: ps_debug_coarse_chol):
+    variant 0 k_coarse_chol, 1 k_coarse_chol_band as the solver launches it, 64 .. 1024 the band kernel with that many threads.
+    -> (Li, LiT, status words, GPU microseconds or None)."""
+    lib = nat.require_gpu()
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    n = ncb * dof
+    assert A.shape == (n, n)
+    Li, LiT, status = np.zeros((n, n)), np.zeros((n, n)), np.zeros(8, dtype=np.int32)
+    us = C.c_double(0.0)
+    nat.check(lib.ps_debug_coarse_chol(nat.f64p(A), ncb, dof, bw, variant, nat.f64p(Li), nat.f64p(LiT),
+                                       status.ctypes.data_as(nat.c_i32p), C.cast(C.byref(us), nat.c_f64p) if timed else None))
+    return Li, LiT, status, (us.value if timed else None)
+
+
+def coarse_chol_clocks(A, ncb, dof, bw, variant):
+    """Phase stamps of that launch in microseconds from kernel entry (measurement build: ps_debug_coarse_chol_clocks):
+    entry, loaded, factor loop, diagonal inverses, doubling levels, stored."""
+    lib = nat.require_gpu()
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    assert A.shape == (ncb * dof, ncb * dof)
+    clocks = np.zeros(6)
+    nat.check(lib.ps_debug_coarse_chol_clocks(nat.f64p(A), ncb, dof, bw, variant, nat.f64p(clocks)))
+    return clocks
+
+
 def dense_factor(A, dense_out=False, ld_extra=0, ainv_fill=0.0):
     """Every stage of the blocked dense factorisation chain on a host matrix (include/pyslam_hip.h: ps_debug_dense_factor).
     -> dict: L (working matrix), Tinv (steps x 24 x 24), Li, LiT, ainv (n x (n + ld_extra) float32, pre-filled with ainv_fill),
