@@ -10,7 +10,7 @@
 // one device block: [A: S, then Sigma (n^2) | L^-1 (n^2) | L^-T (n^2) | Tinv | diag (n) | pose out (nr D^2) | landmark out (9 nv) | stat]
 static size_t cov_layout(const ps_problem* h, size_t off[8]) {
     const size_t n = (size_t)h->nr * h->D, nn = n * n;
-    const size_t sizes[8] = {nn, nn, nn, (size_t)cdiv((long)n, PS_BC_W) * PS_BC_W * PS_BC_W, n, (size_t)h->nr * h->D * h->D,
+    const size_t sizes[8] = {nn, nn, nn, bchol_tinv_count((long)n), n, (size_t)h->nr * h->D * h->D,
                              (size_t)h->nv * 9, (size_t)ST_NWORDS};
     size_t at = 0;
     for (int k = 0; k < 8; ++k) { off[k] = at; at += (sizes[k] + 31) / 32 * 32; }     // (256-byte aligned pieces)

@@ -34,9 +34,8 @@ struct ps_dense {
     PsDenseLevel lv[PS_DENSE_MAX_LEVELS];
     size_t pix_total = 0, blocks_total = 0;
     std::vector<PsDenseSlot> slots;
-    std::vector<void*> allocs;
-    int64_t bytes = 0;
-    double* partials = nullptr;         // k_dense_pass partials (largest level)
+    DevMem mem{8};
+    double* partials = nullptr;       // k_dense_pass partials (largest level)
     int max_parts = 0;
     double* pose = nullptr;
     DenseSolveState* state = nullptr;
@@ -44,14 +43,6 @@ struct ps_dense {
     int hist_cap = 0;
     std::vector<double> h_results;
     double h_pose[12];
-    int alloc_bytes(void** p, size_t b) {
-        if (hipMalloc(p, std::max<size_t>(b, 8)) != hipSuccess) return fail("hipMalloc failed");
-        allocs.push_back(*p);
-        bytes += (int64_t)std::max<size_t>(b, 8);
-        return 0;
-    }
-    template <typename T> int alloc(T** p, size_t n) { return alloc_bytes((void**)p, n * sizeof(T)); }
-    ~ps_dense() { for (void* p : allocs) hipFree(p); }
 };
 }  // extern "C++"
 
@@ -106,15 +97,16 @@ int ps_dense_create(int32_t levels, int32_t max_height, int32_t max_width, int32
     dense_geometry(d.get(), max_height, max_width);
     const size_t P = d->pix_total, B = d->blocks_total;
     d->slots.resize(num_slots);
+    DevMem& M = d->mem;
     for (PsDenseSlot& s : d->slots) {
-        if (d->alloc_bytes(&s.raw, P * 8) || d->alloc(&s.imf, P) || d->alloc(&s.gx, P) || d->alloc(&s.gy, P) ||
-            d->alloc(&s.dl, P) || d->alloc(&s.depth0, (size_t)max_height * max_width) || d->alloc(&s.pt, 3 * P) ||
-            d->alloc(&s.imr, P) || d->alloc(&s.jac, 2 * P) || d->alloc(&s.tri, 3 * P) || d->alloc(&s.flags, P) ||
-            d->alloc(&s.counts, B) || d->alloc(&s.npix, PS_DENSE_MAX_LEVELS)) return -1;
+        if (M.alloc_bytes(&s.raw, P * 8) || M.alloc(&s.imf, P) || M.alloc(&s.gx, P) || M.alloc(&s.gy, P) ||
+            M.alloc(&s.dl, P) || M.alloc(&s.depth0, (size_t)max_height * max_width) || M.alloc(&s.pt, 3 * P) ||
+            M.alloc(&s.imr, P) || M.alloc(&s.jac, 2 * P) || M.alloc(&s.tri, 3 * P) || M.alloc(&s.flags, P) ||
+            M.alloc(&s.counts, B) || M.alloc(&s.npix, PS_DENSE_MAX_LEVELS)) return -1;
         HIP_OK(hipMemsetAsync(s.npix, 0, PS_DENSE_MAX_LEVELS * sizeof(int), d->stream));
     }
     d->max_parts = std::max(1, cdiv((long)max_height * max_width, 256 * PS_PHOTO_PPT));
-    if (d->alloc(&d->partials, (size_t)d->max_parts * PS_PHOTO_NACC) || d->alloc(&d->pose, 12) || d->alloc(&d->state, 1))
+    if (M.alloc(&d->partials, (size_t)d->max_parts * PS_PHOTO_NACC) || M.alloc(&d->pose, 12) || M.alloc(&d->state, 1))
         return -1;
     HIP_OK(hipStreamSynchronize(d->stream));
     *out = d.release();
@@ -222,11 +214,9 @@ int ps_dense_track(ps_dense* d, int32_t ref_slot, int32_t track_slot, int32_t nu
     if (hist > d->hist_cap) {                    // (the only allocation after create; freed with the handle)
         if (d->results) {
             HIP_OK(hipStreamSynchronize(d->stream));
-            hipFree(d->results);
-            d->allocs.erase(std::find(d->allocs.begin(), d->allocs.end(), (void*)d->results));
-            d->bytes -= (int64_t)std::max<size_t>(PS_DENSE_MAX_LEVELS * (2 + (size_t)d->hist_cap) * 8, 8);
+            d->mem.release(d->results);
         }
-        if (d->alloc(&d->results, PS_DENSE_MAX_LEVELS * per)) return -1;
+        if (d->mem.alloc(&d->results, PS_DENSE_MAX_LEVELS * per)) return -1;
         d->hist_cap = hist;
     }
     std::copy(pose12_in, pose12_in + 12, d->h_pose);
@@ -345,6 +335,6 @@ int ps_dense_read_tables(ps_dense* d, int32_t slot, int32_t level, int32_t num_p
 
 int ps_dense_device_bytes(ps_dense* d, int64_t* bytes) {
     if (!d || !bytes) return fail("null argument");
-    *bytes = d->bytes;
+    *bytes = d->mem.bytes();
     return 0;
 }

@@ -42,8 +42,8 @@ struct ps_feat {
     PsFeatFrame frame[3];
     int prev = -1, cur = -1;
     uint64_t clock = 0;
-    int64_t feature_passes = 0, bytes = 0;
-    std::vector<void*> allocs;
+    int64_t feature_passes = 0;
+    DevMem mem{16}, map_mem{16}, db_mem{16};    // what create allocates (and the map's claim words) | what grows with the map | the database
     // scratch of a feature pass and of a match
     long long *R = nullptr, *raw_R = nullptr;
     uint8_t *flags = nullptr, *keep = nullptr, *mflags = nullptr;
@@ -63,16 +63,13 @@ struct ps_feat {
     std::vector<uint8_t> h_map_out;         // its copy on the host: one download per match, read from there (a global match:
                                             // with the N second-best costs behind the cost array)
     unsigned long long* map_claim = nullptr;
-    std::vector<void*> map_allocs;          // the buffers that grow with the map
-    int64_t map_bytes = 0;
     // the keyframe database (step 10): entries are appended, never edited; nothing of it exists before the first ps_feat_db_add
     std::vector<int> db_start, db_len, db_block;   // per entry: first descriptor, length, first workgroup (db_block has K + 1 values)
-    int64_t db_n = 0, db_desc_cap = 0, db_bytes = 0;       // descriptors held, room for
+    int64_t db_n = 0, db_desc_cap = 0;                     // descriptors held, room for
     int db_block_cap = 0, db_entry_cap = 0;
     uint32_t* db_desc = nullptr;
     FeatDbBlock* db_blocks = nullptr;
     int *db_estart = nullptr, *db_elen = nullptr, *db_score = nullptr;
-    std::vector<void*> db_allocs;
     // room for n values where there was room for `cap` (doubling), the first `used` kept: the stream is idle when this is called
     template <typename T> int grow_db(T** p, int64_t used, int64_t cap, int64_t n, int64_t first_cap, int64_t* new_cap) {
         int64_t c = cap ? cap : first_cap;
@@ -80,51 +77,21 @@ struct ps_feat {
         *new_cap = c;
         if (c == cap) return 0;
         T* q = nullptr;
-        if (hipMalloc((void**)&q, (size_t)c * sizeof(T)) != hipSuccess) return fail("hipMalloc failed");
-        if (used && hipMemcpy(q, *p, (size_t)used * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) { hipFree(q); return fail("hipMemcpy failed"); }
-        if (*p) {
-            hipFree(*p);
-            db_allocs.erase(std::find(db_allocs.begin(), db_allocs.end(), (void*)*p));
-        }
-        db_allocs.push_back((void*)q);
-        const int64_t d = (c - cap) * (int64_t)sizeof(T);
-        db_bytes += d; bytes += d;
+        if (db_mem.alloc(&q, (size_t)c)) return -1;
+        if (used && hipMemcpy(q, *p, (size_t)used * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) { db_mem.release(q); return fail("hipMemcpy failed"); }
+        db_mem.release(*p);
         *p = q;
         return 0;
     }
-    int alloc_bytes(void** p, size_t b) {
-        if (hipMalloc(p, std::max<size_t>(b, 16)) != hipSuccess) return fail("hipMalloc failed");
-        allocs.push_back(*p);
-        bytes += (int64_t)std::max<size_t>(b, 16);
-        return 0;
-    }
-    template <typename T> int alloc(T** p, size_t n) { return alloc_bytes((void**)p, n * sizeof(T)); }
-    template <typename T> int alloc_map(T** p, size_t n) {
-        const size_t b = std::max<size_t>(n * sizeof(T), 16);
-        if (hipMalloc((void**)p, b) != hipSuccess) return fail("hipMalloc failed");
-        map_allocs.push_back((void*)*p);
-        map_bytes += (int64_t)b; bytes += (int64_t)b;
-        return 0;
-    }
-    void free_map() {
-        for (void* p : map_allocs) hipFree(p);
-        map_allocs.clear();
-        bytes -= map_bytes; map_bytes = 0; map_cap = 0;
-    }
+    void free_map() { map_mem.clear(); map_cap = 0; }
     static size_t map_out_bytes(size_t n, bool with_second) { return 16 + 28 * n + (with_second ? std::max<size_t>(4 * n, 16) : 0); }
     // the first global match: map_out makes room for the second-best costs (its contents are on the host already)
     int grow_map_out_for_second() {
-        void* old = map_cap ? map_out : nullptr;           // a map that never held a point has no block yet: room for the costs alone
-        const int64_t old_b = (int64_t)map_out_bytes(map_cap, false);
-        if (alloc_map(&map_out, old ? map_out_bytes(map_cap, true) : 16)) { map_out = (uint8_t*)old; return -1; }
-        if (old) {
-            hipFree(old);
-            map_allocs.erase(std::find(map_allocs.begin(), map_allocs.end(), old));
-            map_bytes -= old_b; bytes -= old_b;
-        }
+        uint8_t* old = map_cap ? map_out : nullptr;        // a map that never held a point has no block yet: room for the costs alone
+        if (map_mem.alloc(&map_out, old ? map_out_bytes(map_cap, true) : 16)) { map_out = old; return -1; }
+        map_mem.release(old);
         return 0;
     }
-    ~ps_feat() { for (void* p : db_allocs) hipFree(p); for (void* p : map_allocs) hipFree(p); for (void* p : allocs) hipFree(p); }
 };
 }  // extern "C++"
 
@@ -186,16 +153,17 @@ int ps_feat_create(int32_t max_height, int32_t max_width, int32_t max_features, 
     // non-maximum suppression with nms_n >= 1 leaves at most one feature in every aligned 2 x 2 block
     f->raw_cap = cdiv(max_height, 2) * cdiv(max_width, 2);
     const size_t P = (size_t)max_height * max_width, M = max_features, Rc = f->raw_cap;
+    DevMem& D = f->mem;
     for (PsFeatFrame& fr : f->frame)
         for (PsFeatImage& im : fr.im)
-            if (f->alloc(&im.img, P) || f->alloc(&im.du, P) || f->alloc(&im.dv, P) || f->alloc(&im.uv, M) || f->alloc(&im.R, M) ||
-                f->alloc(&im.desc, 8 * M) || f->alloc(&im.row_start, (size_t)max_height + 1) || f->alloc(&im.n, 1)) return -1;
-    if (f->alloc(&f->R, P) || f->alloc(&f->raw_R, Rc) || f->alloc(&f->flags, P) || f->alloc(&f->keep, Rc) || f->alloc(&f->mflags, M) ||
-        f->alloc(&f->counts, (size_t)cdiv((long)std::max(P, std::max(Rc, M)), 256) + 1) || f->alloc(&f->n_raw, 1) ||
-        f->alloc(&f->visited, 4 * M) || f->alloc(&f->idx4, 4 * M) || f->alloc(&f->n_match, 1) || f->alloc(&f->raw_uv, Rc) ||
-        f->alloc(&f->m8, 8 * M)) return -1;
+            if (D.alloc(&im.img, P) || D.alloc(&im.du, P) || D.alloc(&im.dv, P) || D.alloc(&im.uv, M) || D.alloc(&im.R, M) ||
+                D.alloc(&im.desc, 8 * M) || D.alloc(&im.row_start, (size_t)max_height + 1) || D.alloc(&im.n, 1)) return -1;
+    if (D.alloc(&f->R, P) || D.alloc(&f->raw_R, Rc) || D.alloc(&f->flags, P) || D.alloc(&f->keep, Rc) || D.alloc(&f->mflags, M) ||
+        D.alloc(&f->counts, (size_t)cdiv((long)std::max(P, std::max(Rc, M)), 256) + 1) || D.alloc(&f->n_raw, 1) ||
+        D.alloc(&f->visited, 4 * M) || D.alloc(&f->idx4, 4 * M) || D.alloc(&f->n_match, 1) || D.alloc(&f->raw_uv, Rc) ||
+        D.alloc(&f->m8, 8 * M)) return -1;
     for (int k = 0; k < 4; ++k)
-        if (f->alloc(&f->leg[k], M)) return -1;
+        if (D.alloc(&f->leg[k], M)) return -1;
     *out = f.release();
     return 0;
 }
@@ -300,14 +268,14 @@ int ps_feat_set_map(ps_feat* f, int32_t num_points, const double* points_w, cons
     if (num_points < 0 || num_points > (1 << 20)) return fail("num_points must be 0 .. 2^20");
     if (num_points > 0 && (!points_w || !descriptors)) return fail("null argument");
     hipStream_t s = f->stream;
-    if (!f->map_claim && f->alloc(&f->map_claim, (size_t)f->max_features)) return -1;
+    if (!f->map_claim && f->mem.alloc(&f->map_claim, (size_t)f->max_features)) return -1;
     if (num_points > f->map_cap) {
         HIP_OK(hipStreamSynchronize(s));                   // a match of the old map may still read its buffers
         f->free_map();
         f->map_set = false;
         const size_t n = num_points;
-        if (f->alloc_map(&f->map_pts, 3 * n) || f->alloc_map(&f->map_desc, 8 * n) ||
-            f->alloc_map(&f->map_out, ps_feat::map_out_bytes(n, f->map_global_used))) {
+        if (f->map_mem.alloc(&f->map_pts, 3 * n) || f->map_mem.alloc(&f->map_desc, 8 * n) ||
+            f->map_mem.alloc(&f->map_out, ps_feat::map_out_bytes(n, f->map_global_used))) {
             f->free_map();
             return -1;
         }
@@ -537,6 +505,6 @@ int ps_feat_feature_passes(ps_feat* f, int64_t* passes) {
 
 int ps_feat_device_bytes(ps_feat* f, int64_t* bytes) {
     if (!f || !bytes) return fail("null argument");
-    *bytes = f->bytes;
+    *bytes = f->mem.bytes() + f->map_mem.bytes() + f->db_mem.bytes();
     return 0;
 }

@@ -35,15 +35,16 @@ int ps_sim3pg_create(int32_t num_vertices, const double* vertices13, const uint8
     for (int e = 0; e < ne; ++e) s3g_host_inv(edge_obs13 + 13 * (size_t)e, obsinv.data() + 13 * (size_t)e);
     const size_t n = (size_t)h->n;
     const double zero5[5] = {};
-    if (h->upload(&h->verts, vertices13, (size_t)nv * 13) || h->upload(&h->verts_snap, vertices13, (size_t)nv * 13) ||
-        h->upload(&h->e_i, edge_i, (size_t)ne) || h->upload(&h->e_j, edge_j, (size_t)ne) ||
-        h->upload(&h->e_obsinv, (const double*)obsinv.data(), obsinv.size()) ||
-        (edge_stiffness49 && h->upload(&h->e_W, edge_stiffness49, (size_t)ne * 49)) ||
-        h->upload(&h->free_vid, (const int32_t*)free_vid.data(), free_vid.size()) ||
-        h->alloc(&h->scratch, (size_t)ne * PS_S3G_ROW) || h->alloc(&h->cost_part, (size_t)h->nwg) ||
-        h->alloc(&h->H, n * n) || h->alloc(&h->A, n * n) || h->alloc(&h->g, n) || h->alloc(&h->x, n) || h->alloc(&h->res, n) ||
-        h->alloc(&h->Tinv, (size_t)cdiv((long)n, PS_BC_W) * PS_BC_W * PS_BC_W) || h->alloc(&h->res_part, (size_t)2 * cdiv((long)n, 4)) ||
-        h->alloc(&h->dx_part, (size_t)h->nrt) || h->upload(&h->out, zero5, (size_t)5) || h->alloc(&h->stat, (size_t)ST_NWORDS) ||
+    DevMem& M = h->mem;
+    if (M.upload(&h->verts, vertices13, (size_t)nv * 13) || M.upload(&h->verts_snap, vertices13, (size_t)nv * 13) ||
+        M.upload(&h->e_i, edge_i, (size_t)ne) || M.upload(&h->e_j, edge_j, (size_t)ne) ||
+        M.upload(&h->e_obsinv, obsinv.data(), obsinv.size()) ||
+        (edge_stiffness49 && M.upload(&h->e_W, edge_stiffness49, (size_t)ne * 49)) ||
+        M.upload(&h->free_vid, free_vid.data(), free_vid.size()) ||
+        M.alloc(&h->scratch, (size_t)ne * PS_S3G_ROW) || M.alloc(&h->cost_part, (size_t)h->nwg) ||
+        M.alloc(&h->H, n * n) || M.alloc(&h->A, n * n) || M.alloc(&h->g, n) || M.alloc(&h->x, n) || M.alloc(&h->res, n) ||
+        M.alloc(&h->Tinv, bchol_tinv_count((long)n)) || M.alloc(&h->res_part, spd_part_count((long)n)) ||
+        M.alloc(&h->dx_part, (size_t)h->nrt) || M.upload(&h->out, zero5, (size_t)5) || M.alloc(&h->stat, (size_t)ST_NWORDS) ||
         s3g_build_structure(h.get(), rid, edge_i, edge_j)) return -1;
     HIP_OK(hipMemset(h->stat, 0, ST_NWORDS * sizeof(int32_t)));
     *out = h.release();
@@ -138,7 +139,7 @@ int ps_sim3pg_solve(ps_sim3pg* h, const ps_solve_options* options, double* cost_
 int ps_sim3pg_debug_edges(ps_sim3pg* h, double* tap105) {
     if (!h || !tap105) return fail("ps_sim3pg_debug_edges: null argument");
     if (h->ne == 0) return 0;
-    if (!h->dbg && h->alloc(&h->dbg, (size_t)h->ne * PS_S3G_DBG)) return -1;
+    if (!h->dbg && h->mem.alloc(&h->dbg, (size_t)h->ne * PS_S3G_DBG)) return -1;
     s3g_edges(h, 0, h->dbg);
     HIP_OK(hipMemcpyAsync(tap105, h->dbg, (size_t)h->ne * PS_S3G_DBG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
@@ -151,15 +152,11 @@ int ps_sim3pg_debug_explog(int32_t n, const double* xi_in, double* S13_out, doub
     if (n <= 0 || !xi_in || !S13_out || !xi_back || !adj49_out) return fail("ps_sim3pg_debug_explog: bad argument");
     if (need_device()) return -1;
     DevBuf bi, bs, bx, ba;
-    if (bi.get((size_t)n * 7 * 8) || bs.get((size_t)n * 13 * 8) || bx.get((size_t)n * 7 * 8) || ba.get((size_t)n * 49 * 8)) return -1;
-    HIP_OK(hipMemcpy(bi.p, xi_in, (size_t)n * 7 * 8, hipMemcpyHostToDevice));
+    if (bi.put(xi_in, (size_t)n * 7) || bs.get((size_t)n * 13 * 8) || bx.get((size_t)n * 7 * 8) || ba.get((size_t)n * 49 * 8)) return -1;
     hipLaunchKernelGGL(k_s3g_explog, dim3(cdiv(n, 256)), dim3(256), 0, 0, n, (const double*)bi.as<double>(), bs.as<double>(), bx.as<double>(),
                        ba.as<double>());
     HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpy(S13_out, bs.p, (size_t)n * 13 * 8, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(xi_back, bx.p, (size_t)n * 7 * 8, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(adj49_out, ba.p, (size_t)n * 49 * 8, hipMemcpyDeviceToHost));
-    return 0;
+    return bs.fetch(S13_out, (size_t)n * 13) || bx.fetch(xi_back, (size_t)n * 7) || ba.fetch(adj49_out, (size_t)n * 49) ? -1 : 0;
 }
 
 // measurement entry: enable != 0 times the stages of every later iteration with events; stage_ms5 (or NULL) receives the last

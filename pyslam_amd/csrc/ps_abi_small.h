@@ -91,19 +91,10 @@ int ps_ransac_frame_to_frame(const double* pts_1, const double* pts_2, const dou
 struct ps_photo {
     hipStream_t stream = nullptr;
     PhotoArgs args{};
-    std::vector<void*> allocs;
+    DevMem mem{0};
     double *pose = nullptr, *partials = nullptr, *out = nullptr;
     int nparts = 0;
     double h_out[PS_PHOTO_NOUT];
-    int upload(const double** dst, const double* src, size_t n) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(double)) != hipSuccess) return fail("hipMalloc failed");
-        allocs.push_back(p);
-        if (n && hipMemcpy(p, src, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy failed");
-        *dst = (const double*)p;
-        return 0;
-    }
-    ~ps_photo() { for (void* p : allocs) hipFree(p); }
 };
 
 namespace {
@@ -135,23 +126,19 @@ int ps_photometric_create(const ps_photo_desc* d, void* stream, ps_photo** out) 
     PhotoArgs& a = h->args;
     const size_t n = (size_t)d->num_pixels;
     a.n = d->num_pixels; a.h = d->height; a.w = d->width;
-    if (h->upload(&a.pt_ref, d->pt_ref, 3 * n) || h->upload(&a.im_ref, d->im_ref, n) ||
-        h->upload(&a.im_jac, d->im_jac, 2 * n) || h->upload(&a.tri_jac_d, d->tri_jac_d, 3 * n) ||
-        h->upload(&a.image, d->im_track, (size_t)d->height * d->width)) return -1;
+    DevMem& M = h->mem;
+    if (M.upload(&a.pt_ref, d->pt_ref, 3 * n) || M.upload(&a.im_ref, d->im_ref, n) ||
+        M.upload(&a.im_jac, d->im_jac, 2 * n) || M.upload(&a.tri_jac_d, d->tri_jac_d, 3 * n) ||
+        M.upload(&a.image, d->im_track, (size_t)d->height * d->width)) return -1;
     a.cu = d->cam[0]; a.cv = d->cam[1]; a.fu = d->cam[2]; a.fv = d->cam[3]; a.b = d->cam[4];
     a.cam_type = d->cam_type; a.cam_w = (double)d->cam_w; a.cam_h = (double)d->cam_h;
     a.var_i = d->intensity_covar; a.var_d = d->depth_covar;
     a.loss_id = d->loss_id; a.loss_k = d->loss_k;
     h->nparts = std::max(1, cdiv(d->num_pixels, 256 * PS_PHOTO_PPT));
     const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-    const double* tmp = nullptr;
-    if (h->upload(&tmp, ident, 12)) return -1;
-    h->pose = const_cast<double*>(tmp);
     std::vector<double> zeros((size_t)h->nparts * PS_PHOTO_NACC + PS_PHOTO_NOUT, 0.0);
-    if (h->upload(&tmp, zeros.data(), (size_t)h->nparts * PS_PHOTO_NACC)) return -1;
-    h->partials = const_cast<double*>(tmp);
-    if (h->upload(&tmp, zeros.data(), (size_t)PS_PHOTO_NOUT)) return -1;
-    h->out = const_cast<double*>(tmp);
+    if (M.upload(&h->pose, ident, 12) || M.upload(&h->partials, zeros.data(), (size_t)h->nparts * PS_PHOTO_NACC) ||
+        M.upload(&h->out, zeros.data(), (size_t)PS_PHOTO_NOUT)) return -1;
     *out = h.release();
     return 0;
 }
@@ -210,39 +197,52 @@ int ps_photometric_iteration(ps_photo* h, int32_t split_params, int32_t linesear
     return 0;
 }
 
+// ---- the two sparse solves' input: J and J^T in CSR on the device, and the right-hand side b = rhs or -J^T r ---------------
+extern "C++" {
+namespace {
+struct CsrPair {
+    DevBuf Jr, Jc, Jv, Tr, Tc, Tv, e, b;
+    static int check(int32_t m, int32_t n, const int32_t* j_row_ptr, const int32_t* j_col, const double* j_val, const int32_t* jt_row_ptr,
+                     const int32_t* jt_col, const double* jt_val, const double* r, const double* rhs, const double* dx) {
+        if (!j_row_ptr || !j_col || !j_val || !jt_row_ptr || !jt_col || !jt_val || !dx || m <= 0 || n <= 0 || (!r && !rhs))
+            return fail("bad argument");
+        return 0;
+    }
+    // after check(): the device, the two non-zero counts, the uploads, b (on stream st when it is formed from r)
+    int load(hipStream_t st, int32_t m, int32_t n, const int32_t* j_row_ptr, const int32_t* j_col, const double* j_val,
+             const int32_t* jt_row_ptr, const int32_t* jt_col, const double* jt_val, const double* r, const double* rhs) {
+        if (need_device()) return -1;
+        const size_t nnz = (size_t)j_row_ptr[m];
+        if ((size_t)jt_row_ptr[n] != nnz) return fail("J and its transpose have different numbers of non-zeros");
+        if (Jr.put(j_row_ptr, (size_t)m + 1) || Jc.put(j_col, nnz) || Jv.put(j_val, nnz) || Tr.put(jt_row_ptr, (size_t)n + 1) ||
+            Tc.put(jt_col, nnz) || Tv.put(jt_val, nnz)) return -1;
+        if (rhs) return b.put(rhs, (size_t)n);
+        if (e.put(r, (size_t)m) || b.get((size_t)n * 8)) return -1;
+        hipLaunchKernelGGL(k_sp_spmv, dim3(cdiv(n, 256)), dim3(256), 0, st, n, Tr.as<int32_t>(), Tc.as<int32_t>(), Tv.as<double>(),
+                           e.as<double>(), b.as<double>(), -1.0);
+        return 0;
+    }
+};
+}  // namespace
+}  // extern "C++"
+
 // ---- host-evaluated generic path at scale: CG on J^T J dx = rhs, J sparse in HBM (csrc/ps_sparse.h) -----------------
 int ps_sparse_normal_solve(int32_t m, int32_t n, const int32_t* j_row_ptr, const int32_t* j_col, const double* j_val,
                            const int32_t* jt_row_ptr, const int32_t* jt_col, const double* jt_val,
                            const double* r, const double* rhs, double tol, int32_t max_iters,
                            double* dx, int32_t* iters_out, double* relres_out) {
-    if (!j_row_ptr || !j_col || !j_val || !jt_row_ptr || !jt_col || !jt_val || !dx || m <= 0 || n <= 0 || (!r && !rhs))
-        return fail("bad argument");
-    if (need_device()) return -1;
-    const size_t nnz = (size_t)j_row_ptr[m];
-    if ((size_t)jt_row_ptr[n] != nnz) return fail("J and its transpose have different numbers of non-zeros");
-    DevBuf bJr, bJc, bJv, bTr, bTc, bTv, be, bb, bM, bx, br, bz, bp, bq, by, bpart, bsc;
-    const int nb = std::max(1, std::min(1024, cdiv(n, 256)));
-    if (bJr.get((size_t)(m + 1) * 4) || bJc.get(nnz * 4) || bJv.get(nnz * 8) || bTr.get((size_t)(n + 1) * 4) ||
-        bTc.get(nnz * 4) || bTv.get(nnz * 8) || be.get((size_t)m * 8) || bb.get((size_t)n * 8) || bM.get((size_t)n * 8) ||
-        bx.get((size_t)n * 8) || br.get((size_t)n * 8) || bz.get((size_t)n * 8) || bp.get((size_t)n * 8) ||
-        bq.get((size_t)n * 8) || by.get((size_t)m * 8) || bpart.get((size_t)nb * 8) || bsc.get(SPS_N * 8)) return -1;
-    HIP_OK(hipMemcpy(bJr.p, j_row_ptr, (size_t)(m + 1) * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bJc.p, j_col, nnz * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bJv.p, j_val, nnz * 8, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bTr.p, jt_row_ptr, (size_t)(n + 1) * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bTc.p, jt_col, nnz * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bTv.p, jt_val, nnz * 8, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(bsc.p, 0, SPS_N * 8));
+    if (CsrPair::check(m, n, j_row_ptr, j_col, j_val, jt_row_ptr, jt_col, jt_val, r, rhs, dx)) return -1;
     hipStream_t st = 0;
+    CsrPair J;
+    if (J.load(st, m, n, j_row_ptr, j_col, j_val, jt_row_ptr, jt_col, jt_val, r, rhs)) return -1;
+    DevBuf bM, bx, br, bz, bp, bq, by, bpart, bsc;
+    const int nb = std::max(1, std::min(1024, cdiv(n, 256)));
+    if (bM.get((size_t)n * 8) || bx.get((size_t)n * 8) || br.get((size_t)n * 8) || bz.get((size_t)n * 8) || bp.get((size_t)n * 8) ||
+        bq.get((size_t)n * 8) || by.get((size_t)m * 8) || bpart.get((size_t)nb * 8) || bsc.get(SPS_N * 8)) return -1;
+    HIP_OK(hipMemset(bsc.p, 0, SPS_N * 8));
     const int gm = cdiv(m, 256), gn = cdiv(n, 256);
-    if (rhs) HIP_OK(hipMemcpy(bb.p, rhs, (size_t)n * 8, hipMemcpyHostToDevice));
-    else {                                                          // rhs = -J^T r
-        HIP_OK(hipMemcpy(be.p, r, (size_t)m * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_sp_spmv, dim3(gn), dim3(256), 0, st, n, bTr.as<int32_t>(), bTc.as<int32_t>(), bTv.as<double>(),
-                           be.as<double>(), bb.as<double>(), -1.0);
-    }
-    hipLaunchKernelGGL(k_sp_diag, dim3(gn), dim3(256), 0, st, n, bTr.as<int32_t>(), bTv.as<double>(), bM.as<double>());
-    hipLaunchKernelGGL(k_sp_init, dim3(nb), dim3(256), 0, st, n, bb.as<double>(), bM.as<double>(), bx.as<double>(),
+    hipLaunchKernelGGL(k_sp_diag, dim3(gn), dim3(256), 0, st, n, J.Tr.as<int32_t>(), J.Tv.as<double>(), bM.as<double>());
+    hipLaunchKernelGGL(k_sp_init, dim3(nb), dim3(256), 0, st, n, J.b.as<double>(), bM.as<double>(), bx.as<double>(),
                        br.as<double>(), bz.as<double>(), bp.as<double>(), bpart.as<double>());
     hipLaunchKernelGGL(k_sp_scalars, dim3(1), dim3(256), 0, st, nb, bpart.as<double>(), bsc.as<double>(), (int)SPS_RZ, tol * tol, 1);
     double sc[SPS_N] = {};
@@ -251,9 +251,9 @@ int ps_sparse_normal_solve(int32_t m, int32_t n, const int32_t* j_row_ptr, const
         const int chunk = std::min(32, max_iters - launched);
         for (int k = 0; k < chunk; ++k, ++launched) {
             hipLaunchKernelGGL(k_sp_dir, dim3(nb), dim3(256), 0, st, n, bz.as<double>(), bp.as<double>(), bsc.as<double>());
-            hipLaunchKernelGGL(k_sp_spmv, dim3(gm), dim3(256), 0, st, m, bJr.as<int32_t>(), bJc.as<int32_t>(), bJv.as<double>(),
+            hipLaunchKernelGGL(k_sp_spmv, dim3(gm), dim3(256), 0, st, m, J.Jr.as<int32_t>(), J.Jc.as<int32_t>(), J.Jv.as<double>(),
                                bp.as<double>(), by.as<double>(), 1.0);
-            hipLaunchKernelGGL(k_sp_spmv, dim3(gn), dim3(256), 0, st, n, bTr.as<int32_t>(), bTc.as<int32_t>(), bTv.as<double>(),
+            hipLaunchKernelGGL(k_sp_spmv, dim3(gn), dim3(256), 0, st, n, J.Tr.as<int32_t>(), J.Tc.as<int32_t>(), J.Tv.as<double>(),
                                by.as<double>(), bq.as<double>(), 1.0);
             hipLaunchKernelGGL(k_sp_dot, dim3(nb), dim3(256), 0, st, n, bp.as<double>(), bq.as<double>(), bpart.as<double>());
             hipLaunchKernelGGL(k_sp_scalars, dim3(1), dim3(256), 0, st, nb, bpart.as<double>(), bsc.as<double>(), (int)SPS_PQ, tol * tol, 0);
@@ -261,10 +261,10 @@ int ps_sparse_normal_solve(int32_t m, int32_t n, const int32_t* j_row_ptr, const
                                bx.as<double>(), br.as<double>(), bz.as<double>(), bsc.as<double>(), bpart.as<double>());
             hipLaunchKernelGGL(k_sp_scalars, dim3(1), dim3(256), 0, st, nb, bpart.as<double>(), bsc.as<double>(), (int)SPS_RZ, tol * tol, 0);
         }
-        HIP_OK(hipMemcpy(sc, bsc.p, sizeof(sc), hipMemcpyDeviceToHost));
+        if (bsc.fetch(sc, (size_t)SPS_N)) return -1;
         if (sc[SPS_DONE] != 0.0) break;
     }
-    HIP_OK(hipMemcpy(dx, bx.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (bx.fetch(dx, (size_t)n)) return -1;
     if (iters_out) *iters_out = (int32_t)sc[SPS_ITERS];
     if (relres_out) *relres_out = sc[SPS_RZ0] > 0.0 ? std::sqrt(sc[SPS_RZ] / sc[SPS_RZ0]) : 0.0;
     if (sc[SPS_DONE] == 2.0) return fail("sparse normal-equation CG broke down (J^T J is not positive semi-definite to rounding, or a NaN in J)");
@@ -276,65 +276,42 @@ int ps_sparse_normal_solve(int32_t m, int32_t n, const int32_t* j_row_ptr, const
 int ps_sparse_normal_direct(int32_t m, int32_t n, const int32_t* j_row_ptr, const int32_t* j_col, const double* j_val,
                             const int32_t* jt_row_ptr, const int32_t* jt_col, const double* jt_val,
                             const double* r, const double* rhs, int32_t refine_steps, double* dx, double* relres_out) {
-    if (!j_row_ptr || !j_col || !j_val || !jt_row_ptr || !jt_col || !jt_val || !dx || m <= 0 || n <= 0 || (!r && !rhs))
-        return fail("bad argument");
+    if (CsrPair::check(m, n, j_row_ptr, j_col, j_val, jt_row_ptr, jt_col, jt_val, r, rhs, dx)) return -1;
     if (n > PS_SPD_MAXN) return fail("ps_sparse_normal_direct: more unknowns than the dense direct solve takes (8192)");
-    if (need_device()) return -1;
-    const size_t nnz = (size_t)j_row_ptr[m];
-    if ((size_t)jt_row_ptr[n] != nnz) return fail("J and its transpose have different numbers of non-zeros");
-    const int nsteps = cdiv(n, PS_BC_W), nb = cdiv(n, 4);
-    DevBuf bJr, bJc, bJv, bTr, bTc, bTv, be, bb, bH, bA, bTi, bx, bd, bres, bpart, bst;
-    if (bJr.get((size_t)(m + 1) * 4) || bJc.get(nnz * 4) || bJv.get(nnz * 8) || bTr.get((size_t)(n + 1) * 4) || bTc.get(nnz * 4) ||
-        bTv.get(nnz * 8) || be.get((size_t)m * 8) || bb.get((size_t)n * 8) || bH.get((size_t)n * n * 8) || bA.get((size_t)n * n * 8) ||
-        bTi.get((size_t)nsteps * PS_BC_W * PS_BC_W * 8) || bx.get((size_t)n * 8) || bd.get((size_t)n * 8) || bres.get((size_t)n * 8) ||
-        bpart.get((size_t)2 * nb * 8) || bst.get(ST_NWORDS * 4)) return -1;
-    HIP_OK(hipMemcpy(bJr.p, j_row_ptr, (size_t)(m + 1) * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bJc.p, j_col, nnz * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bJv.p, j_val, nnz * 8, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bTr.p, jt_row_ptr, (size_t)(n + 1) * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bTc.p, jt_col, nnz * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bTv.p, jt_val, nnz * 8, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(bst.p, 0, ST_NWORDS * 4));
     hipStream_t st = 0;
-    if (rhs) HIP_OK(hipMemcpy(bb.p, rhs, (size_t)n * 8, hipMemcpyHostToDevice));
-    else {
-        HIP_OK(hipMemcpy(be.p, r, (size_t)m * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_sp_spmv, dim3(cdiv(n, 256)), dim3(256), 0, st, n, bTr.as<int32_t>(), bTc.as<int32_t>(), bTv.as<double>(),
-                           be.as<double>(), bb.as<double>(), -1.0);
-    }
-    double* H = bH.as<double>();
-    double* A = bA.as<double>();
-    hipLaunchKernelGGL(k_spd_normal, dim3(cdiv((long)n * n, 256)), dim3(256), 0, st, n, bJr.as<int32_t>(), bJc.as<int32_t>(), bJv.as<double>(),
-                       bTr.as<int32_t>(), bTc.as<int32_t>(), bTv.as<double>(), H);
-    HIP_OK(hipMemcpyAsync(A, H, (size_t)n * n * 8, hipMemcpyDeviceToDevice, st));
+    CsrPair J;
+    if (J.load(st, m, n, j_row_ptr, j_col, j_val, jt_row_ptr, jt_col, jt_val, r, rhs)) return -1;
+    DevBuf bH, bA, bTi, bx, bres, bpart, bst;
+    std::vector<double> part(spd_part_count(n));
+    if (bH.get((size_t)n * n * 8) || bA.get((size_t)n * n * 8) || bTi.get(bchol_tinv_count(n) * 8) || bx.get((size_t)n * 8) ||
+        bres.get((size_t)n * 8) || bpart.get(part.size() * 8) || bst.get(ST_NWORDS * 4)) return -1;
+    HIP_OK(hipMemset(bst.p, 0, ST_NWORDS * 4));
+    double *H = bH.as<double>(), *b = J.b.as<double>(), *x = bx.as<double>(), *res = bres.as<double>();
+    hipLaunchKernelGGL(k_spd_normal, dim3(cdiv((long)n * n, 256)), dim3(256), 0, st, n, J.Jr.as<int32_t>(), J.Jc.as<int32_t>(), J.Jv.as<double>(),
+                       J.Tr.as<int32_t>(), J.Tc.as<int32_t>(), J.Tv.as<double>(), H);
+    HIP_OK(hipMemcpyAsync(bA.p, H, (size_t)n * n * 8, hipMemcpyDeviceToDevice, st));
     // blocked right-looking Cholesky over the whole chip (ps_host_bchol.h; substitutions through the factor, no inverse)
-    if (bchol_chain(st, n, BCHOL_FACTOR, A, bTi.as<double>(), bst.as<int32_t>(), nullptr, nullptr, nullptr, 0)) return -1;
-    auto solve_into = [&](double* v) {                         // v <- (L L^T)^-1 v
-        hipLaunchKernelGGL(k_spd_subst, dim3(1), dim3(512), 0, st, n, (const double*)A, (const double*)bTi.as<double>(), v, 0);
-        hipLaunchKernelGGL(k_spd_subst, dim3(1), dim3(512), 0, st, n, (const double*)A, (const double*)bTi.as<double>(), v, 1);
-    };
-    HIP_OK(hipMemcpyAsync(bx.p, bb.p, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-    solve_into(bx.as<double>());
-    std::vector<double> part((size_t)2 * nb);
+    const SpdSolve S{n, bA.as<double>(), bTi.as<double>(), bst.as<int32_t>()};
+    if (S.factor(st)) return -1;
+    HIP_OK(hipMemcpyAsync(x, b, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    S.solve_into(st, x);
     double rel = 0.0;
     for (int it = 0;; ++it) {                                  // residual of the original system; refine through the factor
-        hipLaunchKernelGGL(k_spd_residual, dim3(nb), dim3(256), 0, st, n, (const double*)H, (const double*)bb.as<double>(),
-                           (const double*)bx.as<double>(), bres.as<double>(), bpart.as<double>());
-        HIP_OK(hipMemcpy(part.data(), bpart.p, part.size() * 8, hipMemcpyDeviceToHost));
+        S.residual(st, H, b, x, res, bpart.as<double>());
+        if (bpart.fetch(part.data(), part.size())) return -1;
         double rr = 0.0, bbn = 0.0;
-        for (int k = 0; k < nb; ++k) { rr += part[2 * k]; bbn += part[2 * k + 1]; }
+        for (size_t k = 0; k < part.size(); k += 2) { rr += part[k]; bbn += part[k + 1]; }
         rel = bbn > 0.0 ? std::sqrt(rr / bbn) : 0.0;
         if (it >= refine_steps || !(rel > 1e-15)) break;
-        solve_into(bres.as<double>());
-        hipLaunchKernelGGL(k_spd_axpy, dim3(cdiv(n, 256)), dim3(256), 0, st, n, (const double*)bres.as<double>(), bx.as<double>());
+        S.solve_into(st, res);
+        S.add(st, res, x);
     }
     int32_t stw[ST_NWORDS];
-    HIP_OK(hipMemcpy(stw, bst.p, sizeof(stw), hipMemcpyDeviceToHost));
+    if (bst.fetch(stw, (size_t)ST_NWORDS)) return -1;
     if (relres_out) *relres_out = rel;
     // (a failed factor leaves NaNs in x: dx stays as the caller gave it)
     if (stw[ST_DIAG_FAIL]) return fail("normal matrix is not positive definite to rounding (dense direct solve)");
-    HIP_OK(hipMemcpy(dx, bx.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return 0;
+    return bx.fetch(dx, (size_t)n);
 }
 
 // ---- the band factorisation kernels on their own (csrc/ps_k_band.h, ps_k_bandpart.h): inverse of a symmetric positive definite
@@ -356,20 +333,17 @@ int ps_debug_factor_stress(const double* a, int32_t ncb, int32_t dof, int32_t bw
     if (mode == 2 && nc > 90) return fail("mode 2 (LDS-resident k_coarse_chol) needs ncb dof <= 90");
     DevBuf bA, bInv, bLr, bLc, brd, bXs, bst, bLi, bLiT, bsc, bTi, ga, gb;
     const size_t gn = (size_t)16 << 20;
-    if (bA.get((size_t)nc * nc * 8) || bInv.get((size_t)nc * nc * 4) || bst.get(ST_NWORDS * 4) || bLr.get((size_t)nc * PS_BAND_W * 8) ||
+    if (bA.put(a, (size_t)nc * nc) || bInv.get((size_t)nc * nc * 4) || bst.get(ST_NWORDS * 4) || bLr.get((size_t)nc * PS_BAND_W * 8) ||
         bLc.get((size_t)nc * PS_BAND_W * 8) || brd.get((size_t)nc * 8) || bXs.get((size_t)nc * nc * 8) || bLi.get((size_t)nc * nc * 8) ||
-        bLiT.get((size_t)nc * nc * 8) || bsc.get((size_t)2 * nc * nc * 8) || bTi.get((size_t)cdiv(nc, PS_BC_W) * PS_BC_W * PS_BC_W * 8) ||
+        bLiT.get((size_t)nc * nc * 8) || bsc.get((size_t)2 * nc * nc * 8) || bTi.get(bchol_tinv_count(nc) * 8) ||
         ga.get(gn * 8) || gb.get(gn * 8)) return -1;
-    HIP_OK(hipMemcpy(bA.p, a, (size_t)nc * nc * 8, hipMemcpyHostToDevice));
     HIP_OK(hipMemset(ga.p, 0, gn * 8));
     DevBuf bA1, bA2;
     hipEvent_t evp = nullptr;
     if (produce) {
         std::vector<double> a2((size_t)nc * nc);
         for (size_t k = 0; k < a2.size(); ++k) a2[k] = 2.0 * a[k];
-        if (bA1.get((size_t)nc * nc * 8) || bA2.get((size_t)nc * nc * 8)) return -1;
-        HIP_OK(hipMemcpy(bA1.p, a, (size_t)nc * nc * 8, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(bA2.p, a2.data(), (size_t)nc * nc * 8, hipMemcpyHostToDevice));
+        if (bA1.put(a, a2.size()) || bA2.put(a2.data(), a2.size())) return -1;
         HIP_OK(hipEventCreateWithFlags(&evp, hipEventDisableTiming));
     }
     struct EvGuard { hipEvent_t e; ~EvGuard() { if (e) hipEventDestroy(e); } } evg{evp};
@@ -426,8 +400,7 @@ int ps_debug_factor_stress(const double* a, int32_t ncb, int32_t dof, int32_t bw
     int32_t stw[ST_NWORDS];
     if (run(vs)) return -1;
     HIP_OK(hipStreamSynchronize(vs));
-    HIP_OK(hipMemcpy(ref.data(), bInv.p, ref.size() * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(stw, bst.p, sizeof(stw), hipMemcpyDeviceToHost));
+    if (bInv.fetch(ref.data(), ref.size()) || bst.fetch(stw, (size_t)ST_NWORDS)) return -1;
     if (stw[ST_DIAG_FAIL]) return fail("ps_debug_factor_stress: the input is not positive definite (idle reference run)");
     *n_diff = *n_pivot = 0;
     for (int k = 0; k < launches; ++k) {
@@ -439,8 +412,7 @@ int ps_debug_factor_stress(const double* a, int32_t ncb, int32_t dof, int32_t bw
         }
         if (run(vs)) return -1;
         HIP_OK(hipStreamSynchronize(vs));
-        HIP_OK(hipMemcpy(out.data(), bInv.p, out.size() * 4, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(stw, bst.p, sizeof(stw), hipMemcpyDeviceToHost));
+        if (bInv.fetch(out.data(), out.size()) || bst.fetch(stw, (size_t)ST_NWORDS)) return -1;
         if (std::memcmp(out.data(), ref.data(), out.size() * 4)) ++*n_diff;
         if (stw[ST_DIAG_FAIL]) ++*n_pivot;
     }
@@ -454,8 +426,7 @@ int ps_debug_band_inverse(const double* a, int32_t ncb, int32_t dof, int32_t bw,
     if (need_device()) return -1;
     const int nc = ncb * dof;
     DevBuf bA, bInv, bLr, bLc, brd, bXs, bst;
-    if (bA.get((size_t)nc * nc * 8) || bInv.get((size_t)nc * nc * 4) || bst.get(ST_NWORDS * 4)) return -1;
-    HIP_OK(hipMemcpy(bA.p, a, (size_t)nc * nc * 8, hipMemcpyHostToDevice));
+    if (bA.put(a, (size_t)nc * nc) || bInv.get((size_t)nc * nc * 4) || bst.get(ST_NWORDS * 4)) return -1;
     HIP_OK(hipMemset(bst.p, 0, ST_NWORDS * 4));
     HIP_OK(hipMemset(bInv.p, 0, (size_t)nc * nc * 4));
     hipStream_t st = 0;
@@ -498,8 +469,7 @@ int ps_debug_band_inverse(const double* a, int32_t ncb, int32_t dof, int32_t bw,
     HIP_OK(hipEventElapsedTime(&ms, e0, e1));
     if (elapsed_us) *elapsed_us = 1e3 * ms;
     int32_t stw[ST_NWORDS];
-    HIP_OK(hipMemcpy(stw, bst.p, sizeof(stw), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(ainv_out, bInv.p, (size_t)nc * nc * 4, hipMemcpyDeviceToHost));
+    if (bst.fetch(stw, (size_t)ST_NWORDS) || bInv.fetch(ainv_out, (size_t)nc * nc)) return -1;
     if (stw[ST_DIAG_FAIL]) return fail("band factorisation: the matrix is not positive definite");
     return 0;
 }
@@ -521,8 +491,7 @@ static int debug_coarse_chol(const double* a, int32_t ncb, int32_t dof, int32_t 
     if (need_device()) return -1;
     const size_t nn = (size_t)nc * nc;
     DevBuf bA, bLi, bLiT, bst, bck;
-    if (bA.get(nn * 8) || bLi.get(nn * 8) || bLiT.get(nn * 8) || bst.get(ST_NWORDS * 4) || bck.get(8 * 8)) return -1;
-    HIP_OK(hipMemcpy(bA.p, a, nn * 8, hipMemcpyHostToDevice));
+    if (bA.put(a, nn) || bLi.get(nn * 8) || bLiT.get(nn * 8) || bst.get(ST_NWORDS * 4) || bck.get(8 * 8)) return -1;
     hipStream_t st = nullptr;
     HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     struct St { hipStream_t s; ~St() { hipStreamDestroy(s); } } stg{st};
@@ -552,13 +521,11 @@ static int debug_coarse_chol(const double* a, int32_t ncb, int32_t dof, int32_t 
         HIP_OK(hipStreamSynchronize(st));
     }
     if (elapsed_us) { float ms = 0.f; HIP_OK(hipEventElapsedTime(&ms, e0, e1)); *elapsed_us = 1e3 * ms; }
-    HIP_OK(hipMemcpy(status, bst.p, ST_NWORDS * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(Li, bLi.p, nn * 8, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(LiT, bLiT.p, nn * 8, hipMemcpyDeviceToHost));
+    if (bst.fetch(status, (size_t)ST_NWORDS) || bLi.fetch(Li, nn) || bLiT.fetch(LiT, nn)) return -1;
     if (clocks) {
         long long c[6];
         int khz = 100000;
-        HIP_OK(hipMemcpy(c, bck.p, sizeof c, hipMemcpyDeviceToHost));
+        if (bck.fetch(c, (size_t)6)) return -1;
         HIP_OK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, 0));
         if (!c[3]) c[3] = c[2];                               // (a single block row: no doubling level stamps it)
         for (int k = 0; k < 6; ++k) clocks[k] = (double)(c[k] - c[0]) * 1e3 / khz;
@@ -589,14 +556,12 @@ int ps_debug_dense_factor(const double* a, int32_t n, int32_t flags, double* l_o
     if (!a || n <= 0 || (flags & ~0xff01)) return fail("ps_debug_dense_factor: bad argument");
     if (n > PS_SPD_MAXN) return fail("ps_debug_dense_factor: more than 8192 unknowns");
     if (need_device()) return -1;
-    const int ld = n + ((flags >> 8) & 0xff), nsteps = cdiv(n, PS_BC_W);
-    const size_t nn = (size_t)n * n, nti = (size_t)nsteps * PS_BC_W * PS_BC_W, ninv = (size_t)n * ld;
+    const int ld = n + ((flags >> 8) & 0xff);
+    const size_t nn = (size_t)n * n, nti = bchol_tinv_count(n), ninv = (size_t)n * ld;
     DevBuf bA0, bA, bTi, bLi, bLiT, bInv, bInv0, bst;
-    if (bA0.get(nn * 8) || bA.get(nn * 8) || bTi.get(nti * 8) || bLi.get(nn * 8) || bLiT.get(nn * 8) || bInv.get(ninv * 4) ||
-        bInv0.get(ninv * 4) || bst.get(ST_NWORDS * 4)) return -1;
-    HIP_OK(hipMemcpy(bA0.p, a, nn * 8, hipMemcpyHostToDevice));
-    if (ainv_out) HIP_OK(hipMemcpy(bInv0.p, ainv_out, ninv * 4, hipMemcpyHostToDevice));
-    else HIP_OK(hipMemset(bInv0.p, 0, ninv * 4));
+    if (bA0.put(a, nn) || bA.get(nn * 8) || bTi.get(nti * 8) || bLi.get(nn * 8) || bLiT.get(nn * 8) || bInv.get(ninv * 4) ||
+        (ainv_out ? bInv0.put(ainv_out, ninv) : bInv0.get(ninv * 4)) || bst.get(ST_NWORDS * 4)) return -1;
+    if (!ainv_out) HIP_OK(hipMemset(bInv0.p, 0, ninv * 4));
     hipStream_t st = nullptr;
     HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     struct St { hipStream_t s; ~St() { hipStreamDestroy(s); } } stg{st};
@@ -622,12 +587,8 @@ int ps_debug_dense_factor(const double* a, int32_t n, int32_t flags, double* l_o
     HIP_OK(hipEventElapsedTime(&ms, e0, e1));
     if (elapsed_us) *elapsed_us = 1e3 * ms;
     int32_t stw[ST_NWORDS];
-    HIP_OK(hipMemcpy(stw, bst.p, sizeof(stw), hipMemcpyDeviceToHost));
-    if (l_out) HIP_OK(hipMemcpy(l_out, bA.p, nn * 8, hipMemcpyDeviceToHost));
-    if (tinv_out) HIP_OK(hipMemcpy(tinv_out, bTi.p, nti * 8, hipMemcpyDeviceToHost));
-    if (li_out) HIP_OK(hipMemcpy(li_out, bLi.p, nn * 8, hipMemcpyDeviceToHost));
-    if (lit_out) HIP_OK(hipMemcpy(lit_out, bLiT.p, nn * 8, hipMemcpyDeviceToHost));
-    if (ainv_out) HIP_OK(hipMemcpy(ainv_out, bInv.p, ninv * 4, hipMemcpyDeviceToHost));
+    if (bst.fetch(stw, (size_t)ST_NWORDS) || (l_out && bA.fetch(l_out, nn)) || (tinv_out && bTi.fetch(tinv_out, nti)) ||
+        (li_out && bLi.fetch(li_out, nn)) || (lit_out && bLiT.fetch(lit_out, nn)) || (ainv_out && bInv.fetch(ainv_out, ninv))) return -1;
     if (diag_fail) *diag_fail = stw[ST_DIAG_FAIL];
     else if (stw[ST_DIAG_FAIL]) return fail("ps_debug_dense_factor: the matrix is not positive definite");
     return 0;
@@ -682,38 +643,22 @@ int ps_debug_ldi_gemm(int32_t M, int32_t N, int32_t K, float alpha, const float*
     if (need_device()) return -1;
     DevBuf bA, bB, bD, bC, bF, bK, bS;
     const size_t na = (size_t)M * lda, nb = (size_t)K * ldb, nd = (size_t)M * ldd, nc = (size_t)M * ldc;
-    if (bA.get(na * 4) || bB.get(nb * 4) || bC.get(nc * 4)) return -1;
-    HIP_OK(hipMemcpy(bA.p, A, na * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bB.p, B, nb * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bC.p, C, nc * 4, hipMemcpyHostToDevice));
+    if (bA.put(A, na) || bB.put(B, nb) || bC.put(C, nc)) return -1;
     const float* dD = nullptr;
     if (Dm == A && ldd == lda) dD = bA.as<float>();
     else if (Dm == B && ldd == ldb && M == K) dD = bB.as<float>();
     else if (Dm) {
-        if (bD.get(nd * 4)) return -1;
-        HIP_OK(hipMemcpy(bD.p, Dm, nd * 4, hipMemcpyHostToDevice));
+        if (bD.put(Dm, nd)) return -1;
         dD = bD.as<float>();
     }
-    if (fro_part) {
-        std::vector<double> f((size_t)mt * nt, fro_sentinel);
-        if (bF.get(f.size() * 8)) return -1;
-        HIP_OK(hipMemcpy(bF.p, f.data(), f.size() * 8, hipMemcpyHostToDevice));
-    }
-    if (krange) {
-        if (bK.get((size_t)mt * sizeof(int2))) return -1;
-        HIP_OK(hipMemcpy(bK.p, krange, (size_t)mt * sizeof(int2), hipMemcpyHostToDevice));
-    }
-    if (dev_scale) {
-        if (bS.get(4)) return -1;
-        HIP_OK(hipMemcpy(bS.p, dev_scale, 4, hipMemcpyHostToDevice));
-    }
+    const std::vector<double> f(fro_part ? (size_t)mt * nt : 0, fro_sentinel);
+    if ((fro_part && bF.put(f.data(), f.size())) || (krange && bK.put(krange, (size_t)2 * mt)) || (dev_scale && bS.put(dev_scale, (size_t)1)))
+        return -1;
     ldi_gemm(nullptr, 0, M, N, K, alpha, bA.as<float>(), lda, bB.as<float>(), ldb, beta, dD, ldd, gamma, bC.as<float>(), ldc,
              fro_part ? bF.as<double>() : nullptr, krange ? bK.as<int2>() : nullptr, upper_only ? 1 : 0, dev_scale ? bS.as<float>() : nullptr);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(0));
-    HIP_OK(hipMemcpy(C, bC.p, nc * 4, hipMemcpyDeviceToHost));
-    if (fro_part) HIP_OK(hipMemcpy(fro_part, bF.p, (size_t)mt * nt * 8, hipMemcpyDeviceToHost));
-    return 0;
+    return bC.fetch(C, nc) || (fro_part && bF.fetch(fro_part, f.size())) ? -1 : 0;
 }
 
 // k_ldi_ritz once on the coefficients of a CG of m iterations: rz[k] = r_k . z_k and alpha[k], what the solver's CG leaves in
@@ -728,13 +673,9 @@ int ps_debug_ldi_ritz(const double* rz, const double* alpha, int32_t m, float* o
     stw[ST_PCG_ITERS] = m;
     const float before[3] = {-1.f, -1.f, -1.f};               // (the kernel writes all three words whatever it finds)
     DevBuf bh, bs, bo;
-    if (bh.get(hist.size() * 8) || bs.get(sizeof(stw)) || bo.get(sizeof(before))) return -1;
-    HIP_OK(hipMemcpy(bh.p, hist.data(), hist.size() * 8, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bs.p, stw, sizeof(stw), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(bo.p, before, sizeof(before), hipMemcpyHostToDevice));
+    if (bh.put(hist.data(), hist.size()) || bs.put(stw, (size_t)ST_NWORDS) || bo.put(before, (size_t)3)) return -1;
     hipLaunchKernelGGL(k_ldi_ritz, dim3(1), dim3(64), 0, 0, (const double*)bh.as<double>(), cap, (const int32_t*)bs.as<int32_t>(), bo.as<float>());
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(0));
-    HIP_OK(hipMemcpy(out3, bo.p, sizeof(before), hipMemcpyDeviceToHost));
-    return 0;
+    return bo.fetch(out3, (size_t)3);
 }

@@ -1134,27 +1134,22 @@ int ps_get_stage_times(ps_problem* h, double* ms, int64_t* counts, int reset) {
 int ps_dense_normal_solve(const double* J, const double* r, int32_t m, int32_t n, double* dx, double* covariance) {
     if (!J || !r || !dx || m <= 0 || n <= 0) return fail("bad argument");
     if (n > 2048) return fail("generic (host-evaluated) path supports at most 2048 unknowns");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device visible");
+    if (need_device()) return -1;
     const int nrhs = covariance ? n + 1 : 1;
     DevBuf bJ, br, bH, bB, bst, bg;                   // scoped: released on every return path
-    if (bJ.get((size_t)m * n * sizeof(double)) || br.get((size_t)m * sizeof(double)) || bH.get((size_t)n * n * sizeof(double)) ||
-        bB.get((size_t)n * nrhs * sizeof(double)) || bst.get(ST_NWORDS * sizeof(int32_t)) || bg.get((size_t)n * sizeof(double))) return -1;
-    double *dJ = bJ.as<double>(), *dr = br.as<double>(), *dH = bH.as<double>(), *dB = bB.as<double>(), *dg = bg.as<double>();
-    int32_t* dst = bst.as<int32_t>();
-    HIP_OK(hipMemset(dst, 0, ST_NWORDS * sizeof(int32_t)));
-    HIP_OK(hipMemcpy(dJ, J, (size_t)m * n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(dr, r, (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_dense_normal, dim3(cdiv((long)n * n, 256)), dim3(256), 0, 0, m, n, dJ, dr, dH, dg);
+    if (bJ.put(J, (size_t)m * n) || br.put(r, (size_t)m) || bH.get((size_t)n * n * sizeof(double)) ||
+        bst.get(ST_NWORDS * sizeof(int32_t)) || bg.get((size_t)n * sizeof(double))) return -1;
+    HIP_OK(hipMemset(bst.p, 0, ST_NWORDS * sizeof(int32_t)));
+    hipLaunchKernelGGL(k_dense_normal, dim3(cdiv((long)n * n, 256)), dim3(256), 0, 0, m, n, bJ.as<double>(), br.as<double>(), bH.as<double>(),
+                       bg.as<double>());
     // B = [g | I]
     std::vector<double> B((size_t)n * nrhs, 0.0), gh(n);
-    HIP_OK(hipMemcpy(gh.data(), dg, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (bg.fetch(gh.data(), gh.size())) return -1;
     for (int i = 0; i < n; ++i) { B[(size_t)i * nrhs] = gh[i]; if (covariance) B[(size_t)i * nrhs + 1 + i] = 1.0; }
-    HIP_OK(hipMemcpy(dB, B.data(), B.size() * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_dense_chol_solve, dim3(1), dim3(256), 0, 0, n, nrhs, dH, dB, dst);
-    HIP_OK(hipMemcpy(B.data(), dB, B.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (bB.put(B.data(), B.size())) return -1;
+    hipLaunchKernelGGL(k_dense_chol_solve, dim3(1), dim3(256), 0, 0, n, nrhs, bH.as<double>(), bB.as<double>(), bst.as<int32_t>());
     int32_t st[ST_NWORDS];
-    HIP_OK(hipMemcpy(st, dst, sizeof(st), hipMemcpyDeviceToHost));
+    if (bB.fetch(B.data(), B.size()) || bst.fetch(st, (size_t)ST_NWORDS)) return -1;
     if (st[ST_DIAG_FAIL]) return fail("normal matrix is not positive definite");     // (dx and covariance stay as the caller gave them)
     for (int i = 0; i < n; ++i) {
         dx[i] = B[(size_t)i * nrhs];

@@ -161,6 +161,7 @@ PersistLedger& ps_persist_ledger() { static PersistLedger* p = new PersistLedger
 
 }  // namespace
 
+#include "ps_host_devmem.h"
 #include "ps_host_bandpart.h"
 #include "ps_host_bchol.h"
 #include "ps_options.h"

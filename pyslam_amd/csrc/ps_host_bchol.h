@@ -3,10 +3,10 @@
 //
 // Callers: the coarse level beyond 90 unknowns (coarse_factor, ps_host_cg.h: side stream), the lagged inverse's direct seed
 // (ldi_direct_enqueue, ps_host_ldi.h: its own stream), ps_covariance_marginals (ps_abi_cov.h: the handle's stream, with its
-// pivot check and a synchronisation between BCHOL_FACTOR and BCHOL_INVERSE), ps_sparse_normal_direct (ps_abi_small.h:
-// BCHOL_FACTOR only, substitutions instead of an inverse) and the test entries ps_debug_dense_factor / ps_debug_factor_stress
-// mode 4.  Streams, buffers and what runs between the stages stay with the caller; the order of launches and their grids
-// are here and nowhere else.
+// pivot check and a synchronisation between BCHOL_FACTOR and BCHOL_INVERSE), the test entries ps_debug_dense_factor /
+// ps_debug_factor_stress mode 4, and -- through SpdSolve below: BCHOL_FACTOR only, substitutions instead of an inverse --
+// ps_sparse_normal_direct (ps_abi_small.h) and the Sim(3) pose graph's s3g_iteration (ps_host_sim3pg.h).  Streams, buffers
+// and what runs between the stages stay with the caller; the order of launches and their grids are here and nowhere else.
 #pragma once
 
 enum {
@@ -63,3 +63,27 @@ inline int bchol_chain(hipStream_t st, int n, int stages, double* A, double* Tin
     if (stages & BCHOL_AINV) bchol_ainv(st, n, Li, Ainv, ld);
     return 0;
 }
+
+// doubles of Tinv (the inverses of the diagonal tiles) and of k_spd_residual's partials (r.r, b.b per workgroup) for n unknowns
+inline size_t bchol_tinv_count(long n) { return (size_t)cdiv(n, PS_BC_W) * PS_BC_W * PS_BC_W; }
+inline size_t spd_part_count(long n) { return (size_t)2 * cdiv(n, 4); }
+
+// The dense direct solve through the factor (kernels: ps_sparse.h): a view of the caller's buffers.  What is solved, how often
+// it is refined and who reads the residual's partials stay with the caller.
+struct SpdSolve {
+    int n;
+    double *A, *Tinv;              // A: factored in place; Tinv: bchol_tinv_count(n)
+    int32_t* stat;
+    int factor(hipStream_t st) const { return bchol_chain(st, n, BCHOL_FACTOR, A, Tinv, stat, nullptr, nullptr, nullptr, 0); }
+    void solve_into(hipStream_t st, double* v) const {     // v <- (L L^T)^-1 v
+        hipLaunchKernelGGL(k_spd_subst, dim3(1), dim3(512), 0, st, n, (const double*)A, (const double*)Tinv, v, 0);
+        hipLaunchKernelGGL(k_spd_subst, dim3(1), dim3(512), 0, st, n, (const double*)A, (const double*)Tinv, v, 1);
+    }
+    // res = b - H x with H the unfactored matrix; part: spd_part_count(n)
+    void residual(hipStream_t st, const double* H, const double* b, const double* x, double* res, double* part) const {
+        hipLaunchKernelGGL(k_spd_residual, dim3(cdiv(n, 4)), dim3(256), 0, st, n, H, b, x, res, part);
+    }
+    void add(hipStream_t st, const double* d, double* x) const {   // x += d
+        hipLaunchKernelGGL(k_spd_axpy, dim3(cdiv(n, 256)), dim3(256), 0, st, n, d, x);
+    }
+};

@@ -589,20 +589,6 @@ int gn_solve_and_finish_async(ps_problem* h, double tol, int max_iters, int line
 }  // namespace
 
 namespace {
-struct DevBuf {                      // scoped device allocation for the stateless entry points
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    int get(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8) == hipSuccess ? 0 : fail("hipMalloc failed"); }
-    template <class T> T* as() { return static_cast<T*>(p); }
-};
-int need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device visible");
-    return 0;
-}
-}  // namespace
-
-namespace {
 // ---- host threads for the structure pass of ps_problem_create (round 4: the O(N) loops over 5 M observations and 22 M pairs at
 // C4 were 0.6 s on one core) -------------------------------------------------------------------------------------------------
 inline int ps_host_threads(long items, int cap = 16) {

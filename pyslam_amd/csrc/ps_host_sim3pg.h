@@ -1,7 +1,8 @@
 // ps_host_sim3pg.h -- host driver of the Sim(3) pose graph (kernels: ps_k_sim3pg.h; C ABI: ps_abi_sim3pg.h).  Part of ps_core.hip
 // (inside its extern "C" block, after ps_abi_sim3.h).  A stand-alone handle, as ps_photo, ps_dense and ps_feat are: its own
-// tables, its own kernels, one stream.  The linear solve is the dense chain ps_sparse_normal_direct uses (ps_abi_small.h):
-// bchol_chain with BCHOL_FACTOR, two k_spd_subst, k_spd_residual on the unfactored copy, one refinement step.
+// tables, its own kernels, one stream.  The linear solve is SpdSolve (ps_host_bchol.h), as in ps_sparse_normal_direct:
+// factor() is bchol_chain(BCHOL_FACTOR), solve_into() two k_spd_subst, residual() k_spd_residual on the unfactored copy, add()
+// k_spd_axpy; one refinement step.
 //
 // One iteration, all on the handle's stream, one synchronisation at its end:
 //   k_s3g_edges -> k_s3g_assemble (H undamped, A = H with its diagonal times 1 + lambda, g) -> factor A -> x = A^-1 g ->
@@ -14,7 +15,7 @@ struct ps_sim3pg {
     int nv = 0, ne = 0, nfree = 0, n = 0, nwg = 0, nrt = 0, nslots = 0;
     int loss_id = 0;
     double loss_k = 0.0;
-    std::vector<void*> allocs;
+    DevMem mem{0, "ps_sim3pg: "};
     double *verts = nullptr, *verts_snap = nullptr, *e_obsinv = nullptr, *e_W = nullptr, *scratch = nullptr, *cost_part = nullptr;
     int32_t *e_i = nullptr, *e_j = nullptr, *free_vid = nullptr, *blockmap = nullptr, *eptr = nullptr, *gptr = nullptr, *gitems = nullptr;
     int2* eitems = nullptr;
@@ -26,22 +27,7 @@ struct ps_sim3pg {
     bool profiling = false;
     hipEvent_t ev[6] = {};
     double stage_ms[5] = {};         // edges, assemble, factor, substitute + refine, retract (+ the cost after): the last iteration's
-    template <typename T> int alloc(T** p, size_t count) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return fail("ps_sim3pg: hipMalloc failed");
-        allocs.push_back(q);
-        *p = (T*)q;
-        return 0;
-    }
-    template <typename T> int upload(T** p, const T* src, size_t count) {
-        if (alloc(p, count)) return -1;
-        if (count && hipMemcpy(*p, src, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return fail("ps_sim3pg: hipMemcpy failed");
-        return 0;
-    }
-    ~ps_sim3pg() {
-        for (void* p : allocs) hipFree(p);
-        for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
-    }
+    ~ps_sim3pg() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
 };
 
 namespace {
@@ -88,9 +74,10 @@ int s3g_build_structure(ps_sim3pg* h, const std::vector<int32_t>& rid, const int
     }
     for (int r = 0; r < nf; ++r) { gitems.insert(gitems.end(), gl[r].begin(), gl[r].end()); gptr.push_back((int32_t)gitems.size()); }
     h->nslots = (int)eptr.size() - 1;
-    if (h->upload(&h->blockmap, bm.data(), bm.size()) || h->upload(&h->eptr, eptr.data(), eptr.size()) ||
-        h->upload(&h->eitems, items.data(), items.size()) || h->upload(&h->gptr, gptr.data(), gptr.size()) ||
-        h->upload(&h->gitems, gitems.data(), gitems.size())) return -1;
+    DevMem& M = h->mem;
+    if (M.upload(&h->blockmap, bm.data(), bm.size()) || M.upload(&h->eptr, eptr.data(), eptr.size()) ||
+        M.upload(&h->eitems, items.data(), items.size()) || M.upload(&h->gptr, gptr.data(), gptr.size()) ||
+        M.upload(&h->gitems, gitems.data(), gitems.size())) return -1;
     return 0;
 }
 
@@ -142,23 +129,19 @@ int s3g_iteration(ps_sim3pg* h, double lambda, double* cost_after, double* dx_no
     const int n = h->n;
     hipStream_t st = h->stream;
     HIP_OK(hipMemsetAsync(h->stat, 0, ST_NWORDS * sizeof(int32_t), st));
-    if (bchol_chain(st, n, BCHOL_FACTOR, h->A, h->Tinv, h->stat, nullptr, nullptr, nullptr, 0)) return -1;
+    const SpdSolve S{n, h->A, h->Tinv, h->stat};
+    if (S.factor(st)) return -1;
     if (s3g_mark(h, 3)) return -1;
-    auto solve_into = [&](double* v) {                         // v <- (L L^T)^-1 v
-        hipLaunchKernelGGL(k_spd_subst, dim3(1), dim3(512), 0, st, n, (const double*)h->A, (const double*)h->Tinv, v, 0);
-        hipLaunchKernelGGL(k_spd_subst, dim3(1), dim3(512), 0, st, n, (const double*)h->A, (const double*)h->Tinv, v, 1);
-    };
     auto residual = [&]() {                                    // res = g - (H + lambda diag H) x; out[3], out[4] = res.res, g.g
-        hipLaunchKernelGGL(k_spd_residual, dim3(cdiv(n, 4)), dim3(256), 0, st, n, (const double*)h->H, (const double*)h->g,
-                           (const double*)h->x, h->res, h->res_part);
+        S.residual(st, h->H, h->g, h->x, h->res, h->res_part);
         hipLaunchKernelGGL(k_s3g_resid_fin, dim3(1), dim3(256), 0, st, n, (const double*)h->H, lambda, (const double*)h->x,
                            (const double*)h->g, h->res, h->out + 3);
     };
     HIP_OK(hipMemcpyAsync(h->x, h->g, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    solve_into(h->x);
+    S.solve_into(st, h->x);
     residual();
-    solve_into(h->res);                                        // one refinement step through the same factor
-    hipLaunchKernelGGL(k_spd_axpy, dim3(cdiv(n, 256)), dim3(256), 0, st, n, (const double*)h->res, h->x);
+    S.solve_into(st, h->res);                                  // one refinement step through the same factor
+    S.add(st, h->res, h->x);
     residual();
     if (s3g_mark(h, 4)) return -1;
     hipLaunchKernelGGL(k_s3g_retract, dim3(h->nrt), dim3(256), 0, st, h->nfree, (const int32_t*)h->free_vid, (const double*)h->x,

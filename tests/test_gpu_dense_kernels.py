@@ -426,6 +426,26 @@ def _track_good(t, seq):
     return t.track(0, 1, [2, 1, 0], [1, 0, 0], _options(), _loss(3, 10.), _pose12(np.eye(3), np.zeros(3)))
 
 
+def test_device_bytes_follow_the_history_buffer_exactly():
+    """The history buffer is the handle's only allocation after create: 8 levels x (2 + max_iters + 2) doubles.  max_iters 2,
+    then 6, then 3: the count grows by 8 x (6 - 2) x 8 = 256 bytes at the second call -- the old block's bytes come off as they
+    went on -- and stays at the third."""
+    seq = _good_pair()
+    t = _tracker(2, 96, 128)
+    try:
+        t.upload(0, seq['images'][0], seq['depth'][0])
+        t.upload(1, seq['images'][1])
+        t.make_tables(0, [1, 0], _cams(seq['cam'], [1, 0]), VAR, VAR, 0.1)
+        sizes = []
+        for m in (2, 6, 3):
+            t.track(0, 1, [1, 0], [0, 0], _options(max_iters=m), _loss(3, 10.), _pose12(np.eye(3), np.zeros(3)))
+            sizes.append(t.device_bytes())
+        print('device bytes after max_iters 2, 6, 3:', sizes)
+        assert sizes[1] - sizes[0] == 8 * (6 - 2) * 8 and sizes[2] == sizes[1], sizes
+    finally:
+        t.close()
+
+
 def _assert_same(a, b):
     assert np.array_equal(a[0], b[0]) and a[1] == b[1] and all(np.array_equal(x, y) for x, y in zip(a[2], b[2]))
 
